@@ -24,7 +24,8 @@ resident in HBM (generated on the device by kws_synth_clips_device).  N > 1: one
 `python bench.py --gpus N` without a launcher starts the N ranks itself (torch.distributed.run, 127.0.0.1).  Default clips
 per GPU: 65 536 (configs[1]); 131 072 at N = 8, i.e. BASELINE configs[2]'s 1 M clips over 8 GPUs.
 
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for how roofline / cpu_baseline are defined.
+Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for how roofline / cpu_baseline are defined.  --dump-outputs DIR: what the
+headline's last timed step computed (the scores of every clip) as DIR/scores.npy, for comparing two builds output for output.
 """
 import argparse
 import hashlib
@@ -288,6 +289,10 @@ class GpuBackend:
         # the probability mass of class 0 over every clip: unlike the plain sum (= the number of softmax rows) it depends on the scores
         return float(self.gathered[:, 0].double().sum().item())
 
+    def outputs(self):
+        """what a caller of the timed path holds after the last step: the per-clip scores (every rank's, once gathered)"""
+        return {"scores": self.gathered.cpu().numpy().copy()}
+
     def fallback(self):
         return self.model.fast_fallback_count()
 
@@ -363,6 +368,9 @@ class CpuOracleBackend:
     def checksum_class0(self):
         return float(self.gathered[:, 0].double().sum().item())
 
+    def outputs(self):
+        return {"scores": self.gathered.numpy().copy()}
+
     def fallback(self):
         return 0
 
@@ -398,7 +406,8 @@ def timed_steps(backend, steps, warmup, barrier, max_over_ranks, own=None):
 PREWARM_S = 0.3       # un-counted, time-based (clock ramp); the W warm-up and K timed steps that follow are exactly the ones asked for
 
 
-def measure(backend, model_path, mode, steps, warmup, barrier, max_over_ranks, gather_ranks=None, pcm=None):
+def measure(backend, model_path, mode, steps, warmup, barrier, max_over_ranks, gather_ranks=None, pcm=None, keep_outputs=False):
+    """keep_outputs: res["outputs"] holds what the last timed step computed (backend.outputs())"""
     info = backend.load(model_path, mode)
     if pcm is not None:
         backend.pcm_override = pcm
@@ -409,9 +418,35 @@ def measure(backend, model_path, mode, steps, warmup, barrier, max_over_ranks, g
     res = dict(info, model=os.path.basename(model_path), mode=mode, dt=dt, ms_path=ms_path, ms_gather=ms_gather, checksum=backend.checksum(), checksum0=backend.checksum_class0(),
                fallback=backend.fallback() if mode == "fast" else 0, exact_count=backend.exact_count() if mode == "fast" else 0,
                comm=backend.comm_info(), rank_dt=gather_ranks(own[0]) if gather_ranks else [own[0]])
+    if keep_outputs:
+        res["outputs"] = backend.outputs()
     backend.close_model()
     backend.pcm_override = None
     return res
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(outputs, directory):
+    """DIR/<name>.npy for every output array, float32 (float64 kept as it is).  Above DUMP_LIMIT_BYTES in all, every array keeps the same
+    fixed, seeded sample of its rows (sorted) and DIR/<name>_rows.npy (float64) says which rows they are.  -> {name: shape written}"""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32) for k, v in outputs.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, v in sorted(arrays.items()):
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(v.shape[0] * DUMP_LIMIT_BYTES // (2 * total)))     # half the budget: room for the row indices
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(v.shape[0], keep, replace=False))
+            v = v[rows]
+            np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+            written[name + "_rows"] = [int(keep)]
+        np.save(os.path.join(directory, name + ".npy"), v)
+        written[name] = list(v.shape)
+    return written
 
 
 def pmc_for(kernels, model, batch, mode="fast"):
@@ -448,8 +483,12 @@ def main():
                     help="create the RCCL communicator and all-gather the scores even with one rank (the N > 1 path on a 1-GPU box)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="no GPU: the oracle stands in for the library and gloo for RCCL (exercises sharding, gather and timing code)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step computed (the per-clip scores, every rank's) as DIR/scores.npy")
     ap.add_argument("--cpu-worker", nargs=4, metavar=("KIND", "N_CLIPS", "SECONDS", "FIRST_CLIP"))
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.cpu_worker:
         cpu_worker(a.cpu_worker[0], int(a.cpu_worker[1]), float(a.cpu_worker[2]), a.model, int(a.cpu_worker[3]))
         return
@@ -516,7 +555,9 @@ def main():
             dist.broadcast_object_list(ids, src=0)
             backend.make_comm(ids[0])
 
-    r = measure(backend, a.model, a.mode, a.steps, a.warmup, barrier, max_over_ranks, gather_ranks)
+    keep = bool(a.dump_outputs) and rank == 0                      # rank 0 holds every rank's scores once they are gathered
+    r = measure(backend, a.model, a.mode, a.steps, a.warmup, barrier, max_over_ranks, gather_ranks, keep_outputs=keep)
+    dumped = dump_outputs(r.pop("outputs"), a.dump_outputs) if keep else None
     others, also, int8_exact, inputs, dsp_shapes = [], [], None, [], []
     if world == 1 and not a.no_also and not a.dry_run_cpu:
         side_steps = max(20, a.steps // 8)
@@ -692,6 +733,8 @@ def main():
                                              traffic_per_kernel=out["int8_exact"]["traffic_per_kernel"])
     if cpu is not None:
         out["cpu_baseline"] = cpu
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped, "of": "the headline's last timed step"}
     emit(out, a)
 
 

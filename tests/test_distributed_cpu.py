@@ -117,6 +117,45 @@ def test_bench_spawns_its_own_ranks():
     assert c["ranks_seen_by_rccl"] is None and c["gloo_world_size"] == 2
 
 
+def test_bench_dump_outputs_are_the_last_steps_scores(tmp_path, oracle):
+    """--dump-outputs DIR: after exactly --steps timed steps, DIR/scores.npy holds the float32 scores of the global batch (every rank's,
+    gathered), the same from run to run; ms_per_step is the time of one of those steps.  --dry-run-cpu: the oracle stands in for the GPU."""
+    import json
+    import subprocess
+    from kws_testlib import OracleModel
+    model = os.path.join(MODELS, "l476_no_yes.kwsm")
+    env = dict(os.environ, MASTER_PORT=str(37500 + os.getpid() % 2000))
+    env.pop("WORLD_SIZE", None)
+    dumps = []
+    for run, steps in enumerate((2, 3)):
+        d = str(tmp_path / ("run%d" % run))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-cpu", "--steps", str(steps), "--warmup", "1",
+                              "--batch", "4", "--model", model, "--mode", "exact", "--dump-outputs", d],
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        j = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
+        assert j["steps"] == steps and j["ms_per_step"] > 0
+        assert abs(j["value"] - 8 / (j["ms_per_step"] * 1e-3)) < 1e-2 * j["value"]
+        assert sorted(os.listdir(d)) == ["scores.npy"]
+        dumps.append(np.load(os.path.join(d, "scores.npy")))
+    want = OracleModel(oracle, model).run_batch(oracle.synth(0, 0, 8))
+    for s in dumps:
+        assert s.dtype == np.float32 and s.shape == (8, 4) and (s == want).all()
+
+
+def test_bench_dump_outputs_sample_above_the_limit(tmp_path):
+    """Above the 64 MB cap the dump keeps a fixed, seeded sample of rows and says which (float64 row indices)."""
+    import bench
+    x = np.arange(24 << 20, dtype=np.float32).reshape(-1, 4)    # 96 MB
+    w = bench.dump_outputs({"scores": x}, str(tmp_path))
+    s, rows = np.load(str(tmp_path / "scores.npy")), np.load(str(tmp_path / "scores_rows.npy"))
+    assert rows.dtype == np.float64 and s.dtype == np.float32 and w["scores"] == list(s.shape)
+    assert s.nbytes + rows.nbytes <= bench.DUMP_LIMIT_BYTES and (s == x[rows.astype(np.int64)]).all()
+    assert (np.diff(rows) > 0).all()
+    bench.dump_outputs({"scores": x}, str(tmp_path / "again"))
+    assert (np.load(str(tmp_path / "again" / "scores_rows.npy")) == rows).all()
+
+
 def test_rendezvous_port_is_asked_of_the_kernel():
     """bench.py --gpus N without a launcher takes MASTER_PORT when set, otherwise a port the kernel reports free (round 3's pid-derived
     port could collide)"""
