@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "kws_extract_mfcc_batch_device", "kws_run_inference_batch_device", "kws_mfcc_batch_device",
     "kws_cmvn_inference_batch_device", "kws_nn_batch_device", "kws_nn_batch",
     "kws_streams_create", "kws_streams_destroy", "kws_streams_init", "kws_streams_step_device",
+    "kws_scan_window_count", "kws_scan_recordings_device",
     "kws_extract_mfe_batch_device", "kws_set_mode", "kws_get_mode", "kws_fast_is_fused", "kws_fast_fallback_count", "kws_fast_exact_count", "kws_fast_guard",
     "kws_set_logits_tap", "kws_fast_gain", "kws_fast_tolerance_info",
     "kws_comm_unique_id", "kws_comm_create", "kws_comm_world_size", "kws_comm_rank", "kws_comm_ranks_seen", "kws_comm_rccl_version", "kws_comm_wait", "kws_allgather_scores", "kws_comm_destroy",
@@ -156,6 +157,9 @@ def lib():
         L.kws_streams_destroy.argtypes = [vp]
         L.kws_streams_init.argtypes = [vp]
         L.kws_streams_step_device.argtypes = [vp, vp, sz, vp, vp, C.POINTER(C.c_int), vp]
+        if hasattr(L, "kws_scan_recordings_device"):
+            L.kws_scan_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
+            L.kws_scan_recordings_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
         L.kws_device_malloc.argtypes = [C.POINTER(vp), sz]
         L.kws_device_free.argtypes = [vp]
         L.kws_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -332,6 +336,22 @@ class Model:
 
     def nn_batch_device(self, q_ptr, B, scores_ptr, stream=None):
         _check(self.L.kws_nn_batch_device(self.h, q_ptr, B, scores_ptr, None, None, None, stream))
+
+    # ---- continuous mode over whole recordings (kws_scan_*; the parity contract is in include/kws/kws.h) ---------------------
+    def scan_window_count(self, n_samples, slice_samples=None):
+        """windows one recording of n_samples yields in continuous mode (slice_samples: clip_samples / 4 by default)"""
+        n = C.c_size_t()
+        _check(self.L.kws_scan_window_count(self.h, n_samples, slice_samples or self.clip_samples // 4, C.byref(n)))
+        return n.value
+
+    def scan_recordings_device(self, pcm_ptr, offsets, lengths, scores_ptr, raw_scores_ptr=None, slice_samples=None, stream=None):
+        """every window of R recordings (int16 at pcm_ptr + offsets[r], lengths[r] samples; device) in one call: scores (and raw_scores)
+        [sum of the recordings' window counts][labels], device.  offsets / lengths: host sequences."""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        _check(self.L.kws_scan_recordings_device(self.h, pcm_ptr, _p(off), _p(ln), off.size, slice_samples or self.clip_samples // 4,
+                                                 scores_ptr, raw_scores_ptr, stream))
 
 
 class StreamBatch:

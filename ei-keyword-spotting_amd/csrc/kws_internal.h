@@ -242,6 +242,10 @@ struct kws_handle {
                                   // for both -- the features are then the ones kws_extract_mfcc_batch_device returns -- and the fused launch's goes here
     float *tap_logits = nullptr;  // kws_set_logits_tap: FULLY_CONNECTED outputs of the batch calls' clips (float32 graphs), device [B][labels]
     float *s_cep = nullptr;       // [B][n_features] exact cepstra of the first tier's clips (indexed by clip)
+    // kws_scan.cpp: the bounded scratch of kws_scan_recordings_device and the cepstral rows of its last call; kws_destroy frees it through
+    // scan_release (set with it)
+    struct KwsScanScratch *scan = nullptr;
+    void (*scan_release)(kws_handle *) = nullptr;
     size_t flags_cap = 0, cep_cap = 0;
 
     template <typename T> EI_IMPULSE_ERROR upload(const std::vector<T> &v, const T **out)

@@ -1,0 +1,218 @@
+// kws_scan.cpp -- whole recordings in continuous mode (kws_scan_window_count, kws_scan_recordings_device; contract in include/kws/kws.h).
+//
+// A fresh kws_stream_batch fed one recording slice by slice writes slice 0's nf0 cepstral rows, then nf1 rows per slice, into one
+// rolling buffer; from the step where the buffer is full (ring_rows rows written) every step produces a window.  Read as one contiguous
+// row array per recording, window w is rows [w nf1, w nf1 + ring_rows) followed by the rows the reference never writes (zeros).  The
+// rows of a slice depend only on its own samples and its wrap sample, so every slice of the call is independent work:
+//   1. front end: slices copied from the recordings into aligned rows (kws_scan_stage_kernel), then the spectral kernels the stream API
+//      runs (spectral_device) -- slice 0 of every recording into first_rows [A][nf0][cols], the slices k >= 1 into slot_rows, nf1 rows
+//      each, recording after recording: together the contiguous row arrays;
+//   2. windows gathered in chunks into [chunk][F] (kws_scan_gather_kernel) for the stream API's cmvnw + network (cmvn_nn_device, or
+//      cmvn_nn_fast_device in KWS_MODE_FAST), which write each window's raw scores in place;
+//   3. the moving average per (recording, label) over its windows in order (kws_scan_maf_kernel).
+// A = the recordings of the call that produce at least one window; the others need no work.
+#include "kws_internal.h"
+
+int kws_launch_scan_stage(const int16_t *pcm, const long long *off, const long long *len, const long long *ibase, int n_rec, long long item0, int n_items,
+                          int first, int slice, int grow, int16_t *stage, float *wrap, hipStream_t stream);
+int kws_launch_scan_gather(const float *first_rows, const float *slot_rows, const long long *wbase, const long long *ibase, int n_rec, long long win0,
+                           int n_win, int nf0, int nf1, int ring_rows, int rows, int ncols, float *out, hipStream_t stream);
+int kws_launch_scan_maf(const float *raw, float *scores, const long long *wbase, int n_rec, int labels, hipStream_t stream);
+int kws_launch_scan_count(int *flags, int *flags2, int *acc, int finish, hipStream_t stream);
+
+// bounded scratch of one call (include/kws/kws.h states the bound): staged slices and gathered windows
+static const size_t kScanStageBytes = (size_t)32 << 20;
+static const size_t kScanWindowBytes = (size_t)64 << 20;
+static const size_t kScanMaxItems = 16384, kScanMaxWindows = 32768;
+
+struct KwsScanScratch {
+    int16_t *stage = nullptr;
+    float *wrap = nullptr, *win = nullptr, *rows = nullptr;
+    long long *meta = nullptr;
+    int *acc = nullptr;
+    size_t stage_cap = 0, wrap_cap = 0, win_cap = 0, rows_cap = 0, meta_cap = 0, acc_cap = 0;
+};
+
+static void scan_release(kws_handle *h)
+{
+    KwsScanScratch *s = h->scan;
+    if (!s) return;
+    for (void *p : { (void *)s->stage, (void *)s->wrap, (void *)s->win, (void *)s->rows, (void *)s->meta, (void *)s->acc })
+        if (p) (void)hipFree(p);
+    delete s;
+    h->scan = nullptr;
+}
+
+// grows *p to at least n elements (synchronising the device first: the old buffer may still be in use by enqueued work)
+template <typename T>
+static EI_IMPULSE_ERROR grow(T **p, size_t *cap, size_t n)
+{
+    if (n <= *cap) return EI_IMPULSE_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
+    *cap = n;
+    return EI_IMPULSE_OK;
+}
+
+namespace {
+// The stream API's step rules (kws_streams_step_device) at this slicing, replayed on the host until they repeat.
+struct ScanLayout {
+    int nf0 = 0, nf1 = 0;          // frames of slice 0 / of every later slice
+    int ring_rows = 0;             // rows of the rolling buffer once it is full
+    size_t k_full = 0;             // the first step that produces a window
+    int grow = 0;                  // samples a grown slice claims beyond itself
+    size_t windows(size_t n_slices) const { return n_slices > k_full ? n_slices - k_full : 0; }
+};
+}
+
+static EI_IMPULSE_ERROR scan_layout(const kws_handle *h, size_t slice_samples, ScanLayout *L)
+{
+    const Model &m = h->model;
+    const size_t F = m.nn_input_frame_size;
+    const int frame_len = h->dsp.frame_len, stride = h->dsp.frame_stride, ncols = h->dsp.n_cepstral;
+    const size_t grown_by = (size_t)(m.dsp.frame_length * (float)m.frequency);
+    size_t slice_offset = 0;
+    bool full = false;
+    int ring_rows = 0;
+    L->grow = (int)grown_by;
+    for (size_t k = 0;; ++k) {
+        const size_t n_claimed = slice_samples + (k > 0 ? grown_by : 0);
+        const int nf = n_claimed >= (size_t)frame_len ? (int)floorf((float)(n_claimed - (size_t)frame_len) / (float)stride) : 0;
+        const size_t feature_size = (size_t)(nf > 0 ? nf : 0) * (size_t)ncols;
+        if (nf < 1 || (!h->dsp.generic && nf > kws_mfcc_max_frames(h->dsp.n_filters)) || feature_size > F || slice_offset + feature_size > F ||
+            (size_t)(nf - 1) * stride + std::min(h->dsp.fft_len, frame_len) > slice_samples || (!h->dsp.generic && (slice_samples * 2) % 16 != 0))
+            return fail(EI_IMPULSE_DSP_ERROR, "slice of %zu samples (claimed %zu) yields %d frames", slice_samples, n_claimed, nf);
+        const int row0 = (int)(slice_offset / (size_t)ncols);
+        if (ring_rows && row0 + nf != ring_rows)
+            return fail(EI_IMPULSE_DSP_ERROR, "slice of %d frames in a window laid out for slices of %d", nf, ring_rows - row0);
+        if (k == 0) L->nf0 = nf; else L->nf1 = nf;
+        if (full) break;                                   // a steady step has been checked: every later step is the same
+        slice_offset += feature_size;
+        if (slice_offset > F - feature_size) {
+            full = true;
+            slice_offset -= feature_size;
+            ring_rows = (int)((slice_offset + feature_size) / (size_t)ncols);
+            L->k_full = k;
+        }
+    }
+    L->ring_rows = ring_rows;
+    return EI_IMPULSE_OK;
+}
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+EI_IMPULSE_ERROR kws_scan_window_count(const kws_handle *h, size_t n_samples, size_t slice_samples, size_t *n_windows)
+{
+    if (!h || !n_windows) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    *n_windows = 0;
+    ScanLayout L;
+    EI_IMPULSE_ERROR e = scan_layout(h, slice_samples, &L);
+    if (e) return e;
+    *n_windows = L.windows(n_samples / slice_samples);
+    return EI_IMPULSE_OK;
+}
+
+EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                            size_t slice_samples, float *scores, float *raw_scores, void *stream)
+{
+    if (!h || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (R > 0 && (!pcm || !offsets || !lengths)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (R > 0x3fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "too many recordings");
+    ScanLayout L;
+    EI_IMPULSE_ERROR e = scan_layout(h, slice_samples, &L);
+    if (e) return e;
+    // the recordings that produce windows, and where their windows / slices go
+    std::vector<long long> off, len, wbase(1, 0), ibase(1, 0);
+    for (size_t r = 0; r < R; ++r) {
+        const size_t K = lengths[r] / slice_samples, W = L.windows(K);
+        if (!W) continue;
+        off.push_back((long long)offsets[r]);
+        len.push_back((long long)lengths[r]);
+        wbase.push_back(wbase.back() + (long long)W);
+        ibase.push_back(ibase.back() + (long long)(K - 1));
+    }
+    const int A = (int)off.size();
+    if (A == 0) return EI_IMPULSE_OK;
+    const size_t n_win = (size_t)wbase.back(), n_slots = (size_t)ibase.back();
+    const Model &m = h->model;
+    const size_t F = m.nn_input_frame_size, C = m.labels.size();
+    const int ncols = h->dsp.n_cepstral, rows = (int)(F / (size_t)ncols);
+    if (n_win * C > (size_t)1 << 40) return fail(KWS_ERROR_BAD_ARGUMENT, "too many windows");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->scan) { h->scan = new KwsScanScratch(); h->scan_release = scan_release; }
+    KwsScanScratch &S = *h->scan;
+    const size_t item_cap = std::max<size_t>(1, std::min(kScanMaxItems, kScanStageBytes / (slice_samples * sizeof(int16_t))));
+    const size_t win_chunk = std::min(std::max<size_t>(1, std::min(kScanMaxWindows, kScanWindowBytes / (F * sizeof(float)))), n_win);
+    const size_t first_floats = (size_t)A * L.nf0 * ncols, rows_floats = first_floats + n_slots * L.nf1 * ncols;
+    if ((e = grow(&S.stage, &S.stage_cap, item_cap * slice_samples)) || (e = grow(&S.wrap, &S.wrap_cap, item_cap)) ||
+        (e = grow(&S.win, &S.win_cap, win_chunk * F)) || (e = grow(&S.rows, &S.rows_cap, rows_floats)) ||
+        (e = grow(&S.meta, &S.meta_cap, 4 * (size_t)A + 2)) || (e = grow(&S.acc, &S.acc_cap, 1)) || (e = ensure_scratch(h, win_chunk)))
+        return e;
+    // scan calls write no logits tap (out of the tap's [B][labels] shape): the tap is set aside for the call
+    struct TapAside {
+        kws_handle *h; float *t;
+        ~TapAside() { h->tap_logits = t; }
+    } tap_aside{ h, h->tap_logits };
+    h->tap_logits = nullptr;
+    ScratchUse use(h, st);
+    // per-recording tables: off [A], len [A], wbase [A + 1], ibase [A + 1].  The host copy is complete before the call goes on
+    std::vector<long long> meta;
+    meta.reserve(4 * (size_t)A + 2);
+    meta.insert(meta.end(), off.begin(), off.end());
+    meta.insert(meta.end(), len.begin(), len.end());
+    meta.insert(meta.end(), wbase.begin(), wbase.end());
+    meta.insert(meta.end(), ibase.begin(), ibase.end());
+    HIP_TRY(hipMemcpyAsync(S.meta, meta.data(), meta.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const long long *d_off = S.meta, *d_len = S.meta + A, *d_wbase = S.meta + 2 * A, *d_ibase = S.meta + 3 * A + 1;
+    const int slice = (int)slice_samples;
+    float *first_rows = S.rows, *slot_rows = S.rows + first_floats;
+    // 1. front end: the stream API's spectral launches, on aligned copies of the slices
+    KwsDspPlan P0 = h->dsp, P1 = h->dsp;
+    P0.n_samples = P1.n_samples = slice;
+    P0.n_frames = L.nf0;
+    P1.n_frames = L.nf1;
+    for (size_t a0 = 0; a0 < (size_t)A; a0 += item_cap) {
+        const int n = (int)std::min(item_cap, (size_t)A - a0);
+        int rc = kws_launch_scan_stage(pcm, d_off, d_len, d_ibase, A, (long long)a0, n, 1, slice, L.grow, S.stage, S.wrap, st);
+        if (rc) return fail(KWS_ERROR_HIP, "scan staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if ((e = spectral_device(h, P0, S.stage, 0, n, first_rows + a0 * L.nf0 * ncols, nullptr, st, L.nf0 * ncols))) return e;
+    }
+    for (size_t g0 = 0; g0 < n_slots; g0 += item_cap) {
+        const int n = (int)std::min(item_cap, n_slots - g0);
+        int rc = kws_launch_scan_stage(pcm, d_off, d_len, d_ibase, A, (long long)g0, n, 0, slice, L.grow, S.stage, S.wrap, st);
+        if (rc) return fail(KWS_ERROR_HIP, "scan staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if ((e = spectral_device(h, P1, S.stage, 0, n, slot_rows + g0 * L.nf1 * ncols, S.wrap, st, L.nf1 * ncols))) return e;
+    }
+    // 2. windows in chunks through the stream API's cmvnw + network; raw scores land where the moving average reads them
+    float *raw = raw_scores ? raw_scores : scores;
+    const bool fast = h->mode == KWS_MODE_FAST && h->fast_plain_ok;
+    const bool count = fast && m.dsp.block != DSP_BLOCK_MFE;          // the MFE block's fast form is its exact one: no guard, no counts
+    if (count) HIP_TRY(hipMemsetAsync(S.acc, 0, sizeof(int), st));
+    for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
+        const int n = (int)std::min(win_chunk, n_win - g0);
+        int rc = kws_launch_scan_gather(first_rows, slot_rows, d_wbase, d_ibase, A, (long long)g0, n, L.nf0, L.nf1, L.ring_rows, rows, ncols, S.win, st);
+        if (rc) return fail(KWS_ERROR_HIP, "scan gather kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (fast) e = cmvn_nn_fast_device(h, S.win, n, raw + g0 * C, st, 0, 0);
+        else e = cmvn_nn_device(h, S.win, n, nullptr, nullptr, raw + g0 * C, nullptr, nullptr, nullptr, st);
+        if (e) return e;
+        if (count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 0, st)))
+            return fail(KWS_ERROR_HIP, "scan count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    if (count) {
+        int rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 1, st);
+        if (rc) return fail(KWS_ERROR_HIP, "scan count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    // 3. the moving average, one fresh filter per recording
+    int rc = kws_launch_scan_maf(raw, scores, d_wbase, A, (int)C, st);
+    if (rc) return fail(KWS_ERROR_HIP, "scan moving-average kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EI_IMPULSE_OK;
+}
+
+#pragma GCC visibility pop
+}

@@ -220,6 +220,38 @@ EI_IMPULSE_ERROR kws_streams_init(kws_stream_batch *sb);            /* run_class
 EI_IMPULSE_ERROR kws_streams_step_device(kws_stream_batch *sb, const int16_t *slices, size_t slice_samples,
                                          const float *end_of_signal, float *scores, int *produced, void *stream);
 
+/* ---- continuous mode over whole recordings: every window of R recordings in one call ---------------------------------
+ * Parity contract.  For each recording r, the call returns exactly what a NEWLY CREATED kws_stream_batch with S = 1 returns when it is
+ * stepped through the recording with kws_streams_step_device:
+ *   - the recording is consumed as floor(lengths[r] / slice_samples) consecutive slices; a trailing partial slice is ignored;
+ *   - every recording starts from fresh state (first_run false, zero feature buffer, zero moving-average filters); the process-global
+ *     first_run of the reference is NOT carried from one recording to the next;
+ *   - slice k is the signal_t whose get_data(offset, n) reads the recording from sample k * slice_samples + offset: a read inside the
+ *     recording returns those samples, converted like every other sample of the slice (x / 32768); a read past the recording's end fails,
+ *     so the reference's pre-zeroed buffer gives 0.  In practice this concerns only the pre-emphasis x[-1] of the slices k >= 1, the
+ *     sample at k * slice_samples + slice_samples + frame_length - 1 (the stream API's end_of_signal);
+ *   - window w of the recording is produced at the step where kws_streams_step_device reports *produced (with the shipped slicing,
+ *     4000-sample slices of a 16 000-sample window: the fourth slice and every later one, W = n_slices - 3), and carries that step's scores.
+ * Window counts: kws_scan_window_count (host arithmetic only).  Recording r's windows are rows [sum_{q<r} W_q, + W_r) of the outputs.
+ *   pcm         int16, device; recording r is lengths[r] samples at pcm + offsets[r] (any sample offset, no alignment needed)
+ *   offsets, lengths  [R], HOST arrays
+ *   scores      [sum_r W_r][label_count] float, device: what run_classifier_continuous returns (after the moving average)
+ *   raw_scores  [sum_r W_r][label_count] float, device, optional (NULL): the same windows before the moving average
+ * Slicings and models: exactly what kws_streams_step_device accepts (int8, float32 and MFE-block models, general-shape DSP
+ * configurations); a slicing that the stream API refuses at any step is refused with the same error code, whatever the lengths.
+ * R = 0, or no recording long enough for a window: EI_IMPULSE_OK, nothing written.  scores == NULL: KWS_ERROR_BAD_ARGUMENT.
+ * Mode: KWS_MODE_EXACT is bit-identical to the stream API; KWS_MODE_FAST follows its rule (exact slice cepstra, then the fast cmvnw +
+ * network behind the guard; windows the guard hands back are re-run by the exact kernels inside the call), and kws_fast_fallback_count /
+ * kws_fast_exact_count report the windows of the last scan call that were handed back.  Scan calls do not write the logits tap.
+ * Device memory: the call keeps (on the handle, grown on demand; growing synchronises the device) the cepstral rows of its recordings --
+ * about (n_slices x frames per slice x columns) floats per recording, the only part that grows with the audio -- plus bounded scratch:
+ * at most 32 MiB of staged slices and 64 MiB of windows gathered for the network (chunks of at most 32 768 windows), 32 bytes per
+ * recording and the handle's batch scratch for one chunk.  Ordering: as for every call on the handle (see the top of this file); the
+ * call waits for earlier work on `stream` before it uploads its per-recording tables, the rest is asynchronous. */
+EI_IMPULSE_ERROR kws_scan_window_count(const kws_handle *h, size_t n_samples, size_t slice_samples, size_t *n_windows);
+EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                            size_t slice_samples, float *scores, float *raw_scores, void *stream);
+
 /* ---- multi-GPU: clips shard contiguously over the GPUs of one node (rank r owns clips [r*B, (r+1)*B)), tables are
  * replicated, nothing is exchanged inside the pipeline; the one collective is the all-gather of the per-clip scores over xGMI.
  * It goes through RCCL's C API (librccl is opened on first use: single-GPU applications do not need it).  One process per GPU:
