@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "kws_cmvn_inference_batch_device", "kws_nn_batch_device", "kws_nn_batch",
     "kws_streams_create", "kws_streams_destroy", "kws_streams_init", "kws_streams_step_device",
     "kws_scan_window_count", "kws_scan_recordings_device",
+    "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_extract_mfe_batch_device", "kws_set_mode", "kws_get_mode", "kws_fast_is_fused", "kws_fast_fallback_count", "kws_fast_exact_count", "kws_fast_guard",
     "kws_set_logits_tap", "kws_fast_gain", "kws_fast_tolerance_info",
     "kws_comm_unique_id", "kws_comm_create", "kws_comm_world_size", "kws_comm_rank", "kws_comm_ranks_seen", "kws_comm_rccl_version", "kws_comm_wait", "kws_allgather_scores", "kws_comm_destroy",
@@ -160,6 +161,13 @@ def lib():
         if hasattr(L, "kws_scan_recordings_device"):
             L.kws_scan_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
             L.kws_scan_recordings_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+        if hasattr(L, "kws_live_push_device"):
+            L.kws_live_create.argtypes = [vp, sz, sz, C.POINTER(vp)]
+            L.kws_live_destroy.argtypes = [vp]
+            L.kws_live_destroy.restype = None
+            L.kws_live_reset.argtypes = [vp, vp, sz]
+            L.kws_live_window_count.argtypes = [vp, sz, sz, C.c_int, C.POINTER(sz)]
+            L.kws_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.kws_device_malloc.argtypes = [C.POINTER(vp), sz]
         L.kws_device_free.argtypes = [vp]
         L.kws_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -353,6 +361,10 @@ class Model:
         _check(self.L.kws_scan_recordings_device(self.h, pcm_ptr, _p(off), _p(ln), off.size, slice_samples or self.clip_samples // 4,
                                                  scores_ptr, raw_scores_ptr, stream))
 
+    def live_streams(self, n_streams, slice_samples=None):
+        """a live session of n_streams streams in continuous mode (kws_live_*): see LiveStreams"""
+        return LiveStreams(self, n_streams, slice_samples)
+
 
 class StreamBatch:
     """S audio streams in continuous mode, state in HBM (kws_stream_batch)."""
@@ -378,6 +390,54 @@ class StreamBatch:
         if getattr(self, "sb", None):
             self.L.kws_streams_destroy(self.sb)
             self.sb = None
+
+
+class LiveStreams:
+    """S live streams in continuous mode, state in HBM between pushes (kws_live; the parity contract is in include/kws/kws.h): each push
+    hands any number of new samples to any subset of the streams and returns every window those samples complete."""
+
+    def __init__(self, model, n_streams, slice_samples=None):
+        self.model = model
+        self.L = model.L
+        self.slice_samples = slice_samples or model.clip_samples // 4
+        lv = C.c_void_p()
+        _check(self.L.kws_live_create(model.h, n_streams, self.slice_samples, C.byref(lv)))
+        self.lv = lv
+        self.n_streams = n_streams
+
+    def window_count(self, stream, n_new, finish=False):
+        """windows a push of n_new samples to `stream` (finishing it if finish) would return now"""
+        n = C.c_size_t()
+        _check(self.L.kws_live_window_count(self.lv, stream, n_new, 1 if finish else 0, C.byref(n)))
+        return n.value
+
+    def push_device(self, pcm_ptr, streams, offsets, lengths, scores_ptr, raw_scores_ptr=None, finish=None, stream=None):
+        """entry i: lengths[i] int16 samples at pcm_ptr + offsets[i] (device) to stream streams[i], finishing it if finish[i].  Writes the
+        entries' windows one after the other to scores (and raw_scores) [sum][labels], device; returns n_windows per entry (numpy uint64).
+        streams / offsets / lengths / finish: host sequences."""
+        st = np.ascontiguousarray(streams, np.uint64)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert st.shape == off.shape == ln.shape and st.ndim == 1
+        fin = None if finish is None else np.ascontiguousarray(finish, np.int32)
+        assert fin is None or fin.shape == st.shape
+        nw = np.zeros(st.size, np.uint64)
+        _check(self.L.kws_live_push_device(self.lv, st.size, _p(st), pcm_ptr, _p(off), _p(ln), None if fin is None else _p(fin), scores_ptr,
+                                           raw_scores_ptr, _p(nw), stream))
+        return nw
+
+    def reset(self, streams=None):
+        """streams (host sequence; None: all) back to fresh state"""
+        if streams is None:
+            _check(self.L.kws_live_reset(self.lv, None, 0))
+            return
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_live_reset(self.lv, _p(st), st.size))
+
+    def close(self):
+        if getattr(self, "lv", None):
+            self.L.kws_live_destroy(self.lv)
+            self.lv = None
 
 
 class Comm:

@@ -315,3 +315,28 @@ KWS_INTERNAL EI_IMPULSE_ERROR nn_f32_device(kws_handle *h, const float *features
 KWS_INTERNAL EI_IMPULSE_ERROR cmvn_nn_device(kws_handle *h, const float *mfcc, size_t B, float *features, int8_t *q, float *scores,
                                 int8_t *tap_pooled, int8_t *tap_fc, int8_t *tap_out, hipStream_t s, int ring_rows = 0, int ring_head = 0);
 }
+
+// kws_scan.cpp: the stream API's step rules (kws_streams_step_device) at one slicing, replayed on the host until they repeat; shared by the
+// recording scan and the live sessions (kws_live.cpp).  scan_layout refuses a slicing with the code the stream API would refuse it with.
+struct ScanLayout {
+    int nf0 = 0, nf1 = 0;          // frames of slice 0 / of every later slice
+    int ring_rows = 0;             // rows of the rolling buffer once it is full
+    size_t k_full = 0;             // the first step that produces a window
+    int grow = 0;                  // samples a grown slice claims beyond itself
+    size_t windows(size_t n_slices) const { return n_slices > k_full ? n_slices - k_full : 0; }
+};
+KWS_INTERNAL EI_IMPULSE_ERROR scan_layout(const kws_handle *h, size_t slice_samples, ScanLayout *L);
+
+// grows the device buffer *p to at least n elements (synchronising the device first: the old buffer may still be in use by enqueued work);
+// the per-call scratch of kws_scan.cpp and kws_live.cpp
+template <typename T>
+static EI_IMPULSE_ERROR grow_buffer(T **p, size_t *cap, size_t n)
+{
+    if (n <= *cap) return EI_IMPULSE_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
+    *cap = n;
+    return EI_IMPULSE_OK;
+}

@@ -43,31 +43,8 @@ static void scan_release(kws_handle *h)
     h->scan = nullptr;
 }
 
-// grows *p to at least n elements (synchronising the device first: the old buffer may still be in use by enqueued work)
-template <typename T>
-static EI_IMPULSE_ERROR grow(T **p, size_t *cap, size_t n)
-{
-    if (n <= *cap) return EI_IMPULSE_OK;
-    HIP_TRY(hipDeviceSynchronize());
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return EI_IMPULSE_OK;
-}
-
-namespace {
-// The stream API's step rules (kws_streams_step_device) at this slicing, replayed on the host until they repeat.
-struct ScanLayout {
-    int nf0 = 0, nf1 = 0;          // frames of slice 0 / of every later slice
-    int ring_rows = 0;             // rows of the rolling buffer once it is full
-    size_t k_full = 0;             // the first step that produces a window
-    int grow = 0;                  // samples a grown slice claims beyond itself
-    size_t windows(size_t n_slices) const { return n_slices > k_full ? n_slices - k_full : 0; }
-};
-}
-
-static EI_IMPULSE_ERROR scan_layout(const kws_handle *h, size_t slice_samples, ScanLayout *L)
+// (ScanLayout: kws_internal.h; the live sessions of kws_live.cpp share it)
+EI_IMPULSE_ERROR scan_layout(const kws_handle *h, size_t slice_samples, ScanLayout *L)
 {
     const Model &m = h->model;
     const size_t F = m.nn_input_frame_size;
@@ -149,9 +126,9 @@ EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, c
     const size_t item_cap = std::max<size_t>(1, std::min(kScanMaxItems, kScanStageBytes / (slice_samples * sizeof(int16_t))));
     const size_t win_chunk = std::min(std::max<size_t>(1, std::min(kScanMaxWindows, kScanWindowBytes / (F * sizeof(float)))), n_win);
     const size_t first_floats = (size_t)A * L.nf0 * ncols, rows_floats = first_floats + n_slots * L.nf1 * ncols;
-    if ((e = grow(&S.stage, &S.stage_cap, item_cap * slice_samples)) || (e = grow(&S.wrap, &S.wrap_cap, item_cap)) ||
-        (e = grow(&S.win, &S.win_cap, win_chunk * F)) || (e = grow(&S.rows, &S.rows_cap, rows_floats)) ||
-        (e = grow(&S.meta, &S.meta_cap, 4 * (size_t)A + 2)) || (e = grow(&S.acc, &S.acc_cap, 1)) || (e = ensure_scratch(h, win_chunk)))
+    if ((e = grow_buffer(&S.stage, &S.stage_cap, item_cap * slice_samples)) || (e = grow_buffer(&S.wrap, &S.wrap_cap, item_cap)) ||
+        (e = grow_buffer(&S.win, &S.win_cap, win_chunk * F)) || (e = grow_buffer(&S.rows, &S.rows_cap, rows_floats)) ||
+        (e = grow_buffer(&S.meta, &S.meta_cap, 4 * (size_t)A + 2)) || (e = grow_buffer(&S.acc, &S.acc_cap, 1)) || (e = ensure_scratch(h, win_chunk)))
         return e;
     // scan calls write no logits tap (out of the tap's [B][labels] shape): the tap is set aside for the call
     struct TapAside {

@@ -252,6 +252,48 @@ EI_IMPULSE_ERROR kws_scan_window_count(const kws_handle *h, size_t n_samples, si
 EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
                                             size_t slice_samples, float *scores, float *raw_scores, void *stream);
 
+/* ---- live continuous mode: audio of any length pushed to any subset of S streams, state in HBM between calls ----------------------
+ * A session holds S streams at one slicing.  A push hands any number of new samples (0 included) to any subset of the streams, each its
+ * own length, and returns every window those samples complete; finishing a stream flushes what waited for its look-ahead sample and the
+ * stream starts over from fresh state.
+ * Parity contract.  Take the concatenation of everything pushed to a stream since it was created, reset or last finished, up to and
+ * including the push that finishes it.  The windows the pushes return for that stream, in order, are exactly the windows
+ * kws_scan_recordings_device returns for that concatenation as one recording at the same slice_samples (scores and raw_scores; in
+ * KWS_MODE_EXACT bit-identical).  Before the stream is finished, the windows returned so far are the scan's first windows of the whole
+ * recording: a slice k >= 1 reads its look-ahead sample (k * slice_samples + slice_samples + frame_length - 1), so a push holds such a
+ * slice back, and every window that ends in it, until that sample has arrived; only a finish reads it as 0 past the end.
+ *   kws_live_create   S streams (0 < S < 2^30) at slice_samples; a slicing the stream API refuses is refused with kws_scan_window_count's
+ *                     code.  Models: those of the scan (int8, float32, MFE-block graphs, general-shape DSP configurations).
+ *   kws_live_destroy  waits for the session's enqueued work, then frees it.  Destroy sessions before their handle.
+ *   kws_live_reset    streams [n] (HOST; NULL: all): back to fresh state, as if just created.  Host only: no device work.
+ *   kws_live_window_count  the windows a push of n_new samples (finish != 0: and finishing) to `stream` would return now (host only)
+ *   kws_live_push_device  n entries; streams, offsets, lengths, finish (NULL: none finishes) and n_windows are HOST arrays of n entries.
+ *                     Entry i hands lengths[i] samples at pcm + offsets[i] (int16, device, any sample offset) to stream streams[i]; entry i's
+ *                     windows are rows [sum_{j<i} n_windows[j], + n_windows[i]) of scores / raw_scores ([.][label_count] float, device;
+ *                     raw_scores optional: before the moving average).  n_windows is computed on the host before anything is launched
+ *                     (the session keeps host copies of every stream's sample and slice counts); the call reads nothing back.
+ * Streams not named in a push keep their state.  KWS_ERROR_BAD_ARGUMENT, with no state changed: a stream named twice in one push, a stream
+ * index >= S, n > 0 with streams, lengths, n_windows or scores NULL, samples pushed with pcm or offsets NULL, more than 2^60 samples to one
+ * stream between starts.  A push with no window writes nothing to scores.  If a push fails past its argument checks, reset the streams
+ * it named.
+ * Mode follows the handle at push time, as in the scan: KWS_MODE_FAST runs the exact slice cepstra, then the fast cmvnw + network behind
+ * the guard, with windows it hands back re-run inside the call; kws_fast_fallback_count / kws_fast_exact_count report the windows of the
+ * last push (0 for a push without windows).  Pushes write no logits tap.
+ * Device memory per stream, bounded whatever the audio length: the carried samples, a ring of slice_samples + frame_length int16
+ * (8 640 B at the shipped slicing); the last ring_rows - frames per slice cepstral rows (35 x 13 floats = 1 820 B shipped); the moving
+ * average's taps and running sum per label (3 floats per label).  On top, per session and grown on demand (growing synchronises the
+ * device), the scan's per-call scratch: at most 32 MiB of staged slices, 64 MiB (<= 32 768) of gathered windows, the cepstral rows of
+ * the slices one push finishes and 80 B per entry; plus the handle's batch scratch for one chunk of windows.  Ordering: as for every call
+ * on the handle; a push waits for earlier work on `stream` before it uploads its per-entry tables, the rest is asynchronous. */
+typedef struct kws_live kws_live;
+EI_IMPULSE_ERROR kws_live_create(kws_handle *h, size_t S, size_t slice_samples, kws_live **out);
+void kws_live_destroy(kws_live *lv);
+EI_IMPULSE_ERROR kws_live_reset(kws_live *lv, const size_t *streams, size_t n);
+EI_IMPULSE_ERROR kws_live_window_count(const kws_live *lv, size_t stream, size_t n_new, int finish, size_t *n_windows);
+EI_IMPULSE_ERROR kws_live_push_device(kws_live *lv, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets,
+                                      const size_t *lengths, const int *finish, float *scores, float *raw_scores, size_t *n_windows,
+                                      void *stream);
+
 /* ---- multi-GPU: clips shard contiguously over the GPUs of one node (rank r owns clips [r*B, (r+1)*B)), tables are
  * replicated, nothing is exchanged inside the pipeline; the one collective is the all-gather of the per-clip scores over xGMI.
  * It goes through RCCL's C API (librccl is opened on first use: single-GPU applications do not need it).  One process per GPU:
