@@ -211,11 +211,12 @@ int kwso_filterbanks(const kwso_mfcc_config *c, float *fb_t)
 /* ====================================================================== */
 /* end_of_signal (optional): the `shift` floats the reference's constructor fetched from
  * signal->get_data(total_length - shift, shift) (processing.hpp:68); NULL = take them from pcm[n-shift..n). */
-static int preemphasis_ex(const int16_t *pcm, size_t n, float cof, int shift, size_t offset, size_t length, float *out,
+/* avail >= n: samples readable at pcm (a continuous slice's frames may run past its n samples, into the recording that follows) */
+static int preemphasis_ex(const int16_t *pcm, size_t n, size_t avail, float cof, int shift, size_t offset, size_t length, float *out,
                           const float *end_of_signal)
 {
     if (shift < 1 || (size_t)shift > n) return KWSO_ERR_PARAM;
-    if (offset + length > n) return -1004;   /* EIDSP_OUT_OF_BOUNDS */
+    if (offset + length > avail) return -1004;   /* EIDSP_OUT_OF_BOUNDS */
     for (size_t ix = 0; ix < length; ix++) {
         size_t p = offset + ix;
         float now = (float)pcm[p] / 32768;
@@ -231,7 +232,7 @@ static int preemphasis_ex(const int16_t *pcm, size_t n, float cof, int shift, si
 int kwso_preemphasis(const int16_t *pcm, size_t n, float cof, int shift,
                      size_t offset, size_t length, float *out)
 {
-    return preemphasis_ex(pcm, n, cof, shift, offset, length, out, NULL);
+    return preemphasis_ex(pcm, n, n, cof, shift, offset, length, out, NULL);
 }
 
 /* ====================================================================== */
@@ -462,16 +463,16 @@ int kwso_power_spectrum(const float *frame, size_t frame_size, float *out, int f
 /* ====================================================================== */
 /*  mfe                                             feature.hpp:193-318    */
 /* ====================================================================== */
-static int mfe_ex(const int16_t *pcm, size_t n, size_t n_claimed, const kwso_mfcc_config *c, float *features, float *energies,
+static int mfe_ex(const int16_t *pcm, size_t n, size_t avail, size_t n_claimed, const kwso_mfcc_config *c, float *features, float *energies,
                   const float *end_of_signal);
 int kwso_mfe(const int16_t *pcm, size_t n, const kwso_mfcc_config *c, float *features, float *energies)
 {
-    return mfe_ex(pcm, n, n, c, features, energies, NULL);
+    return mfe_ex(pcm, n, n, n, c, features, energies, NULL);
 }
 
 /* n = samples really available in pcm, n_claimed = signal->total_length the frame count is derived from
  * (continuous mode claims one extra frame length, ei_run_dsp.h:319-325) */
-static int mfe_ex(const int16_t *pcm, size_t n, size_t n_claimed, const kwso_mfcc_config *c, float *features, float *energies,
+static int mfe_ex(const int16_t *pcm, size_t n, size_t avail, size_t n_claimed, const kwso_mfcc_config *c, float *features, float *energies,
                   const float *end_of_signal)
 {
     const int nf = kwso_num_frames(n_claimed, c);
@@ -488,7 +489,7 @@ static int mfe_ex(const int16_t *pcm, size_t n, size_t n_claimed, const kwso_mfc
     memset(features, 0, sizeof(float) * (size_t)nf * M);
     for (int ix = 0; ix < nf && rc == KWSO_OK; ix++) {
         size_t off = (size_t)ix * (size_t)stride;
-        rc = preemphasis_ex(pcm, n, c->pre_cof, c->pre_shift, off, (size_t)flen, frame, end_of_signal);
+        rc = preemphasis_ex(pcm, n, avail, c->pre_cof, c->pre_shift, off, (size_t)flen, frame, end_of_signal);
         if (rc) break;
         rc = kwso_power_spectrum(frame, (size_t)flen, ps, c->fft_length);
         if (rc) break;
@@ -548,13 +549,13 @@ int kwso_dct2_ortho(float *v, int n)
 /* ====================================================================== */
 /*  mfcc (no CMVN)                                  feature.hpp:370-439    */
 /* ====================================================================== */
-static int mfcc_ex(const int16_t *pcm, size_t n, size_t n_claimed, const kwso_mfcc_config *c, float *out, const float *end_of_signal);
+static int mfcc_ex(const int16_t *pcm, size_t n, size_t avail, size_t n_claimed, const kwso_mfcc_config *c, float *out, const float *end_of_signal);
 int kwso_mfcc_nocmvn(const int16_t *pcm, size_t n, const kwso_mfcc_config *c, float *out)
 {
-    return mfcc_ex(pcm, n, n, c, out, NULL);
+    return mfcc_ex(pcm, n, n, n, c, out, NULL);
 }
 
-static int mfcc_ex(const int16_t *pcm, size_t n, size_t n_claimed, const kwso_mfcc_config *c, float *out, const float *end_of_signal)
+static int mfcc_ex(const int16_t *pcm, size_t n, size_t avail, size_t n_claimed, const kwso_mfcc_config *c, float *out, const float *end_of_signal)
 {
     const int nf = kwso_num_frames(n_claimed, c);
     const int M = c->num_filters, K = c->num_cepstral;
@@ -562,7 +563,7 @@ static int mfcc_ex(const int16_t *pcm, size_t n, size_t n_claimed, const kwso_mf
     float *mel = (float *)malloc(sizeof(float) * (size_t)nf * M);
     float *en = (float *)malloc(sizeof(float) * (size_t)nf);
     if (!mel || !en) { free(mel); free(en); return KWSO_ERR_OOM; }
-    int rc = mfe_ex(pcm, n, n_claimed, c, mel, en, end_of_signal);
+    int rc = mfe_ex(pcm, n, avail, n_claimed, c, mel, en, end_of_signal);
     if (rc == KWSO_OK) {
         for (size_t i = 0; i < (size_t)nf * M; i++) mel[i] = kwso_log(mel[i]);
         for (int r = 0; r < nf && rc == KWSO_OK; r++) rc = kwso_dct2_ortho(mel + (size_t)r * M, M);
@@ -1591,6 +1592,13 @@ void kwso_continuous_init(kwso_continuous *s)          /* run_classifier_init, e
 int kwso_continuous_step(kwso_continuous *s, const int16_t *slice, size_t n, const float *end_of_signal, float *scores,
                          int *produced)
 {
+    return kwso_continuous_step_ex(s, slice, n, n, end_of_signal, scores, produced);
+}
+
+int kwso_continuous_step_ex(kwso_continuous *s, const int16_t *slice, size_t n, size_t avail, const float *end_of_signal, float *scores,
+                            int *produced)
+{
+    if (avail < n) return KWSO_ERR_PARAM;
     const kwso_model *m = s->m;
     const size_t F = m->nn_input_frame_size;
     const kwso_mfcc_config *c = &m->dsp;
@@ -1613,10 +1621,10 @@ int kwso_continuous_step(kwso_continuous *s, const int16_t *slice, size_t n, con
         cm.pre_cof = 0.0f;
         float *en = (float *)malloc(sizeof(float) * (size_t)nf);
         if (!en) return -8;
-        rc = mfe_ex(slice, n, n_claimed, &cm, s->features + s->slice_offset, en, eos);
+        rc = mfe_ex(slice, n, avail, n_claimed, &cm, s->features + s->slice_offset, en, eos);
         free(en);
     } else
-        rc = mfcc_ex(slice, n, n_claimed, c, s->features + s->slice_offset, eos);
+        rc = mfcc_ex(slice, n, avail, n_claimed, c, s->features + s->slice_offset, eos);
     if (rc) return -5;
     if (!s->feature_buffer_full) {
         s->slice_offset += feature_size;

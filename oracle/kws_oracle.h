@@ -124,6 +124,10 @@ void kwso_continuous_free(kwso_continuous *s);
 void kwso_continuous_init(kwso_continuous *s);
 int  kwso_continuous_step(kwso_continuous *s, const int16_t *slice, size_t n, const float *end_of_signal, float *scores,
                           int *produced);
+/* the same step where the slice's frames may read past its n samples: avail (>= n) samples are readable at slice, as when the
+ * application's get_data reads a recording beyond the slice (a frame longer than the FFT reads samples the transform drops) */
+int  kwso_continuous_step_ex(kwso_continuous *s, const int16_t *slice, size_t n, size_t avail, const float *end_of_signal,
+                             float *scores, int *produced);
 
 /* mix_audio (/root/reference/dataset-curation.py:93-137) for one clip, without the resampling of librosa.load: word (may be NULL)
  * of word_len float32 samples, noise window (may be NULL) of n samples -> PCM16.  PARITY UNPINNED: librosa / soundfile cannot be

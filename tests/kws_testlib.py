@@ -110,6 +110,7 @@ class Oracle:
         L.kwso_continuous_free.argtypes = [C.c_void_p]
         L.kwso_continuous_init.argtypes = [C.c_void_p]
         L.kwso_continuous_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.kwso_continuous_step_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
 
     def mix_audio(self, word, noise_window, word_vol, bg_vol, n):
         """mix_audio of dataset-curation.py:93-137 (PARITY UNPINNED, see oracle/kws_oracle.h); word / noise_window may be None"""

@@ -349,3 +349,17 @@ def test_random_general_shape_configurations(oracle, reference):
         for c in (rnd, np.concatenate([sp["alternating_fullscale"]] * 2)[:n]):
             a, b = oracle.extract_mfcc(c, cfg), reference.extract_mfcc(c, cfg)
             assert a.shape == b.shape and (bits(a) == bits(b)).all(), (seed, cfg_kw)
+
+
+@pytest.mark.parametrize("slice_samples", [1000, 2000, 3200, 3999, 4001, 4160, 6000, 8000])
+def test_continuous_mode_at_other_slicings(slice_samples):
+    """the oracle's continuous mode (kwso_continuous_step) against the compiled reference's run_classifier_continuous (eiref_continuous)
+    at slicings other than the 4000-sample one continuous_l476.npz pins: produced flags equal and scores bit-identical over 40 slices after
+    one run_classifier_init.  Each slicing runs in a fresh child process (tests/continuous_ref_worker.py): the reference's first_run,
+    feature matrix and slice offset are static to the process."""
+    import subprocess
+    import sys
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "continuous_ref_worker.py")
+    p = subprocess.run([sys.executable, worker, str(slice_samples), "40"], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+    assert "windows OK" in p.stdout
