@@ -11,11 +11,13 @@ Two arithmetic modes of the same library are timed (include/kws/kws.h):
     states; tests/test_gpu_fast_mode.py holds every one of 65 536 clips to it, tests/test_gpu_fast_families.py nine adversarial
     input families), MFCC + network in ONE kernel launch; clips whose cmvnw would amplify the re-ordering past that are re-run by
     the exact kernels inside the same call (their share is reported as config.fast_fallback_rate);
-  * KWS_MODE_EXACT -- MFCC features bit-identical to the reference's, scores within 1e-6; reported under "modes".
-At N = 1 the same run also times the model the reference DOES ship (49x13 MFCC, int8) and the other BASELINE configurations;
-they are reported under "also".  BASELINE configs[3] ("int8 ... bit-exact check, batch 65 536, 1 GPU") is the line "int8_exact": the
-reference's own int8 impulse in KWS_MODE_EXACT -- bit-identical to the reference end to end -- with a roofline object of its own.  The
-KWS_MODE_FAST lines of int8 graphs are NOT that configuration (an int8 input value may sit one step away): they say so.
+  * KWS_MODE_EXACT -- MFCC features bit-identical to the reference's, scores within 1e-6; reported under "modes" (--full).
+A plain run measures the headline alone: set-up, warm-up, the K timed steps, --dump-outputs, the result line.  --full (N = 1) adds
+everything else, each leg timed on its own: the reference's CPU baseline (before the GPU is touched), the headline graph's other mode, the
+model the reference DOES ship (49x13 MFCC, int8) and the other BASELINE configurations, reported under "also".  BASELINE configs[3]
+("int8 ... bit-exact check, batch 65 536, 1 GPU") is the line "int8_exact": the reference's own int8 impulse in KWS_MODE_EXACT --
+bit-identical to the reference end to end -- with a roofline object of its own.  The KWS_MODE_FAST lines of int8 graphs are NOT that
+configuration (an int8 input value may sit one step away): they say so.  --no-cpu-baseline / --no-also leave parts of --full out.
 
 One "step" = one pass of the hot path over one batch of B synthetic 1 s @ 16 kHz int16 clips per GPU, the clips already
 resident in HBM (generated on the device by kws_synth_clips_device).  N > 1: one process per GPU, clips sharded contiguously
@@ -268,8 +270,8 @@ class GpuBackend:
         self.torch.cuda.synchronize()
 
     def prewarm(self, seconds):
-        """un-counted steps until `seconds` of wall time with the GPU busy have passed: the clocks ramp (the driver's 5 warm-up steps are
-        9 ms behind a 10 s CPU-baseline leg with the GPU idle) before the counted warm-up starts; returns how many steps that took"""
+        """un-counted steps until `seconds` of wall time with the GPU busy have passed: the clocks ramp from idle (the driver's 5 warm-up
+        steps are 9 ms, behind set-up or, with --full, a 10 s CPU-baseline leg) before the counted warm-up starts; returns how many steps that took"""
         n, t0 = 0, time.perf_counter()
         pcm = self.pcm if self.pcm_override is None else self.pcm_override
         while time.perf_counter() - t0 < seconds:
@@ -477,8 +479,11 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="clips per GPU per step (default: 65536; 131072 at 8 GPUs = 1 M clips)")
     ap.add_argument("--model", default=DEFAULT_MODEL)
     ap.add_argument("--mode", choices=["fast", "exact"], default="fast", help="which arithmetic mode is the headline value")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra workloads / the other mode timed at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: besides the headline, also the reference's CPU baseline, the other mode, the other models, int8_exact, the input "
+                         "families and the DSP shapes (a plain run times the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the extra workloads / the other mode")
     ap.add_argument("--force-collective", action="store_true",
                     help="create the RCCL communicator and all-gather the scores even with one rank (the N > 1 path on a 1-GPU box)")
     ap.add_argument("--dry-run-cpu", action="store_true",
@@ -505,7 +510,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", 1))
     B = a.batch if a.batch > 0 else (64 if a.dry_run_cpu else default_batch(world))
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.dry_run_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.dry_run_cpu:
         cpu = cpu_baseline(model_path=a.model)                     # before the GPU is touched: children never see a HIP context
 
     import torch
@@ -559,7 +564,7 @@ def main():
     r = measure(backend, a.model, a.mode, a.steps, a.warmup, barrier, max_over_ranks, gather_ranks, keep_outputs=keep)
     dumped = dump_outputs(r.pop("outputs"), a.dump_outputs) if keep else None
     others, also, int8_exact, inputs, dsp_shapes = [], [], None, [], []
-    if world == 1 and not a.no_also and not a.dry_run_cpu:
+    if a.full and world == 1 and not a.no_also and not a.dry_run_cpu:
         side_steps = max(20, a.steps // 8)
         others.append(measure(backend, a.model, "exact" if a.mode == "fast" else "fast", side_steps, a.warmup, barrier, max_over_ranks))
         for mp_ in ALSO_MODELS:

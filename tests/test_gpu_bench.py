@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -35,15 +36,20 @@ def test_bench_force_collective_on_one_gpu():
     assert j["value"] > 1e5 and j["roofline"]["kernel"] in ("kws_fast_kernel", "kws_fast_kernel_w3")
 
 
-def test_bench_line_with_the_drivers_flags_is_compact_and_complete():
-    """The driver's own command (`python bench.py --gpus 1 --steps 20 --warmup 5`, everything on: the CPU baseline leg, the other modes / models /
-    input families): ONE stdout line under 6 KB (round 5's 27 KB line was not parsed by the driver) that carries the headline, its roofline
-    object, the CPU baseline, the exact-mode row of the headline graph and BASELINE configs[3] (int8_exact); the rest is in bench_detail.json."""
+def _bench_line(*flags):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True, timeout=900, env=env)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"] + list(flags),
+                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
+
+
+def test_bench_line_with_the_drivers_flags_is_compact_and_complete():
+    """The driver's command with --full (`python bench.py --gpus 1 --steps 20 --warmup 5 --full`, everything on: the CPU baseline leg, the other
+    modes / models / input families): ONE stdout line under 6 KB (round 5's 27 KB line was not parsed by the driver) that carries the headline,
+    its roofline object, the CPU baseline, the exact-mode row of the headline graph and BASELINE configs[3] (int8_exact); the rest is in
+    bench_detail.json."""
+    out = _bench_line("--full")
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0]) < 6000, (len(lines), [len(ln) for ln in lines])
@@ -61,6 +67,26 @@ def test_bench_line_with_the_drivers_flags_is_compact_and_complete():
     assert {r["family"] for r in j["also_inputs"]} >= {"word_silence", "amp_sweep", "bursts"}
     detail = json.load(open(os.path.join(ROOT, j["detail"])))
     assert detail["value"] == j["value"] and "also_dsp" in detail and len(detail["also_inputs"]) == 2 * len(j["also_inputs"])
+
+
+def test_bench_plain_line_times_the_headline_alone():
+    """The driver's plain command (`python bench.py --gpus 1 --steps 20 --warmup 5`): the headline and its roofline, none of --full's legs
+    (CPU baseline, other modes / models, int8_exact, input families, DSP shapes), and at most 30 s of the run's wall time outside its steps."""
+    t0 = time.monotonic()
+    out = _bench_line()
+    wall = time.monotonic() - t0
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 6000, (len(lines), [len(ln) for ln in lines])
+    j = json.loads(lines[0])
+    assert j["steps"] == 20 and j["warmup"] == 5 and j["n_gpus"] == 1 and j["unit"] == "clips/s" and j["value"] > 1e6 and j["higher_is_better"]
+    assert abs(j["value"] - 65536 / (j["ms_per_step"] * 1e-3)) < 1e-3 * j["value"]
+    assert j["metric"] == "1s@16kHz clips/sec (MFCC+CNN)" and j["dtype"] == "f32" and j["config"]["mode"] == "fast"
+    assert j["roofline"]["kernel"] == "kws_fast_kernel_w3" and j["roofline"]["frac"] > 0
+    assert not {"cpu_baseline", "also", "int8_exact", "also_inputs"} & set(j), sorted(j)
+    detail = json.load(open(os.path.join(ROOT, j["detail"])))
+    assert detail["value"] == j["value"] and not {"cpu_baseline", "modes", "also", "int8_exact", "also_inputs", "also_dsp"} & set(detail)
+    assert wall - 25 * j["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 def test_allgather_scores_c_abi_world_size_one():

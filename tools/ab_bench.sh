@@ -8,8 +8,8 @@
 V="${@:-old new}"; for c in $V; do LAST=$c; done
 for v in $V $V; do
   cp ab_tmp/libkws_$v.so ei-keyword-spotting_amd/libkws_mi355x.so
-  echo -n "$v: "; python bench.py --no-cpu-baseline | python -c "
-import sys,json; d=json.loads(sys.stdin.read()); print(d['roofline']['kernel_ms'], [x['kernel_ms'] for x in d['also']])"
+  echo -n "$v: "; python bench.py --full --no-cpu-baseline | python -c "
+import sys,json; d=json.loads(sys.stdin.read()); print(d['roofline']['hot_path_ms'], [x['ms_per_step'] for x in d['also']])"
 done
 cp ab_tmp/libkws_$LAST.so ei-keyword-spotting_amd/libkws_mi355x.so
 [ -n "$AB_NO_TESTS" ] || timeout 600 python -m pytest tests -m gpu -q -x 2>&1 | grep -E "passed|failed|rror" | head -3

@@ -14,9 +14,9 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() { ( cd "$REPO" && "$@" ); }
 short=$(basename "$MODEL" .kwsm); short=${short/mfcc40_/}      # cfg2_mfcc40_f32 -> cfg2_f32 (the names profiles/ has used since round 2)
-# 1. the official bench line (with the cpu baseline), un-profiled
+# 1. the bench line with --full (the cpu baseline and the other workloads), un-profiled
 if [ "$BENCH" = 1 ]; then
-  run python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  run python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   cp "$REPO/bench_detail.json" "$OUT/bench_detail.json" 2>/dev/null
 fi
 # 2. kernel trace + stats of the same command, per mode
