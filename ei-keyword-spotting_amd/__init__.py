@@ -24,6 +24,7 @@ DEFAULT_MODEL = os.path.join(MODELS_DIR, "l476_no_yes.kwsm")
 
 EI_IMPULSE_OK = 0
 MODE_EXACT, MODE_FAST = 0, 1
+SLIDE_AUTO, SLIDE_DIRECT, SLIDE_SHARED = 0, 1, 2
 ERROR_NAMES = {0: "EI_IMPULSE_OK", -1: "EI_IMPULSE_ERROR_SHAPES_DONT_MATCH", -2: "EI_IMPULSE_CANCELED",
                -3: "EI_IMPULSE_TFLITE_ERROR", -5: "EI_IMPULSE_DSP_ERROR", -6: "EI_IMPULSE_TFLITE_ARENA_ALLOC_FAILED",
                -7: "EI_IMPULSE_CUBEAI_ERROR", -8: "EI_IMPULSE_ALLOC_FAILED", -17: "KWS_ERROR_NO_MODEL",
@@ -42,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "kws_cmvn_inference_batch_device", "kws_nn_batch_device", "kws_nn_batch",
     "kws_streams_create", "kws_streams_destroy", "kws_streams_init", "kws_streams_step_device",
     "kws_scan_window_count", "kws_scan_recordings_device",
+    "kws_frame_stride_samples", "kws_slide_window_count", "kws_slide_plan", "kws_slide_recordings_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_extract_mfe_batch_device", "kws_set_mode", "kws_get_mode", "kws_fast_is_fused", "kws_fast_fallback_count", "kws_fast_exact_count", "kws_fast_guard",
     "kws_set_logits_tap", "kws_fast_gain", "kws_fast_tolerance_info",
@@ -58,6 +60,11 @@ class FastTolerance(C.Structure):
                 ("calibrated", C.c_int), ("n_columns", C.c_int), ("n_frames", C.c_int), ("entry_tier", C.c_int), ("dev_overrides", C.c_int),
                 ("k_sigma_worst_column", C.c_float), ("silent_rows_exact", C.c_int), ("systematic_ratio", C.c_float),
                 ("fused_waves_per_simd", C.c_int), ("fused_waves", C.c_int)]
+
+
+class SlidePlanInfo(C.Structure):                # kws_slide_plan_info
+    _fields_ = [("n_windows", C.c_size_t), ("rows_shared", C.c_size_t), ("rows_first", C.c_size_t), ("rows_direct", C.c_size_t),
+                ("phases", C.c_int), ("path", C.c_int)]
 
 
 class KwsError(RuntimeError):
@@ -161,6 +168,11 @@ def lib():
         if hasattr(L, "kws_scan_recordings_device"):
             L.kws_scan_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
             L.kws_scan_recordings_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+        if hasattr(L, "kws_slide_recordings_device"):
+            L.kws_frame_stride_samples.argtypes = [vp]
+            L.kws_slide_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
+            L.kws_slide_plan.argtypes = [vp, vp, sz, sz, i32, vp]
+            L.kws_slide_recordings_device.argtypes = [vp, vp, vp, vp, sz, sz, i32, vp, vp, vp]
         if hasattr(L, "kws_live_push_device"):
             L.kws_live_create.argtypes = [vp, sz, sz, C.POINTER(vp)]
             L.kws_live_destroy.argtypes = [vp]
@@ -360,6 +372,36 @@ class Model:
         assert off.shape == ln.shape and off.ndim == 1
         _check(self.L.kws_scan_recordings_device(self.h, pcm_ptr, _p(off), _p(ln), off.size, slice_samples or self.clip_samples // 4,
                                                  scores_ptr, raw_scores_ptr, stream))
+
+    # ---- one-shot windows over whole recordings (kws_slide_*; the parity contract is in include/kws/kws.h) ------------------
+    @property
+    def frame_stride_samples(self):
+        """the DSP block's frame stride in samples: a hop that is a multiple of it shares the most rows between windows"""
+        return int(self.L.kws_frame_stride_samples(self.h))
+
+    def slide_window_count(self, n_samples, hop_samples):
+        """one-shot windows of one recording of n_samples, one every hop_samples"""
+        n = C.c_size_t()
+        _check(self.L.kws_slide_window_count(self.h, n_samples, hop_samples, C.byref(n)))
+        return n.value
+
+    def slide_plan(self, lengths, hop_samples, flags=SLIDE_AUTO):
+        """kws_slide_plan_info as a dict: what slide_recordings_device would run for these lengths (host arithmetic only)"""
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert ln.ndim == 1
+        info = SlidePlanInfo()
+        _check(self.L.kws_slide_plan(self.h, _p(ln), ln.size, hop_samples, flags, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in SlidePlanInfo._fields_}
+
+    def slide_recordings_device(self, pcm_ptr, offsets, lengths, hop_samples, scores_ptr, features_ptr=None, flags=SLIDE_AUTO, stream=None):
+        """run_classifier() at every position of R recordings (int16 at pcm_ptr + offsets[r], lengths[r] samples; device), one window every
+        hop_samples: scores [sum of the recordings' window counts][labels] and, optionally, features [.][n_features], device.
+        offsets / lengths: host sequences."""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        _check(self.L.kws_slide_recordings_device(self.h, pcm_ptr, _p(off), _p(ln), off.size, hop_samples, flags, scores_ptr, features_ptr,
+                                                  stream))
 
     def live_streams(self, n_streams, slice_samples=None):
         """a live session of n_streams streams in continuous mode (kws_live_*): see LiveStreams"""

@@ -246,6 +246,9 @@ struct kws_handle {
     // scan_release (set with it)
     struct KwsScanScratch *scan = nullptr;
     void (*scan_release)(kws_handle *) = nullptr;
+    // kws_slide.cpp: the same for kws_slide_recordings_device
+    struct KwsSlideScratch *slide = nullptr;
+    void (*slide_release)(kws_handle *) = nullptr;
     size_t flags_cap = 0, cep_cap = 0;
 
     template <typename T> EI_IMPULSE_ERROR upload(const std::vector<T> &v, const T **out)

@@ -252,6 +252,57 @@ EI_IMPULSE_ERROR kws_scan_window_count(const kws_handle *h, size_t n_samples, si
 EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
                                             size_t slice_samples, float *scores, float *raw_scores, void *stream);
 
+/* ---- one-shot windows over whole recordings: run_classifier() at every position, one window every hop_samples ---------------------
+ * Parity contract.  Let clip = kws_clip_samples(h).  Recording r has W_r = lengths[r] < clip ? 0 : (lengths[r] - clip) / hop_samples + 1
+ * windows (kws_slide_window_count; host arithmetic only); window w is samples [w hop_samples, w hop_samples + clip) of the recording.
+ * Its row of `scores` is what kws_run_classifier_batch_device returns for that window copied out as a clip, and its row of `features`
+ * likewise, in the handle's mode, whichever path runs and whatever `flags` says: in KWS_MODE_EXACT bit-identical to that call and, per
+ * window, to the reference's run_classifier().  These are the ONE-SHOT features the models were trained on -- not continuous mode's
+ * (kws_scan_*, kws_live_*: fake first frame, rows never written, cmvnw over a rolling buffer) -- and there is no moving average.
+ * Recording r's windows are rows [sum_{q<r} W_q, + W_r) of the outputs.
+ *   pcm         int16, device; recording r is lengths[r] samples at pcm + offsets[r] (any sample offset, no alignment needed)
+ *   offsets, lengths  [R], HOST arrays
+ *   scores      [sum_r W_r][label_count] float, device
+ *   features    [sum_r W_r][feature_count] float, device, optional (NULL)
+ *   flags       KWS_SLIDE_AUTO, or one path by name.  DIRECT: every window staged as a clip and its frame_count rows computed for it.
+ *               SHARED: only a window's first sample takes its pre-emphasis predecessor from the window (its last sample), so frame
+ *               f >= 1 of a window is the cepstral row of that position of the recording whichever window reads it: those rows are
+ *               computed once per recording and position (hop_samples / gcd(hop_samples, frame stride) new rows per window), frame 0 once
+ *               per window (MFE block: no pre-emphasis, frame 0 is shared too).  Both run the one-shot path's own spectral kernels and the
+ *               same cmvnw + network launches: the paths are bit-identical to each other in either mode.
+ *               AUTO takes SHARED where rows_shared + rows_first < rows_direct (kws_slide_plan reports all three, and the path).
+ * Models: those of the scan (int8, float32 and MFE-block graphs, general-shape DSP configurations).
+ * hop_samples == 0, scores == NULL, unknown flags, a recording, offset or hop beyond 2^56 samples: KWS_ERROR_BAD_ARGUMENT.  R = 0, or no
+ * recording long enough for a window: EI_IMPULSE_OK, nothing written.
+ * Mode: KWS_MODE_EXACT as above; KWS_MODE_FAST follows the scan's rule (exact cepstral rows, then the fast cmvnw + network behind the
+ * guard; windows the guard hands back are re-run by the exact kernels inside the call: scores within the fast mode's tolerance of the
+ * exact ones), and kws_fast_fallback_count / kws_fast_exact_count report the windows of the last slide call that were handed back.
+ * Slide calls do not write the logits tap.
+ * Device memory: the call keeps (on the handle, grown on demand; growing synchronises the device) bounded scratch -- at most 32 MiB of
+ * staged samples, 64 MiB of windows gathered for the network (chunks of at most 32 768 windows), one frame-0 row per window of a chunk,
+ * the handle's batch scratch for one chunk -- plus, on the shared path only, the part that grows with the audio: the cepstral rows of the
+ * call's recordings, about (lengths[r] / gcd(hop_samples, frame stride)) rows of feature_count / frame_count floats per recording
+ * (3 000 rows = 156 KB per minute for the shipped models at a hop that is a multiple of the frame stride), and 24 bytes per recording
+ * and phase.  Ordering: as for every call on the handle (see the top of this file); the call waits for earlier work on `stream` before
+ * it uploads its tables, the rest is asynchronous. */
+int kws_frame_stride_samples(const kws_handle *h);           /* the DSP block's frame stride in samples */
+#define KWS_SLIDE_AUTO   0   /* the library picks the path */
+#define KWS_SLIDE_DIRECT 1   /* every window's rows computed for that window */
+#define KWS_SLIDE_SHARED 2   /* rows computed once per recording and position, frame 0 per window */
+typedef struct {
+    size_t n_windows;        /* sum over the recordings */
+    size_t rows_shared;      /* cepstral rows the shared path computes once per position (items are padded to whole launches on top) */
+    size_t rows_first;       /* per-window frame-0 rows (0 for an MFE block) */
+    size_t rows_direct;      /* n_windows * frame_count: what the direct path computes */
+    int    phases;           /* frame_stride / gcd(hop, frame_stride) */
+    int    path;             /* KWS_SLIDE_DIRECT or KWS_SLIDE_SHARED: what a call with these arguments runs */
+} kws_slide_plan_info;
+EI_IMPULSE_ERROR kws_slide_window_count(const kws_handle *h, size_t n_samples, size_t hop_samples, size_t *n_windows);
+EI_IMPULSE_ERROR kws_slide_plan(const kws_handle *h, const size_t *lengths, size_t R, size_t hop_samples, int flags,
+                                kws_slide_plan_info *out);                                   /* host arithmetic only */
+EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                             size_t hop_samples, int flags, float *scores, float *features, void *stream);
+
 /* ---- live continuous mode: audio of any length pushed to any subset of S streams, state in HBM between calls ----------------------
  * A session holds S streams at one slicing.  A push hands any number of new samples (0 included) to any subset of the streams, each its
  * own length, and returns every window those samples complete; finishing a stream flushes what waited for its look-ahead sample and the
