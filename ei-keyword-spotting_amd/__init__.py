@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "kws_streams_create", "kws_streams_destroy", "kws_streams_init", "kws_streams_step_device",
     "kws_scan_window_count", "kws_scan_recordings_device",
     "kws_frame_stride_samples", "kws_slide_window_count", "kws_slide_plan", "kws_slide_recordings_device",
+    "kws_bank_create", "kws_bank_destroy", "kws_bank_size", "kws_bank_member", "kws_bank_run_classifier_batch_device",
+    "kws_bank_cmvn_inference_batch_device", "kws_bank_slide_recordings_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_extract_mfe_batch_device", "kws_set_mode", "kws_get_mode", "kws_fast_is_fused", "kws_fast_fallback_count", "kws_fast_exact_count", "kws_fast_guard",
     "kws_set_logits_tap", "kws_fast_gain", "kws_fast_tolerance_info",
@@ -173,6 +175,17 @@ def lib():
             L.kws_slide_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
             L.kws_slide_plan.argtypes = [vp, vp, sz, sz, i32, vp]
             L.kws_slide_recordings_device.argtypes = [vp, vp, vp, vp, sz, sz, i32, vp, vp, vp]
+        if hasattr(L, "kws_bank_create"):
+            L.kws_bank_create.argtypes = [vp, sz, C.POINTER(vp)]
+            L.kws_bank_destroy.argtypes = [vp]
+            L.kws_bank_destroy.restype = None
+            L.kws_bank_size.argtypes = [vp]
+            L.kws_bank_size.restype = sz
+            L.kws_bank_member.argtypes = [vp, sz]
+            L.kws_bank_member.restype = vp
+            L.kws_bank_run_classifier_batch_device.argtypes = [vp, vp, sz, vp, vp, vp]
+            L.kws_bank_cmvn_inference_batch_device.argtypes = [vp, vp, sz, vp, vp, vp]
+            L.kws_bank_slide_recordings_device.argtypes = [vp, vp, vp, vp, sz, sz, i32, vp, vp, vp]
         if hasattr(L, "kws_live_push_device"):
             L.kws_live_create.argtypes = [vp, sz, sz, C.POINTER(vp)]
             L.kws_live_destroy.argtypes = [vp]
@@ -406,6 +419,52 @@ class Model:
     def live_streams(self, n_streams, slice_samples=None):
         """a live session of n_streams streams in continuous mode (kws_live_*): see LiveStreams"""
         return LiveStreams(self, n_streams, slice_samples)
+
+
+class Bank:
+    """K loaded models with an identical DSP block (kws_bank; the contract is in include/kws/kws.h): a call computes the front end once and
+    every member's scores from it, always with the exact kernels.  scores_ptrs: one device pointer per member ([rows][that member's
+    n_labels] float), None to skip a member in that call.  Close the bank before its models."""
+
+    def __init__(self, models):
+        self._models = list(models)
+        self.L = lib()
+        hs = (C.c_void_p * max(len(self._models), 1))(*[m.h for m in self._models])
+        b = C.c_void_p()
+        _check(self.L.kws_bank_create(hs, len(self._models), C.byref(b)))
+        self.b = b
+
+    @property
+    def members(self):
+        """the member models, in the order given"""
+        return list(self._models)
+
+    def __len__(self):
+        return int(self.L.kws_bank_size(self.b))
+
+    def _scores(self, scores_ptrs):
+        ptrs = list(scores_ptrs)
+        assert len(ptrs) == len(self._models), "one scores pointer (or None) per member"
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
+    def run_classifier_batch_device(self, pcm_ptr, B, scores_ptrs, features_ptr=None, stream=None):
+        _check(self.L.kws_bank_run_classifier_batch_device(self.b, pcm_ptr, B, self._scores(scores_ptrs), features_ptr, stream))
+
+    def cmvn_inference_batch_device(self, mfcc_ptr, B, scores_ptrs, features_ptr=None, stream=None):
+        _check(self.L.kws_bank_cmvn_inference_batch_device(self.b, mfcc_ptr, B, self._scores(scores_ptrs), features_ptr, stream))
+
+    def slide_recordings_device(self, pcm_ptr, offsets, lengths, hop_samples, scores_ptrs, features_ptr=None, flags=SLIDE_AUTO, stream=None):
+        """Model.slide_recordings_device for every member: window counts and slide_plan are any member's"""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        _check(self.L.kws_bank_slide_recordings_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, hop_samples, flags, self._scores(scores_ptrs),
+                                                       features_ptr, stream))
+
+    def close(self):
+        if getattr(self, "b", None):
+            self.L.kws_bank_destroy(self.b)
+            self.b = None
 
 
 class StreamBatch:

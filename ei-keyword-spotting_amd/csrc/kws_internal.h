@@ -330,6 +330,13 @@ struct ScanLayout {
 };
 KWS_INTERNAL EI_IMPULSE_ERROR scan_layout(const kws_handle *h, size_t slice_samples, ScanLayout *L);
 
+// kws_slide.cpp: the body of kws_slide_recordings_device for the handle's DSP block, with what follows the gathering as a callable:
+// finish(ctx, win, n, first, s) receives every chunk of gathered windows (win [n][feature_count] cepstra before cmvnw, device; the call's
+// windows first .. first + n - 1) and is called once more with n == 0 after the last chunk.  take_lock == 0: the caller holds h->mu.
+typedef EI_IMPULSE_ERROR (*kws_slide_finish_fn)(void *ctx, float *win, size_t n, size_t first, hipStream_t s);
+KWS_INTERNAL EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R, size_t hop_samples,
+                                            int flags, int take_lock, kws_slide_finish_fn finish, void *ctx, hipStream_t s);
+
 // grows the device buffer *p to at least n elements (synchronising the device first: the old buffer may still be in use by enqueued work);
 // the per-call scratch of kws_scan.cpp and kws_live.cpp
 template <typename T>

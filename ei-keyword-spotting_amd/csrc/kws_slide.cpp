@@ -14,7 +14,8 @@
 //                    spectral_device with the item's frame pitch as the plan's stride; MFE block: no pre-emphasis, frame 0 is shared too;
 //                 3. windows gathered into [chunk][F] (kws_slide_gather_kernel);
 //   direct path:  per chunk, the windows staged as aligned clips and the handle's own plan through spectral_device into [chunk][F];
-//   both:         cmvn_nn_device (cmvn_nn_fast_device in KWS_MODE_FAST) writes the chunk's scores and features in place.
+//   both:         the finishing step of the caller of kws_slide_run: for kws_slide_recordings_device, cmvn_nn_device (cmvn_nn_fast_device in
+//                 KWS_MODE_FAST) writes the chunk's scores and features in place; a bank (kws_bank.cpp) runs cmvnw once, then every member.
 // Where hop / g > frames per window - 1 the windows of a slot do not touch: each is a segment of its own (nothing is shared, and AUTO
 // takes the direct path).
 #include "kws_internal.h"
@@ -129,34 +130,53 @@ static EI_IMPULSE_ERROR slide_plan(const kws_handle *h, const size_t *lengths, s
     return EI_IMPULSE_OK;
 }
 
-extern "C" {
-#pragma GCC visibility push(default)
-
-int kws_frame_stride_samples(const kws_handle *h) { return h->dsp.frame_stride; }
-
-EI_IMPULSE_ERROR kws_slide_window_count(const kws_handle *h, size_t n_samples, size_t hop_samples, size_t *n_windows)
+// The finishing step of kws_slide_recordings_device itself: cmvnw + the handle's network in the handle's mode, chunk by chunk (h->mu held)
+struct SlideOwn {
+    kws_handle *h;
+    float *scores, *features;
+    bool started = false, fast = false, count = false;
+};
+static EI_IMPULSE_ERROR slide_own_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t st)
 {
-    if (!h || !n_windows) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    *n_windows = 0;
-    EI_IMPULSE_ERROR e = slide_check(h, hop_samples, KWS_SLIDE_AUTO);
+    SlideOwn &o = *(SlideOwn *)ctx;
+    kws_handle *h = o.h;
+    const Model &m = h->model;
+    const size_t F = m.nn_input_frame_size, C = m.labels.size();
+    KwsSlideScratch &S = *h->slide;
+    int rc = 0;
+    if (!o.started) {
+        o.started = true;
+        o.fast = h->mode == KWS_MODE_FAST && h->fast_plain_ok;
+        o.count = o.fast && m.dsp.block != DSP_BLOCK_MFE;          // the MFE block's fast form is its exact one: no guard, no counts
+        if (o.count) HIP_TRY(hipMemsetAsync(S.acc, 0, sizeof(int), st));
+    }
+    if (n == 0) {                                                  // after the last chunk
+        if (o.count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 1, st)))
+            return fail(KWS_ERROR_HIP, "count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        return EI_IMPULSE_OK;
+    }
+    // slide calls write no logits tap (out of the tap's [B][labels] shape): the tap is set aside for the step
+    struct TapAside {
+        kws_handle *h; float *t;
+        ~TapAside() { h->tap_logits = t; }
+    } tap_aside{ h, h->tap_logits };
+    h->tap_logits = nullptr;
+    EI_IMPULSE_ERROR e;
+    float *f = o.features ? o.features + g0 * F : nullptr;
+    if (o.fast) e = cmvn_nn_fast_device(h, win, n, o.scores + g0 * C, st, 0, 0, f);
+    else e = cmvn_nn_device(h, win, n, f, nullptr, o.scores + g0 * C, nullptr, nullptr, nullptr, st);
     if (e) return e;
-    if (n_samples > kSlideMaxSamples) return fail(KWS_ERROR_BAD_ARGUMENT, "recording of %zu samples", n_samples);
-    const size_t clip = h->model.raw_sample_count;
-    *n_windows = n_samples < clip ? 0 : (n_samples - clip) / hop_samples + 1;
+    if (o.count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 0, st)))
+        return fail(KWS_ERROR_HIP, "count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return EI_IMPULSE_OK;
 }
 
-EI_IMPULSE_ERROR kws_slide_plan(const kws_handle *h, const size_t *lengths, size_t R, size_t hop_samples, int flags, kws_slide_plan_info *out)
+// The slide: argument checks, staging, cepstral rows and gathering for the handle's DSP block; every chunk of gathered windows
+// (win [n][F] cepstra before cmvnw, the call's windows g0 .. g0 + n - 1) goes to finish(), which is called once more with n == 0 after
+// the last chunk.  take_lock == 0: the caller holds h->mu (kws_bank.cpp, which holds every member's).
+EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R, size_t hop_samples, int flags,
+                               int take_lock, kws_slide_finish_fn finish, void *ctx, hipStream_t st)
 {
-    if (!h || !out) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    SlideGeom G;
-    return slide_plan(h, lengths, R, hop_samples, flags, &G, out);
-}
-
-EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
-                                             size_t hop_samples, int flags, float *scores, float *features, void *stream)
-{
-    if (!h || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (R > 0 && (!pcm || !offsets || !lengths)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     SlideGeom G;
     kws_slide_plan_info I;
@@ -183,12 +203,11 @@ EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, 
     }
     const size_t A = off.size(), NS = ssrc.size(), n_win = I.n_windows, n_items = (size_t)ibase.back();
     if (NS > 0x3fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "too many recordings x phases");
-    const Model &m = h->model;
-    const size_t F = m.nn_input_frame_size, C = m.labels.size();
+    const size_t F = h->model.nn_input_frame_size;
     const int ncols = G.ncols, nfi = G.nfi;
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(h->mu);
+    std::unique_lock<std::mutex> lk(h->mu, std::defer_lock);
+    if (take_lock) lk.lock();
     if (!h->slide) { h->slide = new KwsSlideScratch(); h->slide_release = slide_release; }
     KwsSlideScratch &S = *h->slide;
     // staged items: a run item is nfi frames one stride apart; a frame-0 item is nfi slots of S1 samples; a direct item is a window
@@ -213,12 +232,6 @@ EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, 
         (e = grow_buffer(&S.first, &S.first_cap, shared && G.pre ? first_items * nfi * ncols : 1)) || (e = grow_buffer(&S.meta, &S.meta_cap, n_meta)) ||
         (e = grow_buffer(&S.acc, &S.acc_cap, 1)) || (e = ensure_scratch(h, win_chunk)))
         return e;
-    // slide calls write no logits tap (out of the tap's [B][labels] shape): the tap is set aside for the call
-    struct TapAside {
-        kws_handle *h; float *t;
-        ~TapAside() { h->tap_logits = t; }
-    } tap_aside{ h, h->tap_logits };
-    h->tap_logits = nullptr;
     ScratchUse use(h, st);
     // tables: off [A], end [A], wbase [A + 1], sbase [A + 1], ssrc [NS], send [NS], ibase [NS + 1].  The host copy is complete before the call goes on
     std::vector<long long> meta;
@@ -248,10 +261,7 @@ EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, 
     PF.n_samples = (int)first_len;
     PF.n_frames = nfi;
     PF.wrap_index = PF.n_samples - 1;
-    // 2. windows in chunks through cmvnw + the network
-    const bool fast = h->mode == KWS_MODE_FAST && h->fast_plain_ok;
-    const bool count = fast && m.dsp.block != DSP_BLOCK_MFE;          // the MFE block's fast form is its exact one: no guard, no counts
-    if (count) HIP_TRY(hipMemsetAsync(S.acc, 0, sizeof(int), st));
+    // 2. windows in chunks through the finishing step (cmvnw + the network)
     for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
         const int n = (int)std::min(win_chunk, n_win - g0);
         if (shared) {
@@ -275,16 +285,41 @@ EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, 
                 if ((e = spectral_device(h, h->dsp, S.stage, 0, nw, S.win + i0 * F, nullptr, st, 0))) return e;
             }
         }
-        float *f = features ? features + g0 * F : nullptr;
-        if (fast) e = cmvn_nn_fast_device(h, S.win, n, scores + g0 * C, st, 0, 0, f);
-        else e = cmvn_nn_device(h, S.win, n, f, nullptr, scores + g0 * C, nullptr, nullptr, nullptr, st);
-        if (e) return e;
-        if (count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 0, st)))
-            return fail(KWS_ERROR_HIP, "count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if ((e = finish(ctx, S.win, (size_t)n, g0, st))) return e;
     }
-    if (count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 1, st)))
-        return fail(KWS_ERROR_HIP, "count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return finish(ctx, S.win, 0, n_win, st);
+}
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int kws_frame_stride_samples(const kws_handle *h) { return h->dsp.frame_stride; }
+
+EI_IMPULSE_ERROR kws_slide_window_count(const kws_handle *h, size_t n_samples, size_t hop_samples, size_t *n_windows)
+{
+    if (!h || !n_windows) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    *n_windows = 0;
+    EI_IMPULSE_ERROR e = slide_check(h, hop_samples, KWS_SLIDE_AUTO);
+    if (e) return e;
+    if (n_samples > kSlideMaxSamples) return fail(KWS_ERROR_BAD_ARGUMENT, "recording of %zu samples", n_samples);
+    const size_t clip = h->model.raw_sample_count;
+    *n_windows = n_samples < clip ? 0 : (n_samples - clip) / hop_samples + 1;
     return EI_IMPULSE_OK;
+}
+
+EI_IMPULSE_ERROR kws_slide_plan(const kws_handle *h, const size_t *lengths, size_t R, size_t hop_samples, int flags, kws_slide_plan_info *out)
+{
+    if (!h || !out) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    SlideGeom G;
+    return slide_plan(h, lengths, R, hop_samples, flags, &G, out);
+}
+
+EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                             size_t hop_samples, int flags, float *scores, float *features, void *stream)
+{
+    if (!h || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    SlideOwn own{ h, scores, features };
+    return kws_slide_run(h, pcm, offsets, lengths, R, hop_samples, flags, 1, slide_own_finish, &own, (hipStream_t)stream);
 }
 
 #pragma GCC visibility pop

@@ -303,6 +303,51 @@ EI_IMPULSE_ERROR kws_slide_plan(const kws_handle *h, const size_t *lengths, size
 EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
                                              size_t hop_samples, int flags, float *scores, float *features, void *stream);
 
+/* ---- banks: K models that share one DSP block, scored in one call; the DSP block runs once -----------------------------------------
+ * A bank is K model handles with an identical DSP block.  A bank call computes the front end once -- the feature matrix, from clips,
+ * from cepstra or from the windows of whole recordings -- and every member's scores from it: an int8 graph next to its float32 twin,
+ * a 2-conv graph next to a DS-CNN, one tenant's keyword set next to another's.
+ * Membership.  1 <= K <= 16 handles on one device, none of them twice, equal in: DSP block kind (MFCC / MFE), every field of the DSP
+ * configuration (axes, num_cepstral, frame_length, frame_stride, num_filters, fft_length, win_size, low_frequency, high_frequency,
+ * pre_cof, pre_shift), sampling frequency, raw_sample_count and EIDSP_QUANTIZE_FILTERBANK -- so frames, columns and feature_count are
+ * equal too.  int8 and float32 graphs, tuned and general-shape plans, MFCC and MFE blocks all qualify; label counts may differ.
+ * Anything else: KWS_ERROR_BAD_ARGUMENT, kws_last_error names the first differing field.  kws_bank_create changes no member; a member
+ * stays usable on its own; destroy banks before their members (kws_bank_destroy waits for the bank's enqueued work).
+ * Parity contract.  Member k's rows of scores[k] are bit-identical to what kws_run_classifier_batch_device,
+ * kws_cmvn_inference_batch_device or kws_slide_recordings_device writes for that member alone in KWS_MODE_EXACT on the same input, for
+ * int8 and float32 graphs alike, and `features` is bit-identical to any member's own: int8 scores and features bit-exact with the
+ * reference, float32 scores within 1e-6.  The slide's paths (AUTO, DIRECT, SHARED) stay bit-identical to each other.
+ *   scores    HOST array of K DEVICE pointers; scores[k] is [rows][kws_label_count(member k)] float, or NULL to skip member k in this call
+ *   features  [rows][feature_count] float, device, optional (NULL): the shared feature matrix
+ *   rows      B; for the slide sum_r W_r -- window counts (kws_slide_window_count) and kws_slide_plan are any member's
+ *   other arguments as in the single-model entry point of the same name
+ * Mode.  Bank calls always run the exact kernels, like the host-buffer entry point: they neither read nor change the members'
+ * kws_set_mode state, fast counters (kws_fast_fallback_count / kws_fast_exact_count) or logits taps, and write no tap.
+ * B = 0, or no recording long enough for a window: EI_IMPULSE_OK, nothing written.  Every scores[k] NULL and features NULL, a NULL
+ * bank, pcm / mfcc or scores array, B >= 2^31, and whatever kws_slide_recordings_device refuses: KWS_ERROR_BAD_ARGUMENT.
+ * Ordering.  A bank call counts as a call on EVERY member handle for the rules at the top of this file (a call on another stream than a
+ * member's previous call first waits for that call); it holds the members' locks for its duration, taken in one fixed order (by
+ * address) whatever the members' order, so banks over the same handles cannot deadlock.  Calls on one bank are serialised.
+ * Device memory.  The bank owns K records of 1 072 bytes (the int8 members' plans, written once) and, for calls without `features`, the shared
+ * feature matrix: B x feature_count floats (the slide: one chunk, at most 64 MiB), grown on demand; growing synchronises the device.
+ * int8 members outside the two-block matrix-core shape take their input tensor from their own batch scratch (grown to B clips: 5 bytes
+ * per feature value, as for their own calls); the slide reuses the FIRST member's slide scratch, with kws_slide_recordings_device's
+ * bounds, and that member's batch scratch for one chunk. */
+typedef struct kws_bank kws_bank;
+EI_IMPULSE_ERROR kws_bank_create(kws_handle *const *members, size_t K, kws_bank **out);
+void kws_bank_destroy(kws_bank *b);
+size_t kws_bank_size(const kws_bank *b);
+kws_handle *kws_bank_member(const kws_bank *b, size_t k);                  /* NULL for k >= K */
+/* run_classifier() for B clips and K models: the DSP block once, every member's network from its output */
+EI_IMPULSE_ERROR kws_bank_run_classifier_batch_device(kws_bank *b, const int16_t *pcm, size_t B, float *const *scores, float *features,
+                                                      void *stream);
+/* the same from cepstra before cmvnw (kws_mfcc_batch_device of any member): cmvnw / the MFE normalisation once */
+EI_IMPULSE_ERROR kws_bank_cmvn_inference_batch_device(kws_bank *b, const float *mfcc, size_t B, float *const *scores, float *features,
+                                                      void *stream);
+/* kws_slide_recordings_device for K models: staging, cepstral rows, gathering and cmvnw once per window */
+EI_IMPULSE_ERROR kws_bank_slide_recordings_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                  size_t hop_samples, int flags, float *const *scores, float *features, void *stream);
+
 /* ---- live continuous mode: audio of any length pushed to any subset of S streams, state in HBM between calls ----------------------
  * A session holds S streams at one slicing.  A push hands any number of new samples (0 included) to any subset of the streams, each its
  * own length, and returns every window those samples complete; finishing a stream flushes what waited for its look-ahead sample and the
