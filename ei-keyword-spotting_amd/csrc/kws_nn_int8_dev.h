@@ -55,6 +55,10 @@ __device__ __forceinline__ int one_over_one_plus_x(int a)     // fixedpoint.h:84
 //  owns one clip.  conv accumulators are exact int32 (v_dot4_i32_i8); because requantisation, the folded
 //  ADD+ReLU table and the clamps are all monotonically non-decreasing, max-pooling is applied to the raw
 //  accumulators first (max commutes with a non-decreasing map), then ONE requantisation per pooled output.
+//  PRECONDITION: requantisation is non-decreasing only while its left shift (multipliers of 1 and more) cannot
+//  wrap: (unsigned)(acc + bias) << ls wraps from |acc + bias| = 2^(31 - ls) on.  build_nn_plan (kws_plan.cpp)
+//  refuses every model in which (sum|w| * max|x + input offset| + |bias|) << ls can pass 2^31 - 1 for some
+//  channel, and every negative multiplier and non-monotonic ADD table, so no kernel here ever sees one.
 // ---------------------------------------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));

@@ -176,6 +176,15 @@ EI_IMPULSE_ERROR kws_plan_for_length(kws_handle *h, size_t n, KwsDspPlan *out)
 
 static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h);
 
+// (sum|w| * max(|-128 + in_off|, |127 + in_off|) + |bias|) << shift > 2^31 - 1: the largest |accumulator + bias| any int8 input
+// can produce, shifted left as MultiplyByQuantizedMultiplier shifts it, leaves int32
+static bool h_left_shift_overflows(int64_t wabs, int32_t in_off, int32_t bias, int shift)
+{
+    const int64_t xmax = std::max(std::llabs(-128ll + in_off), std::llabs(127ll + in_off));
+    const int64_t bound = wabs * xmax + std::llabs((long long)bias);
+    return shift > 30 || bound > (0x7fffffffll >> shift);
+}
+
 // Recognise the Edge Impulse 1-D CNN family and fold its per-model constants.
 EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
 {
@@ -246,18 +255,18 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         const bool per_channel = w.scale.size() > 1;
         if (per_channel && (int)w.scale.size() != out_c) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "per-channel scale count");
         for (int oc = 0; oc < out_c; oc++) {
-            int64_t wsum = 0;
+            int64_t wsum = 0, wabs = 0;
             for (int tap = 0; tap < f_w; tap++) {
                 if (dw) {
                     const int8_t v = wd[(size_t)tap * out_c + oc];
                     wp[(size_t)oc * tp4 + tap] = v;
-                    wsum += v;
+                    wsum += v; wabs += std::abs((int)v);
                     continue;
                 }
                 for (int c = 0; c < in_c; c++) {
                     const int8_t v = wd[((size_t)oc * f_w + tap) * in_c + c];
                     wp[((size_t)oc * f_w + tap) * k.in_cpad + c] = v;
-                    wsum += v;
+                    wsum += v; wabs += std::abs((int)v);
                 }
             }
             beff[oc] = (int32_t)((bias ? ((const int32_t *)bias->data.data())[oc] : 0) + (int64_t)in_off * wsum);
@@ -266,6 +275,12 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
             h_quantize_multiplier(eff, &mult[oc], &sh);          // kernel_util_lite.cc:89-103
             shift[oc] = sh;
             if (mult[oc] < 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "negative requantisation multiplier");
+            // A multiplier of 1 or more shifts the accumulator LEFT before the multiplication (common.h:138-162).  Past 2^31 that is a
+            // signed overflow in the reference (undefined), and a wrap here: requantisation then stops being monotonic, and the kernels
+            // pool raw accumulators on the strength of that (kws_nn_int8_dev.h).  Refused when any input could reach the overflow.
+            if (sh > 0 && h_left_shift_overflows(wabs, in_off, bias ? ((const int32_t *)bias->data.data())[oc] : 0, sh))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv block %d channel %d: requantisation shifts left by %d and (sum|w| * max|x| + |bias|) << %d "
+                            "can pass 2^31 - 1", N.n_blocks, oc, sh, sh);
         }
         cur = cv.out[0]; cur_w = out_w; cur_c = out_c;
         i++;
@@ -380,6 +395,13 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         h_quantize_multiplier(in_prod / (double)y.scale[0], &mult, &exponent);
         N.fc_mult = mult; N.fc_shift = exponent;
         h_act_range(fc.p[0], y.scale[0], y.zero[0], &N.fc_act_min, &N.fc_act_max);
+        for (int o = 0; exponent > 0 && o < N.fc_out; o++) {                      // the same left-shift bound as the conv blocks
+            int64_t wabs = 0;
+            for (int d = 0; d < N.fc_in; d++) wabs += std::abs((int)((const int8_t *)w.data.data())[(size_t)o * N.fc_in + d] + N.fc_w_off);
+            if (h_left_shift_overflows(wabs, N.fc_in_off, bias ? ((const int32_t *)bias->data.data())[o] : 0, exponent))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "FULLY_CONNECTED output %d: requantisation shifts left by %d and (sum|w| * max|x| + |bias|) << %d "
+                            "can pass 2^31 - 1", o, exponent, exponent);
+        }
         std::vector<int8_t> wv((const int8_t *)w.data.data(), (const int8_t *)w.data.data() + w.nbytes);
         std::vector<int32_t> bv(N.fc_out, 0);
         if (bias) memcpy(bv.data(), bias->data.data(), sizeof(int32_t) * N.fc_out);

@@ -711,3 +711,407 @@ def random_dsp_spec(seed):
     cfg_kw = dict(num_filters=nf, num_cepstral=ncep, win_size=win, low_frequency=low, high_frequency=high)
     blob_kw = dict(seed=900 + seed, num_filters=nf, ncep=ncep, win_size=win, low=low, high=high, blocks=((8, 3, 7), (4, 3, 7)), n_labels=3)
     return cfg_kw, blob_kw
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  the int8 network at the edges of its quantisation (tests/test_gpu_quant_edges.py, the CPU pins in
+#  tests/test_oracle_vs_reference.py, tests/golden/quant_edges_l476.npz)
+# ---------------------------------------------------------------------------------------------------------------
+# The smallest graphs at which each int8 kernel path still exists (none had to be adjusted: the plan accepts all three).
+QUANT_EDGE_GRAPHS = {
+    # two-block matrix-core kernel with 16-byte rows; under kws_dev_force_scalar_nn(1) the generic kernel's pooled sdot4 path
+    "g2": dict(seed=81, ncep=13, blocks=((24, 3, 7), (8, 3, 7)), n_labels=4),
+    # the same blocks behind 40 cepstra: kws_nn_mfma_kernel<64>
+    "g2w": dict(seed=82, num_filters=40, ncep=40, low=300, high=0, blocks=((24, 3, 7), (8, 3, 7)), n_labels=4),
+    # generic kernel: two un-pooled matrix-core blocks (conv 8, pointwise 12), the four-channel-group depthwise path (multiplier 1)
+    # and the general one (multiplier 2), a VALID-pooled sdot4 block with 32-byte rows
+    "gd": dict(seed=94, ncep=13, blocks=((8, 3, 1), ("dw", 1, 3, 7, 1), ("pw", 12, 1), ("dw", 2, 3, 1, 0), (4, 3, -2)), n_labels=4),
+}
+QUANT_EDGE_REQUANT_OPS = {"g2": 2, "g2w": 1, "gd": 5}     # CONV_2D / DEPTHWISE_CONV_2D positions edited per graph (g2w: its first block)
+QUANT_EDGE_SPARSE_SEED = 20240611                          # the sparse weights' own generator: nothing is drawn from the model's
+
+
+class GraphEdit:
+    """A synthetic graph's (tensors, nodes) with the operations the edge table needs.  Every setter keeps the graph
+    self-consistent: an activation's scale / zero point is changed on every non-constant tensor that shares it (through
+    RESHAPE and MAX_POOL_2D, in both directions), and finish() recomputes every int32 bias scale."""
+
+    def __init__(self, tensors, nodes):
+        self.t, self.n = tensors, nodes
+
+    def requant(self, k):
+        return [nd for nd in self.n if nd["op"] in (1, 6)][k]
+
+    def op(self, code):
+        return [nd for nd in self.n if nd["op"] == code][0]
+
+    def group(self, tid):
+        g, grew = {tid}, True
+        while grew:
+            grew = False
+            for nd in self.n:
+                if nd["op"] in (0, 3) and ((nd["in"][0] in g) != (nd["out"][0] in g)):
+                    g |= {nd["in"][0], nd["out"][0]}
+                    grew = True
+        return g
+
+    def producer(self, tid):
+        g = self.group(tid)
+        return next((nd for nd in self.n if nd["op"] not in (0, 3) and nd["out"][0] in g), None)
+
+    def consumer(self, tid):
+        g = self.group(tid)
+        return next((nd for nd in self.n if nd["op"] not in (0, 3) and any(i in g for i in nd["in"])), None)
+
+    def add_behind(self, nd):
+        c = self.consumer(nd["out"][0])
+        return c if c is not None and c["op"] == 2 else None
+
+    def set_quant(self, tid, scale=None, zero=None):
+        for i in self.group(tid):
+            if scale is not None:
+                self.t[i]["scale"] = [float(np.float32(scale))]
+            if zero is not None:
+                self.t[i]["zero"] = [int(zero)]
+
+    def drop_activation_of(self, tid):
+        """the producer of activation tid loses its fused ReLU (a zero point of +127 under a ReLU leaves one value)"""
+        nd = self.producer(tid)
+        if nd is not None and nd["op"] in (1, 6):
+            nd["p"][3] = 0
+        elif nd is not None and nd["op"] in (2, 4):
+            nd["p"][0] = 0
+
+    def scale_weights(self, nd, factor):
+        tw = self.t[nd["in"][1]]
+        tw["scale"] = [float(np.float32(s * factor)) for s in tw["scale"]]
+
+    def set_scales(self, nd, in_scale=None, w_scale=None, out_scale=None, per_tensor=False):
+        """scales of a CONV_2D / DEPTHWISE_CONV_2D / FULLY_CONNECTED node.  A new output scale is followed downstream so that
+        the ops behind keep the multipliers they were drawn with: an ADD behind has its constant and its output rescaled by the
+        same ratio, and the next convolution's / FULLY_CONNECTED's weight scales are divided by it."""
+        if in_scale is not None:
+            self.set_quant(nd["in"][0], scale=in_scale)
+        tw = self.t[nd["in"][1]]
+        if w_scale is not None:
+            tw["scale"] = [float(np.float32(w_scale))] * len(tw["scale"])
+        if per_tensor:
+            tw["scale"], tw["zero"] = tw["scale"][:1], tw["zero"][:1]
+        if out_scale is not None:
+            o = nd["out"][0]
+            r = float(np.float32(out_scale)) / self.t[o]["scale"][0]
+            self.set_quant(o, scale=out_scale)
+            nxt = self.consumer(o)
+            if nxt is not None and nxt["op"] == 2:
+                tc = self.t[[i for i in nxt["in"] if self.t[i]["const"]][0]]
+                tc["scale"] = [float(np.float32(tc["scale"][0] * r))]
+                o = nxt["out"][0]
+                self.set_quant(o, scale=self.t[o]["scale"][0] * r)
+                nxt = self.consumer(o)
+            if nxt is not None and nxt["op"] in (1, 4, 6):
+                self.scale_weights(nxt, 1.0 / r)
+
+    def set_multiplier(self, nd, eff):
+        """weight scales alone (every channel the same) so that in * w / out is eff to float32 precision: nothing else moves"""
+        i, o = self.t[nd["in"][0]]["scale"][0], self.t[nd["out"][0]]["scale"][0]
+        self.set_scales(nd, w_scale=eff * o / i)
+
+    def set_multiplier_pow2(self, nd, eff):
+        """eff (a power of two) EXACTLY: the output scale becomes the input scale times the nearest power of two, the weight
+        scales the power of two that is left"""
+        i, o = self.t[nd["in"][0]]["scale"][0], self.t[nd["out"][0]]["scale"][0]
+        k = int(np.round(np.log2(o / i)))
+        self.set_scales(nd, w_scale=eff * 2.0 ** k, out_scale=float(np.float32(i)) * 2.0 ** k)
+        ii, oo, ww = (np.float64(self.t[x]["scale"][0]) for x in (nd["in"][0], nd["out"][0], nd["in"][1]))
+        assert ii * ww / oo == eff
+
+    def set_bias(self, nd, values):
+        tb = self.t[nd["in"][2]]
+        n = tb["dims"][0]
+        tb["data"] = np.resize(np.asarray(values, np.int64), n).astype(np.int32).tobytes()
+
+    def sparse_weights(self, nd):
+        """two +-1 entries per output channel and biases in +-20: a left-shifting op with drawn weights clamps 99 % of its outputs"""
+        rng = np.random.default_rng(QUANT_EDGE_SPARSE_SEED)
+        tw = self.t[nd["in"][1]]
+        dims = tw["dims"]
+        if nd["op"] == 6:                                  # [1][1][taps][out_c]: a channel's weights are its taps
+            n_out, per = dims[3], dims[2]
+            w = np.zeros((per, n_out), np.int8)
+            for c in range(n_out):
+                w[rng.choice(per, 2, replace=False), c] = rng.choice([-1, 1], 2)
+        else:                                              # [out_c][1][taps][in_c] or FULLY_CONNECTED [out][in]
+            n_out, per = dims[0], int(np.prod(dims[1:]))
+            w = np.zeros((n_out, per), np.int8)
+            for c in range(n_out):
+                w[c, rng.choice(per, 2, replace=False)] = rng.choice([-1, 1], 2)
+        tw["data"] = w.tobytes()
+        self.set_bias(nd, rng.integers(-20, 21, n_out))
+
+    def finish(self):
+        """every int32 bias scale = float32(input scale) * float32(weight scale[ch]) (kernel_util_lite.cc:47-120 checks that product)"""
+        for nd in self.n:
+            if nd["op"] in (1, 4, 6) and len(nd["in"]) > 2:
+                tw, tb = self.t[nd["in"][1]], self.t[nd["in"][2]]
+                i = np.float32(self.t[nd["in"][0]]["scale"][0])
+                tb["scale"] = [float(i * np.float32(s)) for s in tw["scale"]]
+                tb["zero"] = [0] * len(tw["scale"])
+
+
+# The triple whose double-precision quotient 0x1.fffffffec003dp-1 rounds to 2^31 in QuantizeMultiplier: multiplier 2^30, shift +1
+ROLLOVER_SCALES = (0.05988423526287079, 0.005621093790978193, 0.000336614903062582)
+_EFF_M31 = 1.5 * 2.0 ** -32          # frexp: 0.75 * 2^-31 -> shift -31 exactly
+_EFF_ZERO = 1.5 * 2.0 ** -33         # frexp: 0.75 * 2^-32 -> shift < -31 -> multiplier 0
+# round(x * 0.75 / 2^31) changes at |x| = 2^30 / 0.75: with these biases (sign alternating by channel) the accumulators straddle
+# the only rounding boundary a shift of -31 has inside the int32 range, so the output takes zero point - 1, zero point, zero point + 1
+_BIAS_M31 = (1431655765, -1431655765)
+
+
+def _rq_mult_one(g, nd): g.set_multiplier_pow2(nd, 1.0)
+def _rq_mult_half(g, nd): g.set_multiplier_pow2(nd, 0.5)
+def _rq_mult_1_37(g, nd): g.set_multiplier(nd, 1.37)
+def _rq_mult_3(g, nd): g.set_multiplier(nd, 2.9)
+def _rq_rollover(g, nd): g.set_scales(nd, *ROLLOVER_SCALES)
+def _rq_zero_mult(g, nd): g.set_multiplier(nd, _EFF_ZERO)
+def _rq_per_tensor(g, nd): g.set_scales(nd, per_tensor=True)
+
+
+def _rq_shift_m31(g, nd):
+    g.set_multiplier(nd, _EFF_M31)
+    g.set_bias(nd, _BIAS_M31)
+
+
+def _zp(which, value):
+    def f(g, nd):
+        tid = nd["in"][0] if which == "in" else nd["out"][0]
+        if value == 127:
+            g.drop_activation_of(tid)
+        g.set_quant(tid, zero=value)
+    return f
+
+
+# case -> (edit of one requantising node, its left shift is positive)
+QUANT_EDGE_REQUANT_CASES = {
+    "mult_one": (_rq_mult_one, True), "mult_half": (_rq_mult_half, False), "mult_1_37": (_rq_mult_1_37, True),
+    "mult_3": (_rq_mult_3, True), "rollover": (_rq_rollover, True), "shift_m31": (_rq_shift_m31, False),
+    "zero_mult": (_rq_zero_mult, False), "per_tensor": (_rq_per_tensor, False),
+    "in_zp_m128": (_zp("in", -128), False), "in_zp_p127": (_zp("in", 127), False),
+    "out_zp_m128": (_zp("out", -128), False), "out_zp_p127": (_zp("out", 127), False),
+}
+# mult_half has shift 0, not a left shift, but its drawn weights clamp as much (measured 0.99): it gets the sparse variant too
+QUANT_EDGE_SPARSE_CASES = ("mult_one", "mult_half", "mult_1_37", "mult_3", "rollover")
+
+
+def _add_const_first(g, ad): ad["in"].reverse()
+def _add_act_none(g, ad): ad["p"][0] = 0
+def _add_relu6(g, ad): ad["p"][0] = 3
+def _add_out_zp(g, ad): g.set_quant(ad["out"][0], zero=-77)
+
+
+def _add_const_x100(g, ad):
+    tc = g.t[[i for i in ad["in"] if g.t[i]["const"]][0]]
+    tx = g.t[[i for i in ad["in"] if not g.t[i]["const"]][0]]
+    tc["scale"] = [float(np.float32(100.0 * tx["scale"][0]))]
+    # one step of the constant is now 100 steps of the other input: the drawn values (-127 .. 0) would push every sum under the ReLU
+    tc["data"] = np.random.default_rng(QUANT_EDGE_SPARSE_SEED).integers(-1, 2, tc["dims"][0]).astype(np.int8).tobytes()
+
+
+QUANT_EDGE_ADD_CASES = {"const_first": _add_const_first, "act_none": _add_act_none, "relu6": _add_relu6, "const_x100": _add_const_x100,
+                        "out_zp_m77": _add_out_zp}
+
+
+def _fc_w_zp(v):
+    def f(g): g.t[g.op(4)["in"][1]]["zero"] = [v]
+    return f
+
+
+def _fc_relu(g): g.op(4)["p"][0] = 1
+def _fc_out_scale(v):
+    def f(g): g.set_quant(g.op(4)["out"][0], scale=v)
+    return f
+
+
+def _beta(v):
+    def f(g): g.op(5)["beta"] = v
+    return f
+
+
+QUANT_EDGE_HEAD_CASES = {"fc_w_zp_m7": _fc_w_zp(-7), "fc_w_zp_p9": _fc_w_zp(9), "fc_relu": _fc_relu, "fc_out_scale_2": _fc_out_scale(2.0),
+                         "fc_out_scale_1e-4": _fc_out_scale(1e-4), "beta_0.25": _beta(0.25), "beta_4": _beta(4.0)}
+QUANT_EDGE_LABELS = (13, 16, 17, 32, 33, 47, 48)          # gd: fc_in = 24 * 4 = 96, 96 * 48 <= 32768
+
+
+def _wrap(g, nd):
+    """requantise-then-max != max-then-requantise: multiplier 1610612881, shift +2, and biases that put (acc + bias) << 2 past 2^31"""
+    i = g.t[nd["in"][0]]["scale"][0]
+    g.set_scales(nd, w_scale=0.004, out_scale=float(np.float32(i)) * float(np.float32(0.004)) / 3.0)
+    g.set_bias(nd, [2 ** 29 - 20000])
+
+
+def _quant_edges():
+    """key -> dict(graph, kw, edit, where): where = ("rq", k) | ("fc",) names the op whose output the non-vacuity conditions look at"""
+    out = {}
+
+    def put(key, graph, where, fn, **kw):
+        def edit(tensors, nodes):
+            g = GraphEdit(tensors, nodes)
+            fn(g)
+            g.finish()
+        out[key] = dict(graph=graph, kw=dict(QUANT_EDGE_GRAPHS[graph], **kw), edit=edit, where=where)
+
+    for graph, n_rq in QUANT_EDGE_REQUANT_OPS.items():
+        targets = [("c%d" % k, ("rq", k)) for k in range(n_rq)] + ([("fc", ("fc",))] if graph != "g2w" else [])
+        for tname, where in targets:
+            def node_of(g, where=where):
+                return g.requant(where[1]) if where[0] == "rq" else g.op(4)
+            for case, (fn, _) in QUANT_EDGE_REQUANT_CASES.items():
+                if where[0] == "fc" and case == "per_tensor":
+                    continue                                                   # the FULLY_CONNECTED scale is per tensor already
+                put("%s/%s/%s" % (graph, tname, case), graph, where, lambda g, fn=fn, node_of=node_of: fn(g, node_of(g)))
+                if case in QUANT_EDGE_SPARSE_CASES:
+                    def both(g, fn=fn, node_of=node_of):
+                        fn(g, node_of(g))
+                        g.sparse_weights(node_of(g))
+                    put("%s/%s/%s+sparse" % (graph, tname, case), graph, where, both)
+    for graph in ("g2", "gd"):
+        n_rq = QUANT_EDGE_REQUANT_OPS[graph]
+        adds = [k for k in range(n_rq) if not isinstance(QUANT_EDGE_GRAPHS[graph]["blocks"][k][0], str)]      # (out_c, taps, pool) blocks
+        for k in adds:
+            for case, fn in QUANT_EDGE_ADD_CASES.items():
+                put("%s/add%d/%s" % (graph, k, case), graph, ("add", k), lambda g, fn=fn, k=k: fn(g, g.add_behind(g.requant(k))))
+        for case, fn in QUANT_EDGE_HEAD_CASES.items():
+            put("%s/head/%s" % (graph, case), graph, ("fc",), fn)
+        for n in QUANT_EDGE_LABELS:
+            put("%s/labels/%d" % (graph, n), graph, ("fc",), lambda g: None, n_labels=n)
+    return out
+
+
+QUANT_EDGES = _quant_edges()
+
+
+def _quant_refusals():
+    """models kws_create must refuse with KWS_ERROR_UNSUPPORTED_MODEL: key -> synth_model_blob keyword arguments (edit included)"""
+    out = {}
+
+    def put(key, kw, k):
+        def edit(tensors, nodes):
+            g = GraphEdit(tensors, nodes)
+            _wrap(g, g.requant(k))
+            g.finish()
+        out[key] = dict(kw, edit=edit)
+    put("wrap/conv8", dict(seed=84, blocks=((8, 3, 7), (4, 3, 7)), add_bias=False), 0)       # the model of the report: 53 of 56 pooled outputs differ
+    put("wrap/g2_block2", QUANT_EDGE_GRAPHS["g2"], 1)
+    put("wrap/gd_depthwise", QUANT_EDGE_GRAPHS["gd"], 1)
+    put("wrap/gd_pointwise", QUANT_EDGE_GRAPHS["gd"], 2)
+    out["labels/49"] = dict(QUANT_EDGE_GRAPHS["g2"], n_labels=49)
+    return out
+
+
+QUANT_REFUSALS = _quant_refusals()
+
+
+def quant_edge_groups():
+    """the edge models by graph and edited op ("g2/c0", "gd/add4", "g2/labels", ...): one test case each, the cases of the op inside"""
+    return sorted({k.rsplit("/", 1)[0] for k in QUANT_EDGES})
+
+
+def quant_edge_blob(key):
+    e = QUANT_EDGES[key]
+    return synth_model_blob(edit=e["edit"], **e["kw"])
+
+
+def quant_edge_inputs(n_features, golden_rows=False):
+    """the input set of test_nn_bit_exact_random_int8 cut to 64 uniform rows, 64 normal(-11, 25) rows and the 256 constant rows;
+    golden_rows: the 24 of them tests/golden/quant_edges_l476.npz holds results for (8 uniform, 8 normal, every 32nd constant)"""
+    rng = np.random.default_rng(4)
+    qs = np.concatenate([rng.integers(-128, 128, (64, n_features)).astype(np.int8),
+                         np.clip(rng.normal(-11, 25, (64, n_features)), -128, 127).astype(np.int8),
+                         np.repeat(np.arange(-128, 128, dtype=np.int8)[:, None], n_features, 1)])
+    return qs[quant_edge_golden_rows()] if golden_rows else qs
+
+
+def quant_edge_golden_rows():
+    return np.concatenate([np.arange(8), 64 + np.arange(8), 128 + np.arange(0, 256, 32)])
+
+
+def quant_edge_tensor_ids(blob, where):
+    """(tensor id of the edited op's output, ids of every block's pooled tensor in block order, FULLY_CONNECTED output id) of a blob"""
+    import eon_import
+    tensors, nodes, _, _, _ = eon_import.parse_blob(blob)
+    g = GraphEdit(tensors, nodes)
+    rq = [nd for nd in nodes if nd["op"] in (1, 6)]
+    pooled = []
+    for k, nd in enumerate(rq):                              # the last activation before the next conv / the FULLY_CONNECTED, minus reshapes
+        end = rq[k + 1] if k + 1 < len(rq) else g.op(4)
+        tid = end["in"][0]
+        while True:
+            p = next(n_ for n_ in nodes if n_["out"][0] == tid)
+            if p["op"] != 0:
+                break
+            tid = p["in"][0]
+        pooled.append(tid)
+    fc = g.op(4)["out"][0]
+    if where[0] == "rq":
+        edited = rq[where[1]]["out"][0]
+    elif where[0] == "add":
+        edited = g.add_behind(rq[where[1]])["out"][0]
+    else:
+        edited = fc
+    return edited, pooled, fc
+
+
+def quant_edge_not_vacuous(key, edited, fc_rows):
+    """The conditions that keep a case from testing nothing, on the checker's output of the edited tensor alone (edited: that
+    tensor over all input rows; fc_rows: the FULLY_CONNECTED output [rows][labels]).  Returns None or what is wrong.
+      * at most 75 % of the values at -128 / 127 and at least 32 distinct values;
+      * FULLY_CONNECTED / head / label cases: the FC outputs take at least 5 distinct values;
+      * zero_mult: exempt, constant by design;
+      * shift_m31: a multiplier below 2^-31 maps the whole int32 range onto at most 3 values, so 32 cannot be asked: the biases
+        of _BIAS_M31 put the accumulators on both sides of a rounding boundary, and at least 2 distinct values are required;
+      * the drawn-weight variants of the left-shift cases clamp nearly everything (0.99 measured at multipliers 1 and 1/2): the
+        conditions are asserted on their +sparse variants, the drawn-weight ones only run."""
+    case = key.split("/")[2]
+    where = QUANT_EDGES[key]["where"]
+    if case == "zero_mult" or case in QUANT_EDGE_SPARSE_CASES:
+        return None
+    vals = np.unique(fc_rows if where[0] == "fc" else edited)
+    if case == "shift_m31":
+        return None if len(vals) >= 2 else "%d distinct values" % len(vals)
+    if where[0] == "fc":
+        return None if len(vals) >= 5 else "FC outputs take %d distinct values" % len(vals)
+    share = float(np.isin(edited, (-128, 127)).mean())
+    if share > 0.75:
+        return "%.2f of the values at the limits" % share
+    return None if len(vals) >= 32 else "%d distinct values" % len(vals)
+
+
+def quant_edge_digest(pooled_rows):
+    """[rows][pooled bytes] -> uint8 [rows][8]: the first 8 bytes of each row's SHA-256.  The pooled tensors of gd are 2.6 KB a
+    row, 221 models of them would be past any golden file's size; equal digests are equal tensors, and where they differ the
+    comparison with the checker's tensors (every test that reads these also makes it) says where."""
+    import hashlib
+    return np.stack([np.frombuffer(hashlib.sha256(np.ascontiguousarray(r).tobytes()).digest()[:8], np.uint8) for r in pooled_rows])
+
+
+def quant_edge_run(invoke, blob, where, qs):
+    """invoke(q) -> (output, every tensor) over the rows of qs: dict(out, fc, pooled = every block's pooled tensor concatenated in
+    block order -- the layout of the library's debug tap --, edited = the edited op's output), each [rows][...] int8"""
+    edited, pooled, fc = quant_edge_tensor_ids(blob, where)
+    r = dict(out=[], fc=[], pooled=[], edited=[])
+    for q in qs:
+        o, taps = invoke(q)
+        r["out"].append(np.array(o, np.int8))
+        r["fc"].append(np.array(taps[fc], np.int8))
+        r["pooled"].append(np.concatenate([np.asarray(taps[i], np.int8).reshape(-1) for i in pooled]))
+        r["edited"].append(np.array(taps[edited], np.int8).reshape(-1))
+    return {k: np.stack(v) for k, v in r.items()}
+
+
+def quant_edge_golden():
+    """tests/golden/quant_edges_l476.npz (tools/make_golden.py --only-quant-edges): key -> dict(out, fc [24][labels] int8,
+    pooled_sha [24][8] uint8), the reference's own op registrations on quant_edge_inputs(golden_rows=True)"""
+    g = np.load(os.path.join(GOLDEN, "quant_edges_l476.npz"))
+    n_rows = len(quant_edge_golden_rows())
+    offs = np.cumsum([0] + [int(n) * n_rows for n in g["n_labels"]])
+    return {str(k): dict(out=g["out"][offs[i]:offs[i + 1]].reshape(n_rows, -1), fc=g["fc"][offs[i]:offs[i + 1]].reshape(n_rows, -1),
+                         pooled_sha=g["pooled_sha"][i]) for i, k in enumerate(g["keys"])}

@@ -327,3 +327,24 @@ def test_quantized_filterbank_golden(oracle):
         assert (bits(oracle.filterbanks(cfg)) == bits(g[name + "_fb"])).all(), name
         for i, c in enumerate(clips):
             assert (bits(oracle.extract_mfcc(c, cfg)) == bits(g[name][i])).all(), (name, i)
+
+
+@pytest.mark.parametrize("group", __import__("kws_testlib").quant_edge_groups())
+def test_quant_edge_models_against_recorded_reference(group, oracle, tmp_path):
+    """tests/golden/quant_edges_l476.npz: what the reference's op registrations gave for every model of kws_testlib.QUANT_EDGES on 24
+    input rows (int8 output, FULLY_CONNECTED output, a digest of every block's pooled tensor) -- the restatement held to it where the
+    reference is not built, with the conditions that keep a case from testing nothing asserted over the full 384 rows."""
+    from kws_testlib import (QUANT_EDGES, OracleModel, quant_edge_blob, quant_edge_digest, quant_edge_golden, quant_edge_golden_rows,
+                             quant_edge_inputs, quant_edge_not_vacuous, quant_edge_run)
+    g = quant_edge_golden()
+    assert sorted(g) == sorted(QUANT_EDGES)
+    rows = quant_edge_golden_rows()
+    for key in [k for k in sorted(QUANT_EDGES) if k.rsplit("/", 1)[0] == group]:
+        blob = quant_edge_blob(key)
+        p = tmp_path / "m.kwsm"
+        p.write_bytes(blob)
+        om = OracleModel(oracle, str(p))
+        r = quant_edge_run(lambda q: om.nn_invoke(q, taps=True), blob, QUANT_EDGES[key]["where"], quant_edge_inputs(om.n_features))
+        assert (r["out"][rows] == g[key]["out"]).all() and (r["fc"][rows] == g[key]["fc"]).all(), key
+        assert (quant_edge_digest(r["pooled"][rows]) == g[key]["pooled_sha"]).all(), key
+        assert quant_edge_not_vacuous(key, r["edited"], r["fc"]) is None, (key, quant_edge_not_vacuous(key, r["edited"], r["fc"]))

@@ -363,3 +363,29 @@ def test_continuous_mode_at_other_slicings(slice_samples):
     p = subprocess.run([sys.executable, worker, str(slice_samples), "40"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
     assert "windows OK" in p.stdout
+
+
+@pytest.mark.parametrize("group", __import__("kws_testlib").quant_edge_groups())
+def test_quant_edge_models_through_reference_op_registrations(group, oracle, reference, tmp_path):
+    """The int8 graphs at the edges of their quantisation (kws_testlib.QUANT_EDGES: left shifts, shift 0, the 2^31 rollover of
+    QuantizeMultiplier, shift -31 and the zero multiplier, per-tensor scales, zero points at both ends, every ADD form, FULLY_CONNECTED
+    weight zero points / ReLU / scales, softmax beta, 13 .. 48 labels), each through the reference's own op registrations on the 384
+    input rows the GPU test uses: the restatement equals it on every non-constant tensor and on the output.  And each case tests
+    something: kws_testlib.quant_edge_not_vacuous on the checker's output of the edited tensor.
+    (No case had to be dropped: the reference's Prepare accepts every model of the table.)"""
+    from kws_testlib import QUANT_EDGES, OracleModel, quant_edge_blob, quant_edge_inputs, quant_edge_not_vacuous, quant_edge_run
+    keys = [k for k in sorted(QUANT_EDGES) if k.rsplit("/", 1)[0] == group]
+    assert keys
+    for key in keys:
+        blob = quant_edge_blob(key)
+        p = tmp_path / "m.kwsm"
+        p.write_bytes(blob)
+        om = OracleModel(oracle, str(p))
+        qs = quant_edge_inputs(om.n_features)
+        for q in qs:
+            out, taps = reference.graph_run(blob, q)
+            oo, ot = om.nn_invoke(q, taps=True)
+            assert (out == oo).all(), key
+            assert all((a == t).all() for a, t in zip(taps, ot) if a.dtype == np.int8), key
+        r = quant_edge_run(lambda q: om.nn_invoke(q, taps=True), blob, QUANT_EDGES[key]["where"], qs)
+        assert quant_edge_not_vacuous(key, r["edited"], r["fc"]) is None, (key, quant_edge_not_vacuous(key, r["edited"], r["fc"]))

@@ -18,6 +18,7 @@ Without arguments: leaves_l476, e2e_l476, deep_l476, continuous_l476, f32_twin_l
   --only-debug-cancel      debug_cancel_l476.npz    the text debug = true prints and what the cancellation polls do (FIRST user of continuous mode in its process)
   --only-other-length      other_length_l476.npz    run_classifier on windows of another length (1 .. 49 frames)
   --only-mfe-other-length  mfe_other_length_l432.npz  the same for the MFE-block model, composed from the L432 copy's leaves
+  --only-quant-edges       quant_edges_l476.npz     the int8 graphs at the edges of their quantisation (kws_testlib.QUANT_EDGES)
 """
 import os
 import sys
@@ -169,6 +170,26 @@ def graphs(ref):
         out[name + "_f32_scores"], out[name + "_f32_logits"] = np.stack(sf), np.stack(lf)
     np.savez_compressed(os.path.join(GOLDEN, "graphs_l476.npz"), **out)
     print("graphs_l476.npz", os.path.getsize(os.path.join(GOLDEN, "graphs_l476.npz")), "bytes")
+
+
+def quant_edges(ref):
+    """Every model of kws_testlib.QUANT_EDGES through the reference's own op registrations on 24 rng-seeded input rows
+    (quant_edge_inputs(golden_rows=True)): the int8 output and the FULLY_CONNECTED output in full, every block's pooled tensor
+    as a per-row digest (quant_edge_digest says why).  Recorded results only: models and inputs are regenerated in the tests."""
+    import eon_import
+    from kws_testlib import QUANT_EDGES, quant_edge_blob, quant_edge_digest, quant_edge_inputs, quant_edge_run
+    keys = sorted(QUANT_EDGES)
+    out = {"keys": np.array(keys), "n_labels": [], "out": [], "fc": [], "pooled_sha": []}
+    for key in keys:
+        blob = quant_edge_blob(key)
+        tens, _, t_in, _, _ = eon_import.parse_blob(blob)
+        r = quant_edge_run(lambda q: ref.graph_run(blob, q), blob, QUANT_EDGES[key]["where"], quant_edge_inputs(tens[t_in]["nbytes"], golden_rows=True))
+        out["n_labels"].append(r["out"].shape[1])
+        out["out"].append(r["out"].reshape(-1)); out["fc"].append(r["fc"].reshape(-1)); out["pooled_sha"].append(quant_edge_digest(r["pooled"]))
+    out["n_labels"] = np.int32(out["n_labels"])
+    out["out"], out["fc"], out["pooled_sha"] = np.concatenate(out["out"]), np.concatenate(out["fc"]), np.stack(out["pooled_sha"])
+    np.savez_compressed(os.path.join(GOLDEN, "quant_edges_l476.npz"), **out)
+    print("quant_edges_l476.npz", os.path.getsize(os.path.join(GOLDEN, "quant_edges_l476.npz")), "bytes;", len(keys), "models")
 
 
 def qfb(synth, cfg):
@@ -355,6 +376,8 @@ def main():
         return mfe_model(ref, Oracle(), L476_CONFIG())
     if "--only-graphs" in sys.argv:
         return graphs(ref)
+    if "--only-quant-edges" in sys.argv:
+        return quant_edges(ref)
     synth = Oracle()          # only used for kwso_synth_fill (shared integer generator)
     cfg = L476_CONFIG()
     os.makedirs(GOLDEN, exist_ok=True)

@@ -163,7 +163,7 @@ def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=2
 
 def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((30, 7, 7), (10, 7, 7)), n_labels=4,
                      conv_bias=False, add_bias=True, num_filters=32, raw_samples=16000, fft_length=256, frame_length=0.02,
-                     frame_stride=0.02, pre_cof=0.98, dsp_block="mfcc", logit_std=None, quantize_filterbank=False):
+                     frame_stride=0.02, pre_cof=0.98, dsp_block="mfcc", logit_std=None, quantize_filterbank=False, edit=None):
     """blocks: sequence of
          (out_channels, taps, pool)              CONV_2D 1xK (+ optional int32 bias) -> ADD(int8 per-channel)+ReLU -> MAX_POOL
          ("dw", depth_mult, taps, pool, act)     DEPTHWISE_CONV_2D 1xK with int32 bias and fused activation -> MAX_POOL
@@ -175,7 +175,10 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
        cmvnw hands the network --, every class's logit has zero mean and the logits' pooled deviation is logit_std (the shipped
        impulse's is 1.5).  No random draw is added or removed: every other tensor is the one the same seed gave before.
        Frame geometry defaults to the shipped one (1 s at 16 kHz, 20 ms frames and stride: 49 frames); raw_samples / frame_length /
-       frame_stride / fft_length / pre_cof change the DSP block (the frame count follows speechpy's rule, processing.hpp:260-284)."""
+       frame_stride / fft_length / pre_cof change the DSP block (the frame count follows speechpy's rule, processing.hpp:260-284).
+       edit: a callable edit(tensors, nodes) run on the finished graph just before it is serialised -- the way to any quantisation
+       parameter, constant or node option outside the drawn bands (tests/kws_testlib.py QUANT_EDGES).  It draws nothing from the
+       model's generator: with edit=None every blob is the one the same arguments gave before."""
     rng = np.random.default_rng(seed)
     flen_s = int(round(16000 * np.float32(frame_length)))
     n_frames = int(np.floor(np.float32(raw_samples - flen_s) / np.float32(round(16000 * np.float32(frame_stride)))))
@@ -297,6 +300,8 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
     node(5, [tfo], [tso], beta=1.0)
     if logit_std is not None:
         calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, float(logit_std), seed)
+    if edit is not None:
+        edit(tensors, nodes)
     meta = {"labels": ["label%d" % i for i in range(n_labels)],
             "dsp": {"axes": 1, "num_cepstral": ncep, "frame_length": frame_length, "frame_stride": frame_stride, "num_filters": num_filters,
                     "fft_length": fft_length, "win_size": win_size, "low_frequency": low, "high_frequency": high,
