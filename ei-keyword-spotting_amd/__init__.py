@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "kws_frame_stride_samples", "kws_slide_window_count", "kws_slide_plan", "kws_slide_recordings_device",
     "kws_bank_create", "kws_bank_destroy", "kws_bank_size", "kws_bank_member", "kws_bank_run_classifier_batch_device",
     "kws_bank_cmvn_inference_batch_device", "kws_bank_slide_recordings_device",
+    "kws_window_frame_count", "kws_run_classifier_ragged_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_extract_mfe_batch_device", "kws_set_mode", "kws_get_mode", "kws_fast_is_fused", "kws_fast_fallback_count", "kws_fast_exact_count", "kws_fast_guard",
     "kws_set_logits_tap", "kws_fast_gain", "kws_fast_tolerance_info",
@@ -175,6 +176,9 @@ def lib():
             L.kws_slide_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
             L.kws_slide_plan.argtypes = [vp, vp, sz, sz, i32, vp]
             L.kws_slide_recordings_device.argtypes = [vp, vp, vp, vp, sz, sz, i32, vp, vp, vp]
+        if hasattr(L, "kws_run_classifier_ragged_device"):
+            L.kws_window_frame_count.argtypes = [vp, sz]
+            L.kws_run_classifier_ragged_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp]
         if hasattr(L, "kws_bank_create"):
             L.kws_bank_create.argtypes = [vp, sz, C.POINTER(vp)]
             L.kws_bank_destroy.argtypes = [vp]
@@ -415,6 +419,19 @@ class Model:
         assert off.shape == ln.shape and off.ndim == 1
         _check(self.L.kws_slide_recordings_device(self.h, pcm_ptr, _p(off), _p(ln), off.size, hop_samples, flags, scores_ptr, features_ptr,
                                                   stream))
+
+    def window_frame_count(self, n_samples):
+        """frames the reference's framing yields for a window of n_samples (0: none fits)"""
+        return self.L.kws_window_frame_count(self.h, n_samples)
+
+    def run_classifier_ragged_device(self, pcm_ptr, offsets, lengths, scores_ptr, features_ptr=None, q_ptr=None, stream=None):
+        """run_classifier() for clips of their own lengths (int16 at pcm_ptr + offsets[i], lengths[i] samples each; device): scores
+        [len(lengths)][labels] and, optionally, features / the int8 input tensor [.][n_features], device -- rows zero-filled behind the frames
+        that fit.  scores_ptr=None skips the network.  offsets / lengths: host sequences."""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        _check(self.L.kws_run_classifier_ragged_device(self.h, pcm_ptr, _p(off), _p(ln), off.size, scores_ptr, features_ptr, q_ptr, stream))
 
     def live_streams(self, n_streams, slice_samples=None):
         """a live session of n_streams streams in continuous mode (kws_live_*): see LiveStreams"""

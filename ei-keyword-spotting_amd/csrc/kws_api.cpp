@@ -60,6 +60,7 @@ void kws_destroy(kws_handle *h)
     if (h->s_cep) (void)hipFree(h->s_cep);
     if (h->scan_release) h->scan_release(h);
     if (h->slide_release) h->slide_release(h);
+    if (h->ragged_release) h->ragged_release(h);
     for (hipEvent_t ev : h->gen_tune.ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &g : h->g_sets) for (void *p : { (void *)g.ws, (void *)g.mfcc, (void *)g.feat }) if (p) (void)hipFree(p);
     for (int k = 0; k < 2; ++k) {

@@ -249,6 +249,9 @@ struct kws_handle {
     // kws_slide.cpp: the same for kws_slide_recordings_device
     struct KwsSlideScratch *slide = nullptr;
     void (*slide_release)(kws_handle *) = nullptr;
+    // kws_ragged.cpp: the same for kws_run_classifier_ragged_device (descriptor table, pad maps of every row count, staging buffer)
+    struct KwsRaggedScratch *ragged = nullptr;
+    void (*ragged_release)(kws_handle *) = nullptr;
     size_t flags_cap = 0, cep_cap = 0;
 
     template <typename T> EI_IMPULSE_ERROR upload(const std::vector<T> &v, const T **out)

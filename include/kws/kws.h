@@ -348,6 +348,53 @@ EI_IMPULSE_ERROR kws_bank_cmvn_inference_batch_device(kws_bank *b, const float *
 EI_IMPULSE_ERROR kws_bank_slide_recordings_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
                                                   size_t hop_samples, int flags, float *const *scores, float *features, void *stream);
 
+/* ---- clips of their own lengths: run_classifier() for B clips, each as long as it is, in one call -----------------------------------
+ * run_classifier() accepts a window of any length that yields 1 .. kws_frame_count(h) frames (the shipped impulse: 640 .. 16 319 samples)
+ * and classifies it from the frames that fit: they are normalised among themselves, x[-1] is the last sample of THAT window, and the
+ * rest of the network's input stays at the zeros of the reference's calloc'd matrix.  kws_run_classifier_ragged_device does that for a
+ * batch of isolated utterances -- speech-commands style files, the segments a VAD cuts out -- without padding them (padding changes the
+ * window the model sees: another wrap sample, other cmvnw statistics).  Clip i is lengths[i] samples at pcm + offsets[i].
+ * Parity contract.  Row i of `scores` is what run_classifier() returns for a signal_t of total_length = lengths[i] over those samples.
+ * Row i of `features` ([feature_count]) holds extract_mfcc_features / extract_mfe_features of the frames that fit in its first
+ * frames x columns values (kws_window_frame_count(h, lengths[i]) frames; columns: cepstra, or mel filters for an MFE block), and every
+ * later value of the row is +0.0f -- the call WRITES them, the caller's buffer is not assumed clean.  Row i of `q_in` is run_inference's
+ * quantisation of that whole matrix.  A clip with lengths[i] == kws_clip_samples(h) gets exactly the bits
+ * kws_run_classifier_batch_device gives it in KWS_MODE_EXACT.  int8 graphs: bit-exact with the reference; float32 graphs: features and
+ * logits bit-exact, scores within 1e-6 (the bars of the other entry points).
+ *   pcm       DEVICE pointer, int16
+ *   offsets   HOST array [B], in samples from pcm: any value, no alignment needed; clips may overlap or repeat
+ *   lengths   HOST array [B], in samples
+ *   scores    [B][label_count] float, device, or NULL: the network is skipped (a ragged extract_mfcc_features / extract_mfe_features)
+ *   features  [B][feature_count] float, device, optional (NULL)
+ *   q_in      [B][feature_count] int8, device, optional (NULL); KWS_ERROR_UNSUPPORTED_MODEL for a float32 graph, as in the batch call
+ * The call reads no sample outside [offsets[i], offsets[i] + lengths[i]) for any i: what lies between and around the clips does not
+ * matter and need not be mapped.
+ * Lengths.  Every clip must have 1 .. kws_frame_count(h) frames.  The lengths are checked on the host before anything is enqueued: one bad
+ * clip refuses the whole call with KWS_ERROR_BAD_ARGUMENT, kws_last_error names the first offending index and its length, nothing is
+ * written.  Longer audio is kws_slide_recordings_device's job (one window every hop); this call does not cut recordings.  Also
+ * KWS_ERROR_BAD_ARGUMENT: scores, features and q_in all NULL; B >= 2^31; NULL pcm / offsets / lengths with B > 0.  B == 0: EI_IMPULSE_OK,
+ * nothing written.
+ * Mode.  The call always runs the exact kernels, like bank calls: it neither reads nor changes kws_set_mode state, the fast counters
+ * (kws_fast_fallback_count / kws_fast_exact_count) or the logits tap, and writes no tap.
+ * Models.  Everything the batch call serves: int8 and float32 graphs, MFCC and MFE blocks, tuned and general-shape DSP plans.
+ *   MFCC block on the tuned shapes (fft 256, 32 or 40 filters): the whole DSP block of the batch is ONE launch, however many distinct
+ *     lengths it holds (the ragged form of kws_mfcc8_kernel: frame count, length, base address and pad map per clip).  A clip whose first
+ *     sample lies on a 16-byte boundary (pcm 16-byte aligned, offset a multiple of 8 samples) is read in place, no copy of its audio is
+ *     made; the others are first copied into aligned slots of a staging buffer by one more launch.
+ *   MFE blocks and general-shape plans take a grouped route: the clips are bucketed by frame count on the host and every bucket goes
+ *     through the fixed-length launches with the plan of its frame count (gathered into slots of one stride, scattered into the
+ *     full-stride rows): a handful of launches per DISTINCT frame count in the batch.
+ * Device memory, ordering, streams.  As for the other calls on a handle (top of this file): a call on another stream than the handle's
+ * previous call first waits for it.  Scratch is on the handle, grown on demand; growing synchronises the device.  The call keeps: the
+ * per-clip descriptor table (16 bytes per clip; as much again for the clips that are staged or gathered), the pad maps of all row counts
+ * (uploaded once per handle), the handle's batch scratch for B clips where the network's input is not handed out, and a staging buffer
+ * only for the clips that need one -- tuned shapes: the clips not on a 16-byte boundary, in slots of the longest of them; grouped route:
+ * the largest bucket, plus its packed feature rows. */
+/* frames the reference's framing yields for a window of n_samples (processing.hpp:194-284); 0: none fits (or h is NULL) */
+int kws_window_frame_count(const kws_handle *h, size_t n_samples);
+EI_IMPULSE_ERROR kws_run_classifier_ragged_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths,
+                                                  size_t B, float *scores, float *features, int8_t *q_in, void *stream);
+
 /* ---- live continuous mode: audio of any length pushed to any subset of S streams, state in HBM between calls ----------------------
  * A session holds S streams at one slicing.  A push hands any number of new samples (0 included) to any subset of the streams, each its
  * own length, and returns every window those samples complete; finishing a stream flushes what waited for its look-ahead sample and the
