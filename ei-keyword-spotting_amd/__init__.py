@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = [
     "kws_bank_cmvn_inference_batch_device", "kws_bank_slide_recordings_device",
     "kws_window_frame_count", "kws_run_classifier_ragged_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
+    "kws_slide_live_create", "kws_slide_live_destroy", "kws_slide_live_path", "kws_slide_live_reset", "kws_slide_live_window_count",
+    "kws_slide_live_push_device",
     "kws_extract_mfe_batch_device", "kws_set_mode", "kws_get_mode", "kws_fast_is_fused", "kws_fast_fallback_count", "kws_fast_exact_count", "kws_fast_guard",
     "kws_set_logits_tap", "kws_fast_gain", "kws_fast_tolerance_info",
     "kws_comm_unique_id", "kws_comm_create", "kws_comm_world_size", "kws_comm_rank", "kws_comm_ranks_seen", "kws_comm_rccl_version", "kws_comm_wait", "kws_allgather_scores", "kws_comm_destroy",
@@ -197,6 +199,14 @@ def lib():
             L.kws_live_reset.argtypes = [vp, vp, sz]
             L.kws_live_window_count.argtypes = [vp, sz, sz, C.c_int, C.POINTER(sz)]
             L.kws_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "kws_slide_live_push_device"):
+            L.kws_slide_live_create.argtypes = [vp, sz, sz, i32, C.POINTER(vp)]
+            L.kws_slide_live_destroy.argtypes = [vp]
+            L.kws_slide_live_destroy.restype = None
+            L.kws_slide_live_path.argtypes = [vp]
+            L.kws_slide_live_reset.argtypes = [vp, vp, sz]
+            L.kws_slide_live_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
+            L.kws_slide_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         L.kws_device_malloc.argtypes = [C.POINTER(vp), sz]
         L.kws_device_free.argtypes = [vp]
         L.kws_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -437,6 +447,10 @@ class Model:
         """a live session of n_streams streams in continuous mode (kws_live_*): see LiveStreams"""
         return LiveStreams(self, n_streams, slice_samples)
 
+    def slide_streams(self, n_streams, hop_samples, flags=SLIDE_AUTO):
+        """a live session of n_streams streams of one-shot windows, one every hop_samples (kws_slide_live_*): see SlideStreams"""
+        return SlideStreams(self, n_streams, hop_samples, flags)
+
 
 class Bank:
     """K loaded models with an identical DSP block (kws_bank; the contract is in include/kws/kws.h): a call computes the front end once and
@@ -556,6 +570,57 @@ class LiveStreams:
         if getattr(self, "lv", None):
             self.L.kws_live_destroy(self.lv)
             self.lv = None
+
+
+class SlideStreams:
+    """S live streams of one-shot windows, state in HBM between pushes (kws_slide_live; the parity contract is in include/kws/kws.h): each
+    push hands any number of new samples to any subset of the streams and returns run_classifier() of every window -- one every
+    hop_samples -- those samples complete: the rows Model.slide_recordings_device returns for the stream's audio as one recording."""
+
+    def __init__(self, model, n_streams, hop_samples, flags=SLIDE_AUTO):
+        self.model = model
+        self.L = model.L
+        self.hop_samples = hop_samples
+        sl = C.c_void_p()
+        _check(self.L.kws_slide_live_create(model.h, n_streams, hop_samples, flags, C.byref(sl)))
+        self.sl = sl
+        self.n_streams = n_streams
+
+    @property
+    def path(self):
+        """SLIDE_DIRECT or SLIDE_SHARED: what the session's pushes run"""
+        return int(self.L.kws_slide_live_path(self.sl))
+
+    def window_count(self, stream, n_new):
+        """windows a push of n_new samples to `stream` would return now"""
+        n = C.c_size_t()
+        _check(self.L.kws_slide_live_window_count(self.sl, stream, n_new, C.byref(n)))
+        return n.value
+
+    def push_device(self, pcm_ptr, streams, offsets, lengths, scores_ptr, features_ptr=None, stream=None):
+        """entry i: lengths[i] int16 samples at pcm_ptr + offsets[i] (device) to stream streams[i].  Writes the entries' windows one after the
+        other to scores [sum][labels] (and features [sum][n_features]), device; returns n_windows per entry (numpy uint64).
+        streams / offsets / lengths: host sequences."""
+        st = np.ascontiguousarray(streams, np.uint64)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert st.shape == off.shape == ln.shape and st.ndim == 1
+        nw = np.zeros(st.size, np.uint64)
+        _check(self.L.kws_slide_live_push_device(self.sl, st.size, _p(st), pcm_ptr, _p(off), _p(ln), scores_ptr, features_ptr, _p(nw), stream))
+        return nw
+
+    def reset(self, streams=None):
+        """streams (host sequence; None: all) back to fresh state"""
+        if streams is None:
+            _check(self.L.kws_slide_live_reset(self.sl, None, 0))
+            return
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_slide_live_reset(self.sl, _p(st), st.size))
+
+    def close(self):
+        if getattr(self, "sl", None):
+            self.L.kws_slide_live_destroy(self.sl)
+            self.sl = None
 
 
 class Comm:

@@ -322,6 +322,20 @@ KWS_INTERNAL EI_IMPULSE_ERROR cmvn_nn_device(kws_handle *h, const float *mfcc, s
                                 int8_t *tap_pooled, int8_t *tap_fc, int8_t *tap_out, hipStream_t s, int ring_rows = 0, int ring_head = 0);
 }
 
+// The finishing step of one chunk of gathered one-shot windows (win [n][feature_count] cepstra before cmvnw, device; h->mu held): cmvnw + the
+// handle's network, through the fast forms behind the guard when `fast`; scores [n][labels] and the optional features [n][feature_count] are
+// written in place.  Such calls write no logits tap (out of the tap's [B][labels] shape): it is set aside for the step.  (kws_slide_live.cpp)
+static inline EI_IMPULSE_ERROR kws_finish_window_chunk(kws_handle *h, const float *win, size_t n, float *scores, float *features, bool fast, hipStream_t s)
+{
+    struct TapAside {
+        kws_handle *h; float *t;
+        ~TapAside() { h->tap_logits = t; }
+    } tap_aside{ h, h->tap_logits };
+    h->tap_logits = nullptr;
+    if (fast) return cmvn_nn_fast_device(h, win, n, scores, s, 0, 0, features);
+    return cmvn_nn_device(h, win, n, features, nullptr, scores, nullptr, nullptr, nullptr, s);
+}
+
 // kws_scan.cpp: the stream API's step rules (kws_streams_step_device) at one slicing, replayed on the host until they repeat; shared by the
 // recording scan and the live sessions (kws_live.cpp).  scan_layout refuses a slicing with the code the stream API would refuse it with.
 struct ScanLayout {

@@ -437,6 +437,66 @@ EI_IMPULSE_ERROR kws_live_push_device(kws_live *lv, size_t n, const size_t *stre
                                       const size_t *lengths, const int *finish, float *scores, float *raw_scores, size_t *n_windows,
                                       void *stream);
 
+/* ---- live one-shot windows: audio of any length pushed to any subset of S streams, every hop's run_classifier() result ----------------
+ * A session holds S streams at one hop.  A push hands any number of new samples (0 included) to any subset of the streams, each its own
+ * length, and returns every one-shot window those samples complete: the slide (kws_slide_recordings_device) cut into pushes, with the
+ * features the models were trained on -- not continuous mode's (kws_live_*).
+ * Parity contract.  Let clip = kws_clip_samples(h); number a stream's samples from its start (its creation or last reset).  Window w is
+ * samples [w hop_samples, w hop_samples + clip) and is complete once sample w hop_samples + clip - 1 has arrived: a one-shot window has no
+ * look-ahead sample, so nothing is held back and there is no finish flag.  With windows(n) = n < clip ? 0 : (n - clip) / hop_samples + 1
+ * (kws_slide_window_count), a push of lengths[i] samples to stream streams[i], which had n0 samples, returns the windows windows(n0) up to,
+ * not including, windows(n0 + lengths[i]); entry i's windows are rows [sum_{j<i} n_windows[j], + n_windows[i]) of `scores` and of the
+ * optional `features`.  Take everything pushed to a stream since its start as one recording: the rows the pushes return for that stream, in
+ * order, are exactly the rows kws_slide_recordings_device returns for that recording at the same hop_samples -- scores and features, in the
+ * handle's mode at push time, on whichever path the session runs.  In KWS_MODE_EXACT they are bit-identical to the slide's and so, through
+ * the slide's contract, to kws_run_classifier_batch_device on the window cut out as a clip and to the reference's run_classifier().  In
+ * KWS_MODE_FAST they are bit-identical to the fast slide's (every tier of the fast finishing step works per window), and
+ * kws_fast_fallback_count / kws_fast_exact_count describe the last push (0 for a push without windows).  Pushes write no logits tap.
+ * Streams not named in a push keep their state.  With hop_samples > clip the samples between two windows are dropped as they arrive.
+ *   kws_slide_live_create   S streams (0 < S < 2^30) at hop_samples; flags are the slide's.  Models: those of the slide (int8 and float32
+ *                     graphs, MFCC and MFE blocks, tuned and general-shape DSP plans).
+ *                     KWS_SLIDE_DIRECT serves any hop: every completed window is staged as a clip from the stream's carried samples and
+ *                     the pushed chunk, and its frame_count rows are computed for it.
+ *                     KWS_SLIDE_SHARED, the retained-row path, serves hop_samples % frame stride == 0 with hop_samples / frame stride <=
+ *                     frame_count - pre (pre = 1; 0 for an MFE block: no pre-emphasis): frame f >= pre of window w is the cepstral row of
+ *                     position w hop_samples / stride + f of the stream, so a push computes only the positions its completed windows need
+ *                     and no earlier push has computed, plus frame 0 of each completed window (its predecessor sample is the window's
+ *                     last); the stream keeps its last frame_count - pre rows between pushes.
+ *                     KWS_SLIDE_AUTO takes SHARED where it is served and computes fewer rows per window (hop_samples / stride + pre <
+ *                     frame_count), else DIRECT -- the slide's rule, by row count.  Hops that are no multiple of the frame stride run
+ *                     DIRECT (retained rows per phase: not in this version).  Both paths run the one-shot path's own spectral kernels
+ *                     and the same finishing launches: bit-identical to each other in either mode.
+ *   kws_slide_live_destroy  waits for the session's enqueued work, then frees it.  Destroy sessions before their handle.
+ *   kws_slide_live_path     KWS_SLIDE_DIRECT or KWS_SLIDE_SHARED: what the session's pushes run
+ *   kws_slide_live_reset    streams [n] (HOST; NULL: all): back to fresh state, as if just created.  Host only: no device work.
+ *   kws_slide_live_window_count  the windows a push of n_new samples to `stream` would return now (host only)
+ *   kws_slide_live_push_device   n entries; streams, offsets, lengths and n_windows are HOST arrays of n entries.  Entry i hands lengths[i]
+ *                     samples at pcm + offsets[i] (int16, device, any sample offset) to stream streams[i].  scores [.][label_count] float,
+ *                     device; features [.][feature_count] float, device, optional (NULL).  n_windows is computed on the host before
+ *                     anything is launched (the session keeps host copies of every stream's sample and computed-row counts); the call
+ *                     reads nothing back.
+ * KWS_ERROR_BAD_ARGUMENT, with no state changed and nothing written: S == 0 or S >= 2^30; hop_samples == 0 or beyond the slide's limit;
+ * unknown flags; KWS_SLIDE_SHARED at a hop the retained-row path does not serve; a stream named twice in one push, a stream index >= S;
+ * n > 0 with streams, lengths, n_windows or scores NULL; samples pushed with pcm or offsets NULL; more than 2^60 samples to one stream
+ * between starts.  A push that completes no window writes nothing to scores / features.  If a push fails past its argument checks, reset
+ * the streams it named.
+ * Device memory per stream, bounded whatever the audio length: the carried samples -- from the next incomplete window's start on, fewer
+ * than clip -- in a ring of clip int16 (32 000 B for the shipped models); on the shared path the last frame_count - pre cepstral rows
+ * (48 x 13 floats = 2 496 B, 48 x 40 floats = 7 680 B shipped).  On top, per session and grown on demand (growing synchronises the
+ * device), the slide's per-call scratch: at most 32 MiB of staged samples, 64 MiB (<= 32 768) of gathered windows, the cepstral rows one
+ * push computes and 72 B per entry; plus the handle's batch scratch for one chunk of windows.  A session keeps nothing in the handle's
+ * slide scratch: sessions at different hops and slide calls may interleave on one handle.  Ordering: a push counts as a call on the
+ * handle (see the top of this file); it waits for earlier work on `stream` before it uploads its per-entry tables, the rest is
+ * asynchronous. */
+typedef struct kws_slide_live kws_slide_live;
+EI_IMPULSE_ERROR kws_slide_live_create(kws_handle *h, size_t S, size_t hop_samples, int flags, kws_slide_live **out);
+void kws_slide_live_destroy(kws_slide_live *sl);
+int kws_slide_live_path(const kws_slide_live *sl);
+EI_IMPULSE_ERROR kws_slide_live_reset(kws_slide_live *sl, const size_t *streams, size_t n);
+EI_IMPULSE_ERROR kws_slide_live_window_count(const kws_slide_live *sl, size_t stream, size_t n_new, size_t *n_windows);
+EI_IMPULSE_ERROR kws_slide_live_push_device(kws_slide_live *sl, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets,
+                                            const size_t *lengths, float *scores, float *features, size_t *n_windows, void *stream);
+
 /* ---- multi-GPU: clips shard contiguously over the GPUs of one node (rank r owns clips [r*B, (r+1)*B)), tables are
  * replicated, nothing is exchanged inside the pipeline; the one collective is the all-gather of the per-clip scores over xGMI.
  * It goes through RCCL's C API (librccl is opened on first use: single-GPU applications do not need it).  One process per GPU:
