@@ -242,9 +242,9 @@ struct kws_handle {
                                   // for both -- the features are then the ones kws_extract_mfcc_batch_device returns -- and the fused launch's goes here
     float *tap_logits = nullptr;  // kws_set_logits_tap: FULLY_CONNECTED outputs of the batch calls' clips (float32 graphs), device [B][labels]
     float *s_cep = nullptr;       // [B][n_features] exact cepstra of the first tier's clips (indexed by clip)
-    // kws_scan.cpp: the bounded scratch of kws_scan_recordings_device and the cepstral rows of its last call; kws_destroy frees it through
-    // scan_release (set with it)
-    struct KwsScanScratch *scan = nullptr;
+    // kws_scan.cpp: the bounded scratch of kws_scan_recordings_device and the cepstral rows of its last call (kws_windows.h); kws_destroy frees
+    // it through scan_release (set with it)
+    struct KwsWindowScratch *scan = nullptr;
     void (*scan_release)(kws_handle *) = nullptr;
     // kws_slide.cpp: the same for kws_slide_recordings_device
     struct KwsSlideScratch *slide = nullptr;
@@ -322,20 +322,6 @@ KWS_INTERNAL EI_IMPULSE_ERROR cmvn_nn_device(kws_handle *h, const float *mfcc, s
                                 int8_t *tap_pooled, int8_t *tap_fc, int8_t *tap_out, hipStream_t s, int ring_rows = 0, int ring_head = 0);
 }
 
-// The finishing step of one chunk of gathered one-shot windows (win [n][feature_count] cepstra before cmvnw, device; h->mu held): cmvnw + the
-// handle's network, through the fast forms behind the guard when `fast`; scores [n][labels] and the optional features [n][feature_count] are
-// written in place.  Such calls write no logits tap (out of the tap's [B][labels] shape): it is set aside for the step.  (kws_slide_live.cpp)
-static inline EI_IMPULSE_ERROR kws_finish_window_chunk(kws_handle *h, const float *win, size_t n, float *scores, float *features, bool fast, hipStream_t s)
-{
-    struct TapAside {
-        kws_handle *h; float *t;
-        ~TapAside() { h->tap_logits = t; }
-    } tap_aside{ h, h->tap_logits };
-    h->tap_logits = nullptr;
-    if (fast) return cmvn_nn_fast_device(h, win, n, scores, s, 0, 0, features);
-    return cmvn_nn_device(h, win, n, features, nullptr, scores, nullptr, nullptr, nullptr, s);
-}
-
 // kws_scan.cpp: the stream API's step rules (kws_streams_step_device) at one slicing, replayed on the host until they repeat; shared by the
 // recording scan and the live sessions (kws_live.cpp).  scan_layout refuses a slicing with the code the stream API would refuse it with.
 struct ScanLayout {
@@ -355,7 +341,7 @@ KWS_INTERNAL EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, c
                                             int flags, int take_lock, kws_slide_finish_fn finish, void *ctx, hipStream_t s);
 
 // grows the device buffer *p to at least n elements (synchronising the device first: the old buffer may still be in use by enqueued work);
-// the per-call scratch of kws_scan.cpp and kws_live.cpp
+// the per-call scratch of the window pipelines (kws_windows.h), of kws_bank.cpp and of kws_ragged.cpp
 template <typename T>
 static EI_IMPULSE_ERROR grow_buffer(T **p, size_t *cap, size_t n)
 {

@@ -17,7 +17,9 @@
 //   4. kws_live_maf_kernel: the moving average per (entry, label), resumed from the stored filter.
 // Finish and reset touch no device memory: a stream with no window before a push starts from fresh state, and its carry and rows are only
 // read in the ranges its host counts say were written.
+// Scratch, table upload, finishing step, fast counters and the session skeleton (mirrors, push checks, reset, destroy): kws_windows.h.
 #include "kws_internal.h"
+#include "kws_windows.h"
 
 #include "../../include/kws/ei_compat.h"
 
@@ -28,32 +30,16 @@ int kws_launch_live_gather(const float *first_rows, const float *slot_rows, cons
 int kws_launch_live_commit(const int16_t *pcm, const float *first_rows, const float *slot_rows, const long long *meta, int n_act, int slice, int cap, int nf0,
                            int nf1, int keep, int ncols, int16_t *carry, float *kept, hipStream_t stream);
 int kws_launch_live_maf(const float *raw, float *scores, const long long *meta, int n_act, int labels, int k_full, float *maf, hipStream_t stream);
-int kws_launch_scan_count(int *flags, int *flags2, int *acc, int finish, hipStream_t stream);      // kws_scan_kernels.hip
 
 static const int kLiveTaps = EI_CLASSIFIER_SLICES_PER_MODEL_WINDOW >> 1;
-// bounded scratch of one push: the scan's bounds (include/kws/kws.h)
-static const size_t kLiveStageBytes = (size_t)32 << 20;
-static const size_t kLiveWindowBytes = (size_t)64 << 20;
-static const size_t kLiveMaxItems = 16384, kLiveMaxWindows = 32768;
-static const unsigned long long kLiveMaxSamples = 1ull << 60;           // samples of one stream between starts (positions stay in long long)
 
-struct kws_live {
-    kws_handle *h = nullptr;
-    size_t S = 0, slice = 0;
+// (KwsLiveSession, kws_windows.h: the handle, the streams' sample counts, carry [S][cap], kept [S][max(keep, 1)][ncols], the per-push scratch)
+struct kws_live : KwsLiveSession {
+    std::vector<unsigned long long> &k = m2;       // per stream: finished slices
+    size_t slice = 0;
     ScanLayout L;
     int cap = 0, keep = 0;                 // carry ring (samples), retained-row ring (rows)
-    std::vector<unsigned long long> n;     // per stream: samples since its start
-    std::vector<unsigned long long> k;     // per stream: finished slices
-    // state in HBM
-    int16_t *carry = nullptr;              // [S][cap]
-    float *kept = nullptr;                 // [S][max(keep, 1)][ncols]
-    float *maf = nullptr;                  // [S][labels][taps + 1]
-    // per-push scratch, grown on demand
-    int16_t *stage = nullptr;
-    float *wrap = nullptr, *win = nullptr, *rows = nullptr;
-    long long *meta = nullptr;
-    int *acc = nullptr;
-    size_t stage_cap = 0, wrap_cap = 0, win_cap = 0, rows_cap = 0, meta_cap = 0, acc_cap = 0;
+    float *maf = nullptr;                  // state in HBM: [S][labels][taps + 1]
 
     // slices a stream of n1 samples has finished: slice 0 once complete, slice k >= 1 once its look-ahead sample has arrived; all complete ones at finish
     size_t finished(unsigned long long n1, bool fin) const
@@ -62,15 +48,13 @@ struct kws_live {
         const unsigned long long g = (unsigned long long)L.grow;
         return std::max<size_t>(1, n1 >= g ? (size_t)((n1 - g) / slice) : 0);
     }
+    void free_device()
+    {
+        if (maf) (void)hipFree(maf);
+        maf = nullptr;
+        KwsLiveSession::free_device();
+    }
 };
-
-static void live_free(kws_live *lv)
-{
-    for (void *p : { (void *)lv->carry, (void *)lv->kept, (void *)lv->maf, (void *)lv->stage, (void *)lv->wrap, (void *)lv->win, (void *)lv->rows,
-                     (void *)lv->meta, (void *)lv->acc })
-        if (p) (void)hipFree(p);
-    delete lv;
-}
 
 extern "C" {
 #pragma GCC visibility push(default)
@@ -84,11 +68,10 @@ EI_IMPULSE_ERROR kws_live_create(kws_handle *h, size_t S, size_t slice_samples, 
     if (e) return e;
     HIP_TRY(hipSetDevice(h->device));
     kws_live *lv = new kws_live();
-    lv->h = h; lv->S = S; lv->slice = slice_samples; lv->L = L;
+    lv->open(h, S);
+    lv->slice = slice_samples; lv->L = L;
     lv->cap = (int)slice_samples + L.grow;
     lv->keep = L.ring_rows - L.nf1;
-    lv->n.assign(S, 0);
-    lv->k.assign(S, 0);
     const size_t ncols = (size_t)h->dsp.n_cepstral, C = h->model.labels.size();
     const size_t carry_b = S * lv->cap * sizeof(int16_t), kept_b = S * std::max(lv->keep, 1) * ncols * sizeof(float);
     const size_t maf_b = S * C * (kLiveTaps + 1) * sizeof(float);
@@ -97,75 +80,41 @@ EI_IMPULSE_ERROR kws_live_create(kws_handle *h, size_t S, size_t slice_samples, 
     // (nothing reads these before a push has written it; cleared so that no stale value can ever reach a result)
     ok = ok && hipMemset(lv->carry, 0, carry_b) == hipSuccess && hipMemset(lv->kept, 0, kept_b) == hipSuccess && hipMemset(lv->maf, 0, maf_b) == hipSuccess;
     if (!ok) {
-        live_free(lv);
+        lv->free_device();
+        delete lv;
         return fail(KWS_ERROR_HIP, "live session allocation failed");
     }
     *out = lv;
     return EI_IMPULSE_OK;
 }
 
-void kws_live_destroy(kws_live *lv)
-{
-    if (!lv) return;
-    kws_handle *h = lv->h;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        (void)hipSetDevice(h->device);
-        // every push brackets its work with ScratchUse: the handle's event marks the end of the latest call, this session's last push included
-        if (h->scratch_used && h->scratch_ev) (void)hipEventSynchronize(h->scratch_ev);
-        live_free(lv);
-    }
-}
+void kws_live_destroy(kws_live *lv) { kws_session_destroy(lv); }
 
 EI_IMPULSE_ERROR kws_live_reset(kws_live *lv, const size_t *streams, size_t n)
 {
-    if (!lv || (n > 0 && !streams)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> lk(lv->h->mu);
-    if (!streams) {
-        std::fill(lv->n.begin(), lv->n.end(), 0);
-        std::fill(lv->k.begin(), lv->k.end(), 0);
-        return EI_IMPULSE_OK;
-    }
-    for (size_t i = 0; i < n; ++i)
-        if (streams[i] >= lv->S) return fail(KWS_ERROR_BAD_ARGUMENT, "stream %zu of %zu", streams[i], lv->S);
-    for (size_t i = 0; i < n; ++i) lv->n[streams[i]] = lv->k[streams[i]] = 0;
-    return EI_IMPULSE_OK;
+    if (!lv) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    return lv->reset(streams, n);
 }
 
 EI_IMPULSE_ERROR kws_live_window_count(const kws_live *lv, size_t stream, size_t n_new, int finish, size_t *n_windows)
 {
-    if (!lv || !n_windows) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    *n_windows = 0;
-    if (stream >= lv->S) return fail(KWS_ERROR_BAD_ARGUMENT, "stream %zu of %zu", stream, lv->S);
-    std::lock_guard<std::mutex> lk(lv->h->mu);
-    const unsigned long long n0 = lv->n[stream];
-    if (n_new > kLiveMaxSamples - n0) return fail(KWS_ERROR_BAD_ARGUMENT, "stream %zu: too many samples", stream);
-    *n_windows = lv->L.windows(lv->finished(n0 + n_new, finish != 0)) - lv->L.windows(lv->k[stream]);
-    return EI_IMPULSE_OK;
+    if (!lv) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    return lv->window_count(stream, n_new, n_windows, [&](unsigned long long, unsigned long long n1) {
+        return lv->L.windows(lv->finished(n1, finish != 0)) - lv->L.windows(lv->k[stream]);
+    });
 }
 
 EI_IMPULSE_ERROR kws_live_push_device(kws_live *lv, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets, const size_t *lengths,
                                       const int *finish, float *scores, float *raw_scores, size_t *n_windows, void *stream)
 {
     if (!lv) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (n > 0 && (!streams || !lengths || !n_windows || !scores)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (n > lv->S) return fail(KWS_ERROR_BAD_ARGUMENT, "%zu entries for %zu streams", n, lv->S);
     kws_handle *h = lv->h;
     const ScanLayout &L = lv->L;
     const size_t slice = lv->slice;
     std::lock_guard<std::mutex> lk(h->mu);
     // argument checks and every count of the push, before any state changes
-    std::vector<char> named(lv->S, 0);
-    bool any_samples = false;
-    for (size_t i = 0; i < n; ++i) {
-        const size_t s = streams[i];
-        if (s >= lv->S) return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: stream %zu of %zu", i, s, lv->S);
-        if (named[s]) return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: stream %zu named twice", i, s);
-        named[s] = 1;
-        if (lengths[i] > kLiveMaxSamples - lv->n[s]) return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: too many samples", i);
-        any_samples = any_samples || lengths[i] > 0;
-    }
-    if (any_samples && (!pcm || !offsets)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    EI_IMPULSE_ERROR e = lv->check_push(n, streams, pcm, offsets, lengths, n_windows, scores);
+    if (e) return e;
     // the entries with device work (A of them): windows, or a continuing stream's new samples
     std::vector<long long> off, n0, len, sid, k0, k1, fin, fbase(1, 0), ibase(1, 0), wbase(1, 0);
     for (size_t i = 0; i < n; ++i) {
@@ -191,8 +140,7 @@ EI_IMPULSE_ERROR kws_live_push_device(kws_live *lv, size_t n, const size_t *stre
     const size_t F = m.nn_input_frame_size, C = m.labels.size();
     const int ncols = h->dsp.n_cepstral, rows = (int)(F / (size_t)ncols);
     if (n_win * C > (size_t)1 << 40) return fail(KWS_ERROR_BAD_ARGUMENT, "too many windows");
-    const bool fast = h->mode == KWS_MODE_FAST && h->fast_plain_ok;
-    const bool count = fast && m.dsp.block != DSP_BLOCK_MFE;          // the MFE block's fast form is its exact one: no guard, no counts
+    const bool count = KwsChunkCounts::wanted(h);
     auto commit_mirrors = [&]() {
         for (size_t i = 0; i < n; ++i) {
             const size_t s = streams[i];
@@ -207,39 +155,22 @@ EI_IMPULSE_ERROR kws_live_push_device(kws_live *lv, size_t n, const size_t *stre
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    EI_IMPULSE_ERROR e;
-    const size_t item_cap = std::max<size_t>(1, std::min(kLiveMaxItems, kLiveStageBytes / (slice * sizeof(int16_t))));
-    const size_t win_chunk = std::min(std::max<size_t>(1, std::min(kLiveMaxWindows, kLiveWindowBytes / (F * sizeof(float)))), std::max<size_t>(n_win, 1));
+    KwsWindowScratch &S = lv->scratch;
+    const size_t item_cap = kws_window_item_cap(slice), win_chunk = kws_window_chunk(F, n_win);
     const size_t first_floats = n_first * L.nf0 * ncols, rows_floats = std::max<size_t>(first_floats + n_slots * L.nf1 * ncols, 1);
-    const size_t meta_n = 7 * (size_t)A + 3 * ((size_t)A + 1);
-    if ((e = grow_buffer(&lv->stage, &lv->stage_cap, item_cap * slice)) || (e = grow_buffer(&lv->wrap, &lv->wrap_cap, item_cap)) ||
-        (e = grow_buffer(&lv->win, &lv->win_cap, win_chunk * F)) || (e = grow_buffer(&lv->rows, &lv->rows_cap, rows_floats)) ||
-        (e = grow_buffer(&lv->meta, &lv->meta_cap, meta_n)) || (e = grow_buffer(&lv->acc, &lv->acc_cap, 1)) || (e = ensure_scratch(h, win_chunk)))
-        return e;
-    // pushes write no logits tap (out of the tap's [B][labels] shape): the tap is set aside for the call
-    struct TapAside {
-        kws_handle *h; float *t;
-        ~TapAside() { h->tap_logits = t; }
-    } tap_aside{ h, h->tap_logits };
-    h->tap_logits = nullptr;
+    if ((e = S.reserve(h, item_cap * slice, item_cap, win_chunk * F, rows_floats, 7 * (size_t)A + 3 * ((size_t)A + 1), win_chunk))) return e;
     ScratchUse use(h, st);
     if (count && n_win == 0) {
-        // kws_fast_fallback_count / kws_fast_exact_count describe the last push: none of its windows was handed back
-        HIP_TRY(hipMemsetAsync(h->d_flags, 0, sizeof(int), st));
-        HIP_TRY(hipMemsetAsync(h->d_flags2, 0, sizeof(int), st));
+        if ((e = KwsChunkCounts::none(h, st))) return e;
         if (A == 0) {
             commit_mirrors();
             return EI_IMPULSE_OK;
         }
     }
-    // per-entry tables (kws_live_kernels.hip KwsLiveMeta).  The host copy is complete before the call goes on
-    std::vector<long long> meta;
-    meta.reserve(meta_n);
-    for (const std::vector<long long> *v : { &off, &n0, &len, &sid, &k0, &k1, &fin, &fbase, &ibase, &wbase }) meta.insert(meta.end(), v->begin(), v->end());
-    HIP_TRY(hipMemcpyAsync(lv->meta, meta.data(), meta.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    // per-entry tables (kws_live_kernels.hip KwsLiveMeta)
+    if ((e = kws_upload_tables(S, { &off, &n0, &len, &sid, &k0, &k1, &fin, &fbase, &ibase, &wbase }, st))) return e;
     const int sl = (int)slice;
-    float *first_rows = lv->rows, *slot_rows = lv->rows + first_floats;
+    float *first_rows = S.rows, *slot_rows = S.rows + first_floats;
     // 1. front end: the finished slices, assembled from carry and chunk, through the stream API's spectral launches
     KwsDspPlan P0 = h->dsp, P1 = h->dsp;
     P0.n_samples = P1.n_samples = sl;
@@ -247,39 +178,33 @@ EI_IMPULSE_ERROR kws_live_push_device(kws_live *lv, size_t n, const size_t *stre
     P1.n_frames = L.nf1;
     for (size_t g0 = 0; g0 < n_first; g0 += item_cap) {
         const int c = (int)std::min(item_cap, n_first - g0);
-        int rc = kws_launch_live_stage(pcm, lv->carry, lv->meta, A, (long long)g0, c, 1, sl, L.grow, lv->cap, lv->stage, lv->wrap, st);
+        int rc = kws_launch_live_stage(pcm, lv->carry, S.meta, A, (long long)g0, c, 1, sl, L.grow, lv->cap, S.stage, S.wrap, st);
         if (rc) return fail(KWS_ERROR_HIP, "live staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if ((e = spectral_device(h, P0, lv->stage, 0, c, first_rows + g0 * L.nf0 * ncols, nullptr, st, L.nf0 * ncols))) return e;
+        if ((e = spectral_device(h, P0, S.stage, 0, c, first_rows + g0 * L.nf0 * ncols, nullptr, st, L.nf0 * ncols))) return e;
     }
     for (size_t g0 = 0; g0 < n_slots; g0 += item_cap) {
         const int c = (int)std::min(item_cap, n_slots - g0);
-        int rc = kws_launch_live_stage(pcm, lv->carry, lv->meta, A, (long long)g0, c, 0, sl, L.grow, lv->cap, lv->stage, lv->wrap, st);
+        int rc = kws_launch_live_stage(pcm, lv->carry, S.meta, A, (long long)g0, c, 0, sl, L.grow, lv->cap, S.stage, S.wrap, st);
         if (rc) return fail(KWS_ERROR_HIP, "live staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if ((e = spectral_device(h, P1, lv->stage, 0, c, slot_rows + g0 * L.nf1 * ncols, lv->wrap, st, L.nf1 * ncols))) return e;
+        if ((e = spectral_device(h, P1, S.stage, 0, c, slot_rows + g0 * L.nf1 * ncols, S.wrap, st, L.nf1 * ncols))) return e;
     }
     // 2. windows in chunks through the stream API's cmvnw + network; raw scores land where the moving average reads them
     float *raw = raw_scores ? raw_scores : scores;
-    if (count && n_win) HIP_TRY(hipMemsetAsync(lv->acc, 0, sizeof(int), st));
+    KwsChunkCounts cnt(h);
+    if ((e = cnt.begin(S.acc, n_win, st))) return e;
     for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
         const int c = (int)std::min(win_chunk, n_win - g0);
-        int rc = kws_launch_live_gather(first_rows, slot_rows, lv->kept, lv->meta, A, (long long)g0, c, L.nf0, L.nf1, L.ring_rows, lv->keep, (int)L.k_full,
-                                        rows, ncols, lv->win, st);
+        int rc = kws_launch_live_gather(first_rows, slot_rows, lv->kept, S.meta, A, (long long)g0, c, L.nf0, L.nf1, L.ring_rows, lv->keep, (int)L.k_full,
+                                        rows, ncols, S.win, st);
         if (rc) return fail(KWS_ERROR_HIP, "live gather kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (fast) e = cmvn_nn_fast_device(h, lv->win, c, raw + g0 * C, st, 0, 0);
-        else e = cmvn_nn_device(h, lv->win, c, nullptr, nullptr, raw + g0 * C, nullptr, nullptr, nullptr, st);
-        if (e) return e;
-        if (count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, lv->acc, 0, st)))
-            return fail(KWS_ERROR_HIP, "live count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if ((e = kws_finish_window_chunk(h, S.win, c, raw + g0 * C, nullptr, cnt.fast, st)) || (e = cnt.chunk(st))) return e;
     }
-    if (count && n_win) {
-        int rc = kws_launch_scan_count(h->d_flags, h->d_flags2, lv->acc, 1, st);
-        if (rc) return fail(KWS_ERROR_HIP, "live count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
+    if ((e = cnt.end(st))) return e;
     // 3. the continuing streams' carry and retained rows (after every read of the old ones above)
-    int rc = kws_launch_live_commit(pcm, first_rows, slot_rows, lv->meta, A, sl, lv->cap, L.nf0, L.nf1, lv->keep, ncols, lv->carry, lv->kept, st);
+    int rc = kws_launch_live_commit(pcm, first_rows, slot_rows, S.meta, A, sl, lv->cap, L.nf0, L.nf1, lv->keep, ncols, lv->carry, lv->kept, st);
     if (rc) return fail(KWS_ERROR_HIP, "live commit kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     // 4. the moving average, resumed per (stream, label)
-    if (n_win && (rc = kws_launch_live_maf(raw, scores, lv->meta, A, (int)C, (int)L.k_full, lv->maf, st)))
+    if (n_win && (rc = kws_launch_live_maf(raw, scores, S.meta, A, (int)C, (int)L.k_full, lv->maf, st)))
         return fail(KWS_ERROR_HIP, "live moving-average kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     commit_mirrors();
     return EI_IMPULSE_OK;

@@ -12,6 +12,7 @@
 // Nothing here rounds except the int16 -> float of the wrap sample (kws_mfcc_kernel's product) and the moving average (kws_maf_kernel's
 // operations, in its order).
 #include "kws_device.h"
+#include "kws_window_kernels.h"
 
 #include "../../include/kws/ei_compat.h"
 
@@ -30,17 +31,6 @@ struct KwsLiveMeta {
     const long long *wbase;    // [n_act + 1] prefix: windows of the entries before
 };
 
-// index a of the last prefix entry <= g (prefix[0] = 0, ascending, n entries): the entry that owns item g, empty entries skipped
-__device__ __forceinline__ int live_owner(const long long *__restrict__ prefix, int n, long long g)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (prefix[mid] <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // first = 1: item g is the slice 0 of the entry with fbase[a] <= g < fbase[a + 1]; first = 0: item g is a slice k >= 1, counted over the
 // entries in order from each entry's first new slice max(k0, 1).  One block per item.
 __global__ void kws_live_stage_kernel(const int16_t *__restrict__ pcm, const int16_t *__restrict__ carry, KwsLiveMeta m, int n_act, long long item0,
@@ -49,7 +39,7 @@ __global__ void kws_live_stage_kernel(const int16_t *__restrict__ pcm, const int
     const long long *prefix = first ? m.fbase : m.ibase;
     for (int j = blockIdx.x; j < n_items; j += gridDim.x) {
         const long long g = item0 + j;
-        const int a = live_owner(prefix, n_act, g);
+        const int a = kws_prefix_owner(prefix, n_act, g);
         const long long k = first ? 0 : (m.k0[a] > 1 ? m.k0[a] : 1) + (g - prefix[a]);
         const long long n0 = m.n0[a], n1 = n0 + m.len[a];
         const long long base = m.off[a] - n0;                         // pcm[base + p]: stream position p >= n0, in the chunk
@@ -90,7 +80,7 @@ __global__ void kws_live_gather_kernel(const float *__restrict__ first_rows, con
     const int per = rows * ncols;
     for (int j = blockIdx.x; j < n_win; j += gridDim.x) {
         const long long g = win0 + j;
-        const int a = live_owner(m.wbase, n_act, g);
+        const int a = kws_prefix_owner(m.wbase, n_act, g);
         const long long w = (m.k0[a] > k_full ? m.k0[a] - k_full : 0) + (g - m.wbase[a]);
         float *dst = out + (size_t)j * per;
         for (int e = threadIdx.x; e < per; e += blockDim.x) {

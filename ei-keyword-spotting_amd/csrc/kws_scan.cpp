@@ -11,35 +11,21 @@
 //      cmvn_nn_fast_device in KWS_MODE_FAST), which write each window's raw scores in place;
 //   3. the moving average per (recording, label) over its windows in order (kws_scan_maf_kernel).
 // A = the recordings of the call that produce at least one window; the others need no work.
+// Scratch and its bounds, the table upload, the finishing step of a chunk and the fast counters: the window pipelines' core, kws_windows.h.
 #include "kws_internal.h"
+#include "kws_windows.h"
 
 int kws_launch_scan_stage(const int16_t *pcm, const long long *off, const long long *len, const long long *ibase, int n_rec, long long item0, int n_items,
                           int first, int slice, int grow, int16_t *stage, float *wrap, hipStream_t stream);
 int kws_launch_scan_gather(const float *first_rows, const float *slot_rows, const long long *wbase, const long long *ibase, int n_rec, long long win0,
                            int n_win, int nf0, int nf1, int ring_rows, int rows, int ncols, float *out, hipStream_t stream);
 int kws_launch_scan_maf(const float *raw, float *scores, const long long *wbase, int n_rec, int labels, hipStream_t stream);
-int kws_launch_scan_count(int *flags, int *flags2, int *acc, int finish, hipStream_t stream);
-
-// bounded scratch of one call (include/kws/kws.h states the bound): staged slices and gathered windows
-static const size_t kScanStageBytes = (size_t)32 << 20;
-static const size_t kScanWindowBytes = (size_t)64 << 20;
-static const size_t kScanMaxItems = 16384, kScanMaxWindows = 32768;
-
-struct KwsScanScratch {
-    int16_t *stage = nullptr;
-    float *wrap = nullptr, *win = nullptr, *rows = nullptr;
-    long long *meta = nullptr;
-    int *acc = nullptr;
-    size_t stage_cap = 0, wrap_cap = 0, win_cap = 0, rows_cap = 0, meta_cap = 0, acc_cap = 0;
-};
 
 static void scan_release(kws_handle *h)
 {
-    KwsScanScratch *s = h->scan;
-    if (!s) return;
-    for (void *p : { (void *)s->stage, (void *)s->wrap, (void *)s->win, (void *)s->rows, (void *)s->meta, (void *)s->acc })
-        if (p) (void)hipFree(p);
-    delete s;
+    if (!h->scan) return;
+    h->scan->release();
+    delete h->scan;
     h->scan = nullptr;
 }
 
@@ -121,31 +107,14 @@ EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, c
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->scan) { h->scan = new KwsScanScratch(); h->scan_release = scan_release; }
-    KwsScanScratch &S = *h->scan;
-    const size_t item_cap = std::max<size_t>(1, std::min(kScanMaxItems, kScanStageBytes / (slice_samples * sizeof(int16_t))));
-    const size_t win_chunk = std::min(std::max<size_t>(1, std::min(kScanMaxWindows, kScanWindowBytes / (F * sizeof(float)))), n_win);
+    if (!h->scan) { h->scan = new KwsWindowScratch(); h->scan_release = scan_release; }
+    KwsWindowScratch &S = *h->scan;
+    const size_t item_cap = kws_window_item_cap(slice_samples), win_chunk = kws_window_chunk(F, n_win);
     const size_t first_floats = (size_t)A * L.nf0 * ncols, rows_floats = first_floats + n_slots * L.nf1 * ncols;
-    if ((e = grow_buffer(&S.stage, &S.stage_cap, item_cap * slice_samples)) || (e = grow_buffer(&S.wrap, &S.wrap_cap, item_cap)) ||
-        (e = grow_buffer(&S.win, &S.win_cap, win_chunk * F)) || (e = grow_buffer(&S.rows, &S.rows_cap, rows_floats)) ||
-        (e = grow_buffer(&S.meta, &S.meta_cap, 4 * (size_t)A + 2)) || (e = grow_buffer(&S.acc, &S.acc_cap, 1)) || (e = ensure_scratch(h, win_chunk)))
-        return e;
-    // scan calls write no logits tap (out of the tap's [B][labels] shape): the tap is set aside for the call
-    struct TapAside {
-        kws_handle *h; float *t;
-        ~TapAside() { h->tap_logits = t; }
-    } tap_aside{ h, h->tap_logits };
-    h->tap_logits = nullptr;
+    if ((e = S.reserve(h, item_cap * slice_samples, item_cap, win_chunk * F, rows_floats, 4 * (size_t)A + 2, win_chunk))) return e;
     ScratchUse use(h, st);
-    // per-recording tables: off [A], len [A], wbase [A + 1], ibase [A + 1].  The host copy is complete before the call goes on
-    std::vector<long long> meta;
-    meta.reserve(4 * (size_t)A + 2);
-    meta.insert(meta.end(), off.begin(), off.end());
-    meta.insert(meta.end(), len.begin(), len.end());
-    meta.insert(meta.end(), wbase.begin(), wbase.end());
-    meta.insert(meta.end(), ibase.begin(), ibase.end());
-    HIP_TRY(hipMemcpyAsync(S.meta, meta.data(), meta.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    // per-recording tables: off [A], len [A], wbase [A + 1], ibase [A + 1]
+    if ((e = kws_upload_tables(S, { &off, &len, &wbase, &ibase }, st))) return e;
     const long long *d_off = S.meta, *d_len = S.meta + A, *d_wbase = S.meta + 2 * A, *d_ibase = S.meta + 3 * A + 1;
     const int slice = (int)slice_samples;
     float *first_rows = S.rows, *slot_rows = S.rows + first_floats;
@@ -168,23 +137,15 @@ EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, c
     }
     // 2. windows in chunks through the stream API's cmvnw + network; raw scores land where the moving average reads them
     float *raw = raw_scores ? raw_scores : scores;
-    const bool fast = h->mode == KWS_MODE_FAST && h->fast_plain_ok;
-    const bool count = fast && m.dsp.block != DSP_BLOCK_MFE;          // the MFE block's fast form is its exact one: no guard, no counts
-    if (count) HIP_TRY(hipMemsetAsync(S.acc, 0, sizeof(int), st));
+    KwsChunkCounts cnt(h);
+    if ((e = cnt.begin(S.acc, n_win, st))) return e;
     for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
         const int n = (int)std::min(win_chunk, n_win - g0);
         int rc = kws_launch_scan_gather(first_rows, slot_rows, d_wbase, d_ibase, A, (long long)g0, n, L.nf0, L.nf1, L.ring_rows, rows, ncols, S.win, st);
         if (rc) return fail(KWS_ERROR_HIP, "scan gather kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (fast) e = cmvn_nn_fast_device(h, S.win, n, raw + g0 * C, st, 0, 0);
-        else e = cmvn_nn_device(h, S.win, n, nullptr, nullptr, raw + g0 * C, nullptr, nullptr, nullptr, st);
-        if (e) return e;
-        if (count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 0, st)))
-            return fail(KWS_ERROR_HIP, "scan count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if ((e = kws_finish_window_chunk(h, S.win, n, raw + g0 * C, nullptr, cnt.fast, st)) || (e = cnt.chunk(st))) return e;
     }
-    if (count) {
-        int rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 1, st);
-        if (rc) return fail(KWS_ERROR_HIP, "scan count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
+    if ((e = cnt.end(st))) return e;
     // 3. the moving average, one fresh filter per recording
     int rc = kws_launch_scan_maf(raw, scores, d_wbase, A, (int)C, st);
     if (rc) return fail(KWS_ERROR_HIP, "scan moving-average kernel launch failed: %s", hipGetErrorString((hipError_t)rc));

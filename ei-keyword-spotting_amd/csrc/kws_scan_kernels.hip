@@ -6,21 +6,11 @@
 // The arithmetic of the front end and of the network is the existing kernels'; nothing here rounds except the int16 -> float of the wrap
 // sample (the same product as kws_mfcc_kernel's) and the moving average (kws_maf_kernel's operations, in its order).
 #include "kws_device.h"
+#include "kws_window_kernels.h"
 
 #include "../../include/kws/ei_compat.h"
 
 #define KWS_SCAN_TAPS (EI_CLASSIFIER_SLICES_PER_MODEL_WINDOW >> 1)
-
-// index a of the last prefix entry <= g (prefix[0] = 0, prefix ascending, n entries + the total at prefix[n])
-__device__ __forceinline__ int scan_owner(const long long *__restrict__ prefix, int n, long long g)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (prefix[mid] <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // first = 1: item j of the chunk is slice 0 of recording item0 + j; first = 0: item j is the (item0 + j)-th slice k >= 1 of the call, counted
 // over the recordings in order (ibase[a] = slices k >= 1 of the recordings before a).  One block per item.
@@ -34,7 +24,7 @@ __global__ void kws_scan_stage_kernel(const int16_t *__restrict__ pcm, const lon
         if (first) { a = (int)(item0 + j); k = 0; }
         else {
             const long long g = item0 + j;
-            a = scan_owner(ibase, n_rec, g);
+            a = kws_prefix_owner(ibase, n_rec, g);
             k = 1 + g - ibase[a];
         }
         const int16_t *src = pcm + off[a] + k * (long long)slice;
@@ -56,7 +46,7 @@ __global__ void kws_scan_gather_kernel(const float *__restrict__ first_rows, con
     const int per = rows * ncols;
     for (int j = blockIdx.x; j < n_win; j += gridDim.x) {
         const long long g = win0 + j;
-        const int a = scan_owner(wbase, n_rec, g);
+        const int a = kws_prefix_owner(wbase, n_rec, g);
         const long long w = g - wbase[a];
         float *dst = out + (size_t)j * per;
         for (int e = threadIdx.x; e < per; e += blockDim.x) {

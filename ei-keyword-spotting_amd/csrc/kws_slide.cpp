@@ -18,7 +18,9 @@
 //                 KWS_MODE_FAST) writes the chunk's scores and features in place; a bank (kws_bank.cpp) runs cmvnw once, then every member.
 // Where hop / g > frames per window - 1 the windows of a slot do not touch: each is a segment of its own (nothing is shared, and AUTO
 // takes the direct path).
+// Scratch and its bounds, the table upload, the finishing step, the fast counters and the geometry (SlideGeom): kws_windows.h.
 #include "kws_internal.h"
+#include "kws_windows.h"
 
 int kws_launch_slide_stage(const int16_t *pcm, const long long *src, const long long *end, const long long *ibase, int n_slots, long long item0,
                            int n_items, long long ips, long long seg_pitch, long long item_adv, int item_len, int has_wrap, int16_t *stage, float *wrap,
@@ -28,69 +30,23 @@ int kws_launch_slide_stage_first(const int16_t *pcm, const long long *off, const
 int kws_launch_slide_gather(const float *rows, const float *first, const long long *wbase, const long long *sbase, const long long *ibase, int n_rec,
                             long long win0, int n_win, long long phases, long long pitch, int nfi, int pre, int nf, int ncols, float *out,
                             hipStream_t stream);
-int kws_launch_scan_count(int *flags, int *flags2, int *acc, int finish, hipStream_t stream);      // kws_scan_kernels.hip
 
-// bounded scratch of one call (include/kws/kws.h states the bound): staged items and gathered windows, as the scan's
-static const size_t kSlideStageBytes = (size_t)32 << 20;
-static const size_t kSlideWindowBytes = (size_t)64 << 20;
-static const size_t kSlideMaxItems = 16384, kSlideMaxWindows = 32768;
-static const int kSlideItemFrames = 48;            // frames per item: six eight-frame passes of kws_mfcc8_kernel, whole chunks of the general kernels
 static const size_t kSlideMaxSamples = (size_t)1 << 56;      // per recording, offset and hop: beyond it the arguments are refused
 static const size_t kSlideMaxTotal = (size_t)1 << 40;        // windows x labels of one call, as the scan's
 
-struct KwsSlideScratch {
-    int16_t *stage = nullptr;
-    float *wrap = nullptr, *win = nullptr, *rows = nullptr, *first = nullptr;
-    long long *meta = nullptr;
-    int *acc = nullptr;
-    size_t stage_cap = 0, wrap_cap = 0, win_cap = 0, rows_cap = 0, first_cap = 0, meta_cap = 0, acc_cap = 0;
+struct KwsSlideScratch : KwsWindowScratch {
+    float *first = nullptr;        // frame 0 of a chunk's windows (shared path)
+    size_t first_cap = 0;
 };
 
 static void slide_release(kws_handle *h)
 {
     KwsSlideScratch *s = h->slide;
     if (!s) return;
-    for (void *p : { (void *)s->stage, (void *)s->wrap, (void *)s->win, (void *)s->rows, (void *)s->first, (void *)s->meta, (void *)s->acc })
-        if (p) (void)hipFree(p);
+    s->release();
+    if (s->first) (void)hipFree(s->first);
     delete s;
     h->slide = nullptr;
-}
-
-static size_t gcd_sz(size_t a, size_t b) { while (b) { const size_t t = a % b; a = b; b = t; } return a; }
-
-// what depends on the model and the hop alone
-struct SlideGeom {
-    size_t clip = 0, hop = 0;
-    int nf = 0, stride = 0, ncols = 0, used = 0;
-    int pre = 0;                   // 1: pre-emphasis block, frame 0 is per window; 0: MFE block
-    int run = 0;                   // shared rows per window: nf - pre
-    size_t hg = 0, phases = 0;     // hop / g, stride / g
-    bool touching = false;         // the windows of a slot overlap or abut: a slot is one run
-    int nfi = 0;                   // frames per item
-    size_t ips = 0, pitch = 0;     // items per segment (one run: no limit); rows from a slot's window to its next
-    size_t windows(size_t n) const { return n < clip ? 0 : (n - clip) / hop + 1; }
-    size_t slots(size_t W) const { return run > 0 ? std::min(W, phases) : 0; }
-    size_t slot_windows(size_t W, size_t t) const { return (W - t + phases - 1) / phases; }
-    size_t slot_rows(size_t nt) const { return touching ? (nt - 1) * hg + (size_t)run : nt * (size_t)run; }
-    size_t slot_items(size_t nt) const { return touching ? (slot_rows(nt) + nfi - 1) / nfi : nt * ips; }
-};
-
-static void slide_geom(const kws_handle *h, size_t hop, SlideGeom *G)
-{
-    const KwsDspPlan &P = h->dsp;
-    G->clip = h->model.raw_sample_count;
-    G->hop = hop;
-    G->nf = P.n_frames; G->stride = P.frame_stride; G->ncols = P.n_cepstral;
-    G->used = std::min(P.frame_len, P.fft_len);
-    G->pre = h->model.dsp.block == DSP_BLOCK_MFE ? 0 : 1;
-    G->run = G->nf - G->pre;
-    const size_t g = gcd_sz(hop, (size_t)G->stride);
-    G->hg = hop / g;
-    G->phases = (size_t)G->stride / g;
-    G->touching = G->hg <= (size_t)G->run;
-    G->nfi = std::max(1, std::min(kSlideItemFrames, G->nf));
-    G->ips = G->touching ? (size_t)1 << 62 : ((size_t)G->run + G->nfi - 1) / G->nfi;
-    G->pitch = G->touching ? G->hg : G->ips * (size_t)G->nfi;
 }
 
 // the AUTO rule: the shared path where it computes fewer rows than the direct one
@@ -132,43 +88,23 @@ static EI_IMPULSE_ERROR slide_plan(const kws_handle *h, const size_t *lengths, s
 
 // The finishing step of kws_slide_recordings_device itself: cmvnw + the handle's network in the handle's mode, chunk by chunk (h->mu held)
 struct SlideOwn {
-    kws_handle *h;
     float *scores, *features;
-    bool started = false, fast = false, count = false;
+    KwsChunkCounts counts;
+    bool started = false;
 };
 static EI_IMPULSE_ERROR slide_own_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t st)
 {
     SlideOwn &o = *(SlideOwn *)ctx;
-    kws_handle *h = o.h;
-    const Model &m = h->model;
-    const size_t F = m.nn_input_frame_size, C = m.labels.size();
-    KwsSlideScratch &S = *h->slide;
-    int rc = 0;
+    kws_handle *h = o.counts.h;
+    const size_t F = h->model.nn_input_frame_size, C = h->model.labels.size();
+    EI_IMPULSE_ERROR e;
     if (!o.started) {
         o.started = true;
-        o.fast = h->mode == KWS_MODE_FAST && h->fast_plain_ok;
-        o.count = o.fast && m.dsp.block != DSP_BLOCK_MFE;          // the MFE block's fast form is its exact one: no guard, no counts
-        if (o.count) HIP_TRY(hipMemsetAsync(S.acc, 0, sizeof(int), st));
+        if ((e = o.counts.begin(h->slide->acc, n, st))) return e;
     }
-    if (n == 0) {                                                  // after the last chunk
-        if (o.count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 1, st)))
-            return fail(KWS_ERROR_HIP, "count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        return EI_IMPULSE_OK;
-    }
-    // slide calls write no logits tap (out of the tap's [B][labels] shape): the tap is set aside for the step
-    struct TapAside {
-        kws_handle *h; float *t;
-        ~TapAside() { h->tap_logits = t; }
-    } tap_aside{ h, h->tap_logits };
-    h->tap_logits = nullptr;
-    EI_IMPULSE_ERROR e;
-    float *f = o.features ? o.features + g0 * F : nullptr;
-    if (o.fast) e = cmvn_nn_fast_device(h, win, n, o.scores + g0 * C, st, 0, 0, f);
-    else e = cmvn_nn_device(h, win, n, f, nullptr, o.scores + g0 * C, nullptr, nullptr, nullptr, st);
-    if (e) return e;
-    if (o.count && (rc = kws_launch_scan_count(h->d_flags, h->d_flags2, S.acc, 0, st)))
-        return fail(KWS_ERROR_HIP, "count kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EI_IMPULSE_OK;
+    if (n == 0) return o.counts.end(st);                           // after the last chunk
+    if ((e = kws_finish_window_chunk(h, win, n, o.scores + g0 * C, o.features ? o.features + g0 * F : nullptr, o.counts.fast, st))) return e;
+    return o.counts.chunk(st);
 }
 
 // The slide: argument checks, staging, cepstral rows and gathering for the handle's DSP block; every chunk of gathered windows
@@ -212,11 +148,8 @@ EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *
     KwsSlideScratch &S = *h->slide;
     // staged items: a run item is nfi frames one stride apart; a frame-0 item is nfi slots of S1 samples; a direct item is a window
     const size_t run_len = (((size_t)(nfi - 1) * G.stride + (size_t)std::max(G.used, 1)) + 7) & ~(size_t)7;
-    const size_t S1 = ((size_t)G.used + 1 + 7) & ~(size_t)7, first_len = (size_t)nfi * S1;
-    const size_t win_chunk = std::min(std::max<size_t>(1, std::min(kSlideMaxWindows, kSlideWindowBytes / (F * sizeof(float)))), n_win);
-    const size_t run_cap = std::max<size_t>(1, std::min(kSlideMaxItems, kSlideStageBytes / (run_len * sizeof(int16_t))));
-    const size_t first_cap = std::max<size_t>(1, std::min(kSlideMaxItems, kSlideStageBytes / (first_len * sizeof(int16_t))));
-    const size_t clip_cap = std::max<size_t>(1, std::min(kSlideMaxItems, kSlideStageBytes / (G.clip * sizeof(int16_t))));
+    const size_t first_len = (size_t)nfi * G.S1, win_chunk = kws_window_chunk(F, n_win);
+    const size_t run_cap = kws_window_item_cap(run_len), first_cap = kws_window_item_cap(first_len), clip_cap = kws_window_item_cap(G.clip);
     const size_t first_items = (win_chunk + nfi - 1) / nfi;
     size_t stage_need, wrap_need;
     if (shared) {
@@ -226,19 +159,12 @@ EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *
         stage_need = std::min(clip_cap, win_chunk) * G.clip;
         wrap_need = 1;
     }
-    const size_t n_meta = 2 * A + 2 * (A + 1) + 2 * NS + (NS + 1);
-    if ((e = grow_buffer(&S.stage, &S.stage_cap, stage_need)) || (e = grow_buffer(&S.wrap, &S.wrap_cap, wrap_need)) ||
-        (e = grow_buffer(&S.win, &S.win_cap, win_chunk * F)) || (e = grow_buffer(&S.rows, &S.rows_cap, std::max<size_t>(n_items * nfi * ncols, 1))) ||
-        (e = grow_buffer(&S.first, &S.first_cap, shared && G.pre ? first_items * nfi * ncols : 1)) || (e = grow_buffer(&S.meta, &S.meta_cap, n_meta)) ||
-        (e = grow_buffer(&S.acc, &S.acc_cap, 1)) || (e = ensure_scratch(h, win_chunk)))
+    if ((e = S.reserve(h, stage_need, wrap_need, win_chunk * F, std::max<size_t>(n_items * nfi * ncols, 1), 2 * A + 2 * (A + 1) + 2 * NS + (NS + 1), win_chunk)) ||
+        (e = grow_buffer(&S.first, &S.first_cap, shared && G.pre ? first_items * nfi * ncols : 1)))
         return e;
     ScratchUse use(h, st);
-    // tables: off [A], end [A], wbase [A + 1], sbase [A + 1], ssrc [NS], send [NS], ibase [NS + 1].  The host copy is complete before the call goes on
-    std::vector<long long> meta;
-    meta.reserve(n_meta);
-    for (const std::vector<long long> *v : { &off, &end, &wbase, &sbase, &ssrc, &send, &ibase }) meta.insert(meta.end(), v->begin(), v->end());
-    HIP_TRY(hipMemcpyAsync(S.meta, meta.data(), meta.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    // tables: off [A], end [A], wbase [A + 1], sbase [A + 1], ssrc [NS], send [NS], ibase [NS + 1]
+    if ((e = kws_upload_tables(S, { &off, &end, &wbase, &sbase, &ssrc, &send, &ibase }, st))) return e;
     const long long *d_off = S.meta, *d_end = d_off + A, *d_wbase = d_end + A, *d_sbase = d_wbase + A + 1, *d_ssrc = d_sbase + A + 1, *d_send = d_ssrc + NS,
                     *d_ibase = d_send + NS;
     int rc = 0;
@@ -256,18 +182,14 @@ EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *
             if ((e = spectral_device(h, PR, S.stage, 0, n, S.rows + g0 * nfi * ncols, S.wrap, st, nfi * ncols))) return e;
         }
     }
-    KwsDspPlan PF = h->dsp;                                 // frame 0 of nfi windows per item: the frames S1 samples apart
-    PF.frame_stride = (int)S1;
-    PF.n_samples = (int)first_len;
-    PF.n_frames = nfi;
-    PF.wrap_index = PF.n_samples - 1;
+    const KwsDspPlan PF = G.first_plan(h);                 // frame 0 of nfi windows per item: the frames S1 samples apart
     // 2. windows in chunks through the finishing step (cmvnw + the network)
     for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
         const int n = (int)std::min(win_chunk, n_win - g0);
         if (shared) {
             for (size_t i0 = 0; G.pre && i0 < (size_t)n; i0 += first_cap * nfi) {
                 const int nw = (int)std::min(first_cap * nfi, (size_t)n - i0), ni = (nw + nfi - 1) / nfi;
-                rc = kws_launch_slide_stage_first(pcm, d_off, d_wbase, (int)A, (long long)(g0 + i0), nw, nfi, (int)S1, G.used, (long long)G.hop, (int)G.clip,
+                rc = kws_launch_slide_stage_first(pcm, d_off, d_wbase, (int)A, (long long)(g0 + i0), nw, nfi, (int)G.S1, G.used, (long long)G.hop, (int)G.clip,
                                                   S.stage, S.wrap, st);
                 if (rc) return fail(KWS_ERROR_HIP, "slide staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
                 if ((e = spectral_device(h, PF, S.stage, 0, ni, S.first + i0 * ncols, S.wrap, st, nfi * ncols))) return e;
@@ -302,8 +224,9 @@ EI_IMPULSE_ERROR kws_slide_window_count(const kws_handle *h, size_t n_samples, s
     EI_IMPULSE_ERROR e = slide_check(h, hop_samples, KWS_SLIDE_AUTO);
     if (e) return e;
     if (n_samples > kSlideMaxSamples) return fail(KWS_ERROR_BAD_ARGUMENT, "recording of %zu samples", n_samples);
-    const size_t clip = h->model.raw_sample_count;
-    *n_windows = n_samples < clip ? 0 : (n_samples - clip) / hop_samples + 1;
+    SlideGeom G;
+    slide_geom(h, hop_samples, &G);
+    *n_windows = G.windows(n_samples);
     return EI_IMPULSE_OK;
 }
 
@@ -318,7 +241,7 @@ EI_IMPULSE_ERROR kws_slide_recordings_device(kws_handle *h, const int16_t *pcm, 
                                              size_t hop_samples, int flags, float *scores, float *features, void *stream)
 {
     if (!h || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    SlideOwn own{ h, scores, features };
+    SlideOwn own{ scores, features, KwsChunkCounts(h) };
     return kws_slide_run(h, pcm, offsets, lengths, R, hop_samples, flags, 1, slide_own_finish, &own, (hipStream_t)stream);
 }
 

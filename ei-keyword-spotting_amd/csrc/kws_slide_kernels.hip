@@ -9,17 +9,7 @@
 // The arithmetic of the front end and of the network is the existing kernels'; nothing here rounds except the int16 -> float of the wrap
 // sample (the same product as kws_mfcc_kernel's).
 #include "kws_device.h"
-
-// index a of the last prefix entry <= g (prefix[0] = 0, prefix ascending, n entries + the total at prefix[n])
-__device__ __forceinline__ int slide_owner(const long long *__restrict__ prefix, int n, long long g)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (prefix[mid] <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+#include "kws_window_kernels.h"
 
 // n samples from pcm + p (samples at or past `end` read as 0) to dst, dword-wide where both sides allow it.  All threads of the block.
 __device__ __forceinline__ void slide_copy(const int16_t *__restrict__ pcm, long long p, long long end, int16_t *__restrict__ dst, int n)
@@ -62,7 +52,7 @@ __global__ void kws_slide_stage_kernel(const int16_t *__restrict__ pcm, const lo
 {
     for (int j = blockIdx.x; j < n_items; j += gridDim.x) {
         const long long g = item0 + j;
-        const int s = slide_owner(ibase, n_slots, g);
+        const int s = kws_prefix_owner(ibase, n_slots, g);
         const long long k = g - ibase[s], seg = k / ips;
         const long long p = src[s] + seg * seg_pitch + (k - seg * ips) * item_adv;
         slide_copy(pcm, p, end[s], stage + (size_t)j * item_len, item_len);
@@ -83,7 +73,7 @@ __global__ void kws_slide_stage_first_kernel(const int16_t *__restrict__ pcm, co
         auto start_of = [&](int k) -> long long {
             const long long j = (long long)m * nfi + k;
             if (k >= nfi || j >= n_win) return -1;
-            const int a = slide_owner(wbase, n_rec, win0 + j);
+            const int a = kws_prefix_owner(wbase, n_rec, win0 + j);
             return off[a] + (win0 + j - wbase[a]) * hop;
         };
         long long p = start_of(0);
@@ -110,7 +100,7 @@ __global__ void kws_slide_gather_kernel(const float *__restrict__ rows, const fl
         float *dst = out + (size_t)j * (n_first + n_rest);
         if (n_rest > 0) {
             const long long g = win0 + j;
-            const int a = slide_owner(wbase, n_rec, g);
+            const int a = kws_prefix_owner(wbase, n_rec, g);
             const long long w = g - wbase[a], i = phases > 1 ? w / phases : w, t = w - i * phases;
             const float *src = rows + (size_t)(ibase[sbase[a] + t] * nfi + i * pitch) * ncols;
             for (int e = threadIdx.x; e < n_rest; e += blockDim.x) dst[n_first + e] = src[e];

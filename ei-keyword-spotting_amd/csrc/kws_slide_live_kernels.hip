@@ -16,6 +16,7 @@
 // The arithmetic of the front end and of the network is the existing kernels'; nothing here rounds except the int16 -> float of the wrap
 // sample (the same product as kws_slide_stage_kernel's).
 #include "kws_device.h"
+#include "kws_window_kernels.h"
 
 // The per-entry tables of one push, n_act entries (the entries of the call with device work), each a device array:
 struct KwsSlideLiveMeta {
@@ -29,17 +30,6 @@ struct KwsSlideLiveMeta {
     const long long *rbase;    // [n_act + 1] prefix: staged frames (new positions, then frame 0 of each new window) of the entries before
     const long long *wbase;    // [n_act + 1] prefix: windows of the entries before
 };
-
-// index a of the last prefix entry <= g (prefix[0] = 0, ascending, n entries): the entry that owns item g, empty entries skipped
-__device__ __forceinline__ int slide_live_owner(const long long *__restrict__ prefix, int n, long long g)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (prefix[mid] <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // where the samples of entry a's stream are: position p < n0 in ring[p % cap], p >= n0 at pcm[cidx + p]
 struct SlideLiveSrc {
@@ -120,7 +110,7 @@ __global__ void kws_slide_live_stage_rows_kernel(const int16_t *__restrict__ pcm
         auto frame_of = [&](int k, long long *start, long long *pred) -> int {
             const long long g = (item0 + j) * nfi + k;
             if (k >= nfi || g >= n_frames) return -1;
-            const int a = slide_live_owner(m.rbase, n_act, g);
+            const int a = kws_prefix_owner(m.rbase, n_act, g);
             const long long i = g - m.rbase[a];
             if (i < m.np[a]) {
                 *start = (m.pc0[a] + i + pre) * stride;
@@ -153,7 +143,7 @@ __global__ void kws_slide_live_stage_clips_kernel(const int16_t *__restrict__ pc
 {
     for (int j = blockIdx.x; j < n_win; j += gridDim.x) {
         const long long g = win0 + j;
-        const int a = slide_live_owner(m.wbase, n_act, g);
+        const int a = kws_prefix_owner(m.wbase, n_act, g);
         const long long w = m.w0[a] + (g - m.wbase[a]);
         slide_live_copy(slide_live_src(pcm, carry, m, a, clip), w * hop, clip, stage + (size_t)j * clip);
     }
@@ -167,7 +157,7 @@ __global__ void kws_slide_live_gather_kernel(const float *__restrict__ rows, con
     const int n_first = pre * ncols, n_rest = run * ncols;
     for (int jw = blockIdx.x; jw < n_win; jw += gridDim.x) {
         const long long g = win0 + jw;
-        const int a = slide_live_owner(m.wbase, n_act, g);
+        const int a = kws_prefix_owner(m.wbase, n_act, g);
         const long long i_w = g - m.wbase[a], j0 = (m.w0[a] + i_w) * hs, pc0 = m.pc0[a];
         const long long old = pc0 - j0;
         const int n_old = old <= 0 ? 0 : old >= run ? run : (int)old;              // the window's first n_old shared rows are retained ones
