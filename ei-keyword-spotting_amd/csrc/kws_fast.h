@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "kws_plan.h"
+#include "kws_split22.h"
 
 #define KWS_FAST_MAX_BLOCKS 8        // conv / depthwise / pointwise blocks of a fused float32 graph (= KWS_MAX_BLOCKS)
 #define KWS_FAST_NZ_MAX 12        // longest mel filter (filters 0..31) kept in registers
@@ -146,4 +147,14 @@ struct KwsFastPlan {
     // have left (kws_fast.hip: the clip loop and the kernel's end).  (A launch that does not run to its end -- a device fault -- leaves them dirty: like the rest of
     // the handle's device state, they are only good for launches that complete.)
     int *tickets;
+    // (wps = 3 only, and always 1 there: build_fast_fused gives a graph that cannot take it the two-wave layout) block 0's image ARRIVES SPLIT: cmvnw stores
+    // every feature as its two halves of x 2^KWS_SPLIT22_PRE_EXP (kws_split22.h; fast_cmvn<..., SPLIT>) and the first block skips fast_split_image.  A row
+    // keeps its stride fs; the 16 columns of cmvnw column block cb (fp32 bytes [4 cb, 4 cb + 64) of the row, read by that block alone) become 16 hi halves at
+    // byte 4 cb and 16 lo halves at byte 4 cb + 32; a last block of eight columns puts its lo halves at 4 cb + 32 as well -- for 40 columns bytes 160 .. 175,
+    // the row's padding.  So lo is KWS_FAST_PRE_LO bytes behind hi everywhere, a block's stores touch only bytes its own lanes have read (or padding), and
+    // the contraction's groups of eight channels stay contiguous: group cg at byte 64 (cg / 2) + 16 (cg % 2) (block 0's h_tab_off table).
+    // The kernel does not read this field: the three-wave build stores and contracts split operands unconditionally (kws_fast.hip: `pre`), so the field is the
+    // host's side of the agreement -- the plan builder lays block 0's table and zero block out by it, and the three-wave launchers refuse a plan without it.
+    int presplit;
 };
+#define KWS_FAST_PRE_LO 32

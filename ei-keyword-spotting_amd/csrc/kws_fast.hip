@@ -36,9 +36,13 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // Expands to nothing in the product build (two waves per SIMD), whose code it must not perturb.
 #if KWS_FAST_WPS >= 3
 #define KWS_OPAQUE3(v) asm volatile("" : "+v"(v))
+// ... and where a phase of the clip loop starts from the lane index, that index is COUNTED (two instructions, no operand) instead of copied: the copy's source lives
+// through the whole clip loop -- in scratch, as it turned out, with a reload waited for at every phase that starts from it
+#define KWS_LANE3(lane) ((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)))
 #define KWS_FAST_SINK (shared + FP.sink_off)          // one sink per workgroup (KwsFastPlan::sink_off is relative to the shared block in this build)
 #else
 #define KWS_OPAQUE3(v) do { } while (0)
+#define KWS_LANE3(lane) (lane)
 #define KWS_FAST_SINK (F + FP.sink_off)               // a sink per wave, behind its image
 #endif
 static_assert(KWS_FAST_ZF == KWS_ZF && KWS_FAST_WAVE == KWS_WAVE, "kws_fast.h mirrors kws_device.h");
@@ -424,7 +428,7 @@ __device__ __forceinline__ float fast_split_image(float *__restrict__ img, int i
 // then only reads the image.
 template <int MT>
 __device__ __forceinline__ float fast_conv_small_h(const KwsFastBlock &k, float *__restrict__ in, float *__restrict__ stage, int sstride,
-                                                   const float *__restrict__ shared, int zero_off, int lane, float *__restrict__ sink)
+                                                   const float *__restrict__ shared, int zero_off, int lane, float *__restrict__ sink, bool pre)
 {
     constexpr int KSM = 8;
     const int lm = lane & 15, lq = lane >> 4, n_ks = k.h_ks;
@@ -436,11 +440,11 @@ __device__ __forceinline__ float fast_conv_small_h(const KwsFastBlock &k, float 
         bh[ks] = *(kws_gv8h)(bg + (kc * 2) * (KWS_WAVE * 16));
         blo[ks] = *(kws_gv8h)(bg + (kc * 2 + 1) * (KWS_WAVE * 16));
     }
-    const float inv_s = fast_split_image(in, k.in_w, k.in_c, k.in_cp, k.in_stride, lane, k.inv_ppr20);
+    const float inv_s = pre ? 1.0f / (float)(1 << KWS_SPLIT22_PRE_EXP) : fast_split_image(in, k.in_w, k.in_c, k.in_cp, k.in_stride, lane, k.inv_ppr20);
     v4f acc[MT][1];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt][0] = v4f{ 0.f, 0.f, 0.f, 0.f };
-    const int rowb = k.in_stride * 4, in_w = k.in_w, lo_off = 2 * k.in_cp;
+    const int rowb = k.in_stride * 4, in_w = k.in_w, lo_off = pre ? KWS_FAST_PRE_LO : 2 * k.in_cp;
     const int row0 = lm - k.pad_left;
     const char *const abase = (const char *)in + row0 * rowb;
     const char *const zb = (const char *)(shared + zero_off);
@@ -483,18 +487,20 @@ __device__ __forceinline__ float fast_conv_small_h(const KwsFastBlock &k, float 
 // spilled registers around the block loop whichever shape runs (49x40 fp32, fragments from L2: 1.273 -> 1.254 ms same-box without it).  Where the fragments
 // ARE in LDS the two-set loop is the faster one (49x13 fp32: 1.020 against 1.051 ms), so the choice follows the kernel instantiation: the 40-filter
 // front end's plans (13.6 KB per wave: fragments of a 49-row block in L2) take ROT, the 32-filter one's (fragments in LDS) do not.
+// pre (wave-uniform; always false in the two-wave build): the image ARRIVES split -- cmvnw stored block 0's operands (fast_cmvn<..., SPLIT>; KwsFastPlan::presplit
+// has the row layout, which the plan's h_tab_off table follows): no pass over the image here, the clip-independent scale, lo KWS_FAST_PRE_LO bytes behind hi.
 template <int MT, int NT, bool BG, bool ROT = false>
 __device__ __forceinline__ float fast_conv_tiles_h(const KwsFastBlock &k, float *__restrict__ in, float *__restrict__ stage, int sstride,
-                                                   const float *__restrict__ shared, int zero_off, int lane, float *__restrict__ sink)
+                                                   const float *__restrict__ shared, int zero_off, int lane, float *__restrict__ sink, bool pre)
 {
     const int lm = lane & 15, lq = lane >> 4;
-    const float inv_s = fast_split_image(in, k.in_w, k.in_c, k.in_cp, k.in_stride, lane, k.inv_ppr20);
+    const float inv_s = pre ? 1.0f / (float)(1 << KWS_SPLIT22_PRE_EXP) : fast_split_image(in, k.in_w, k.in_c, k.in_cp, k.in_stride, lane, k.inv_ppr20);
     v4f acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = v4f{ 0.f, 0.f, 0.f, 0.f };
-    const int rowb = k.in_stride * 4, in_w = k.in_w, lo_off = 2 * k.in_cp, n_ks = k.h_ks;
+    const int rowb = k.in_stride * 4, in_w = k.in_w, lo_off = pre ? KWS_FAST_PRE_LO : 2 * k.in_cp, n_ks = k.h_ks;
     const int row0 = lm - k.pad_left;                       // image row of this lane's operand for tile 0, tap 0
     const char *const zb = (const char *)(shared + zero_off);          // 16 bytes of zeros, and again lo_off bytes further
     const int2 *const tab = (const int2 *)(shared + k.h_tab_off) + lq;  // [k-step][lane / 16] { byte offset of the group, tap }
@@ -819,11 +825,22 @@ __device__ __forceinline__ void fast_dwconv(const KwsFastBlock &k, const float *
 //  DEFER: the guard's terms are kept in registers and summed in the store loop, under the predicate the stores need anyway -- a select
 //  of its own per window (compare, scalar and, conditional move: 17 x 2 per clip) costs 2.6 % of the whole kernel; the forms with the int8
 //  network behind them sit at 256 registers and would spill the CR extra values (+7 % there): they sum in place.
-template <int CR, int CG, bool DEFER>
+//  SPLIT (the three-waves-per-SIMD build; KwsFastPlan::presplit has the row layout): the image is the first convolution block's input and leaves as that
+//  block's OPERANDS -- a value is in a register when it is stored, so the two halves of x 2^KWS_SPLIT22_PRE_EXP are formed here (kws_split22: six instructions
+//  per value) and the block's own pass over the image (fast_split_image: every value read back, a wave-wide maximum, two stores, two syncs) is gone.  The
+//  scale is the same for every clip: |output| <= sqrt(window rows) < 16 (kws_split22.h).  The k-padding channels (columns n_cepstral .. in_cp - 1) receive
+//  zero halves.  OVERFLOW: the bound is mathematical; a window whose variance cancels to zero in the running sums has rstd = 1 / eps and can exceed it.
+//  Nothing is clamped: kws_split22 then returns a difference that is not finite, its product with zero -- a NaN -- is added to this lane's guard sum, and the
+//  caller's !(V ... <= 1) hands the clip on.  One instruction per value and no predicate: a lane's rows past the last frame repeat its last live window (their
+//  update entry upd[n_frames - 1] takes out the row it puts in) and the columns past n_cepstral work on a copy of the last column, so what is not stored is
+//  finite wherever what is stored is -- but for a row group without any live row (fewer than 40 frames), whose lanes are left out.  (The NaN path through the network would NOT do: the activation clamps' fminf /
+//  fmaxf drop a NaN operand and turn an infinity into a finite bound.)
+template <int CR, int CG, bool DEFER, bool SPLIT = false>
 __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float *__restrict__ cnt_tab, const int *__restrict__ upd, int fs,
                                            float inv_win, const float *__restrict__ guard_tab, float level, float abs_scale, bool silent, float sys_t2, int piv_row, const float *__restrict__ mref, bool c0_exact, int lane, int nfr, int ncep,
-                                           const float *__restrict__ ext_tab, float *__restrict__ sink)
+                                           const float *__restrict__ ext_tab, float *__restrict__ sink, int in_cp = 0)
 {
+    static_assert(!SPLIT || (DEFER && CG == 16), "the split store is written for column blocks of 16 and the deferred guard sum");
     constexpr int NG = KWS_WAVE / CG;
     const int cgrp = min(lane / CG, NG - 1), cl = lane - (lane / CG) * CG;
     const bool lane_on = lane < NG * CG;
@@ -966,12 +983,39 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
             }
         }
         WAVE_SYNC();                                  // every lane's reads of this column block are done
+        if constexpr (SPLIT) {
+            // hi halves of the block's columns at byte 4 cb of the row, lo halves KWS_FAST_PRE_LO bytes further (an immediate offset of the second store; the
+            // sink has room for it).  A column past n_cepstral is a k-padding channel while it is below in_cp: zeros (the factor: its lane worked on a copy of the
+            // last column); past in_cp it has no place in the row.
+            _Float16 *const hcol = (_Float16 *)((char *)img + 4 * cb) + cl;
+            const bool col_on = lane_on && c < in_cp;
+            // (the factor doubles as the overflow flag -- it turns into a NaN, and with it whatever the lane stores from then on: one register instead of two)
+            float sc = c < ncep ? (float)(1 << KWS_SPLIT22_PRE_EXP) : 0.0f;
+            // (the values are pinned behind the sync: converted ahead of it -- nothing but the stores has to wait -- every value is two registers, hi and lo, where
+            // the statistics loop is at its widest, and the kernel spills the ticket it carries through the clip: a device-memory round trip waited for per clip)
+#pragma unroll
+            for (int i = 0; i < CR; ++i) asm volatile("" : "+v"(o[i]));
+#pragma unroll
+            for (int i = 0; i < CR; ++i) {
+                const int r = r0 + i;
+                const bool live = act && r < nfr;
+                _Float16 hi, lo;
+                const float d = kws_split22(o[i], sc, &hi, &lo);
+                _Float16 *const dst = (col_on && r < nfr) ? hcol + r * (2 * fs) : (_Float16 *)sink;
+                dst[0] = hi;
+                dst[KWS_FAST_PRE_LO / 2] = lo;
+                sc = __fmaf_rn(d, 0.0f, sc);                        // unchanged, or a NaN where a value left binary16's range (see above)
+                vacc = live ? __fmaf_rn(gq[i], gq[i], vacc) : vacc;
+            }
+            vacc = r0 < nfr ? __fmaf_rn(sc, 0.0f, vacc) : vacc;
+        } else {
 #pragma unroll
         for (int i = 0; i < CR; ++i) {
             const int r = r0 + i;
             const bool live = act && r < nfr;
             *(live ? col + r * fs : sink) = o[i];                  // no branch per value: rows / columns outside the matrix go to the sink
             if constexpr (DEFER) vacc = live ? __fmaf_rn(gq[i], gq[i], vacc) : vacc;
+        }
         }
     }
     WAVE_SYNC();
@@ -1068,6 +1112,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
     const int *pad_idx = (const int *)(shared + FP.pad_off);
     const int win_size = P.win_size, prow = nfr + 2 * P.pad;
     const int cr = FP.cr, n_blocks = FP.n_blocks, n_labels = FP.n_labels;
+    (void)cr;
     long long ph[KWS_FAST_NPHASE] = { 0 }, tlast = PROF ? clock64() : 0;
 
     // A window of 8 k + 1 frames leaves one frame for the tail pass, which has room for two: the tail pass of every other clip also
@@ -1082,23 +1127,27 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
 #if KWS_FAST_WPS >= 3
     // Three waves per SIMD, clips by TICKET: a workgroup of eleven waves leaves one SIMD with two, whose waves run faster -- with the static split below they
     // finish early and the launch waits for the SIMDs that hold three (vector pipe 80 % occupied where twelve waves reach 89 %, profiles/r06_occupancy.md).
-    // A wave's first clip is its own number; every further one is drawn from a counter in device memory, two clips ahead (the paired tail pass and the
-    // prefetches want the NEXT clip when a clip starts): the draw's round trip ends long before its value is looked at.  The counter cleans up after
+    // A wave's first clip is its own number; every further one is the grid's size + a ticket drawn from a counter in device memory.  A clip draws its successor's
+    // ticket FIRST THING, in front of the per-clip loads of the spectral phase, and looks at it behind them ("the ticket", below): loads and the draw return in
+    // order, so the wave waits for the draw where it would wait for those loads anyway -- and the ticket occupies a vector register over that stretch only.
+    // (Until this round it was drawn when a clip ended and looked at when the next one ended.  Its round trip was over no sooner for that -- the next clip's
+    // first wait for a load waited for it --, and carried through a whole clip it is the register the allocator gives up first wherever a phase grows by one: a
+    // ticket that lives in scratch is waited for where it is drawn, a device-memory round trip per clip.)  The counter cleans up after
     // itself -- a wave that leaves counts itself out, and the last one to do so zeroes both words (below the loop) --, so a launch needs nothing from the
     // host: no argument that changes from launch to launch, no memset.  Launches of a handle are serial (its flag
     // lists are too).
+    // (a flat pointer on purpose: said to be device memory, the draw is rewritten as one add for the whole wave whose result is handed out lane by lane --
+    // and waited for on the spot)
+    // (ni is assigned where the ticket is looked at, in the PCM forms' spectral phase: a form that starts from cepstra would never leave this loop)
+    static_assert(!FROM_CEP, "the forms that start from cepstra are not built for three waves per SIMD");
     int *const tk = FP.tickets;
-    int tv = 0;                                                       // lane 0: the ticket drawn last
     int ni = 0;
-    // (a draw only while the clip it would follow exists: when the wave leaves the loop, every draw it made has been waited for)
-    auto draw = [&]() { if (ni < n_sel && lane == 0) tv = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    draw();
-    ni = clip_stride + __builtin_amdgcn_readfirstlane(tv);
-    draw();
-    for (int ci = blockIdx.x * n_waves + wave; ci < n_sel; ci = ni, ni = ni < n_sel ? clip_stride + __builtin_amdgcn_readfirstlane(tv) : ni, draw()) {
+    for (int ci = blockIdx.x * n_waves + wave; ci < n_sel; ci = ni) {
+        // (every draw is looked at in the clip that makes it: when the wave leaves the loop, every draw it made has been waited for)
+        int tv = 0;                                                       // lane 0: the ticket
+        if (KWS_LANE3(lane) == 0) tv = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int clip = FROM_CEP ? sel_clip(sel, ci) : ci;
-        const int next_ci = ni;
-        const int next_clip = ni < n_sel ? ni : -1;                                    // the wave's next clip (paired tail pass; PCM forms only)
+        const int next_ci = ci;                                                        // (the forms that start from cepstra are not built for three waves)
 #else
     for (int ci = blockIdx.x * n_waves + wave; ci < n_sel; ci += clip_stride) {
         const int clip = FROM_CEP ? sel_clip(sel, ci) : ci;
@@ -1109,7 +1158,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         //      re-derived per clip from a lane index the compiler cannot see through: hoisted out of the clip loop, the FFT's
         //      twiddles and the three dozen LDS addresses of the pair loop stay live through the DCT, cmvnw and convolution phases
         //      and push those into scratch; re-deriving them costs ~60 L2-resident loads per clip.
-        int lane_c = lane;
+        int lane_c = KWS_LANE3(lane);
         asm volatile("" : "+v"(lane_c));
         // Eight lanes own a frame (eight frames per pass), a lane owns sixteen of its 128 complex points: kf_bfly2 (m = 1) and
         // kf_bfly4 (m = 2) run on two blocks of eight output positions in registers, ONE exchange through LDS re-deals the
@@ -1255,6 +1304,11 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         fast_i2 nxt[2][8];
         fetch(0, nxt);
         int touched = touch(1);
+#if KWS_FAST_WPS >= 3
+        // the ticket: this clip's successor
+        ni = clip_stride + __builtin_amdgcn_readfirstlane(tv);
+        const int next_clip = ni < n_sel ? ni : -1;                                    // the wave's next clip (paired tail pass)
+#endif
         const bool pair_tail = n_tail == 1 && !have_stash && next_clip >= 0;
         // the next clip's last frame: 256 samples = 512 bytes, warmed now so that the tail pass finds them in the cache
         int touched_tail = 0;
@@ -1513,7 +1567,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         //      16-frame tiles.  The transform's operand fragments are re-read per clip (L2-resident, 4 DG values per lane): kept in
         //      registers across the clip loop they push the FFT's constants into scratch.
         if constexpr (!MFE) {
-            int lane_l = lane;
+            int lane_l = KWS_LANE3(lane);
             asm volatile("" : "+v"(lane_l));                 // not loop-invariant as far as the compiler can tell
             const int lm = lane_l & 15, lq = lane_l >> 4;
             float dB[DG][2][2];
@@ -1592,7 +1646,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         int8_t *qclip = q_out ? q_out + (size_t)clip * (nfr * ncep) : nullptr;
         int8_t *const act1 = (int8_t *)R1;                              // [KWS_A1_ROWS][QCP]: row = time + tap, padding = the input zero point
         float vlane = 0.0f;
-        int lane_m = lane;
+        int lane_m = KWS_LANE3(lane);
         asm volatile("" : "+v"(lane_m));
         float *const csink = KWS_FAST_SINK + lane_m;
         // ---- column 0's window means in the reference's own order (processing.hpp:326-389 over numpy::mean_axis0, numpy.hpp:746-784:
@@ -1705,8 +1759,13 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                 abs_scale = __builtin_amdgcn_sqrtf(live / rows);
                 level *= abs_scale;
             }
-            if (KWS_FAST_WPS >= 3 || cr == 13) vlane = fast_cmvn<13, 16, QCP == 0>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink);
+#if KWS_FAST_WPS >= 3
+            // (this build runs plans with KwsFastPlan::presplit only -- the launcher checks --: ONE cmvnw instantiation, whose stores are block 0's operands)
+            vlane = fast_cmvn<13, 16, true, true>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink, FP.blk[0].in_cp);
+#else
+            if (cr == 13) vlane = fast_cmvn<13, 16, QCP == 0>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink);
             else vlane = fast_cmvn<17, 20, QCP == 0>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink);
+#endif
             gV = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wave_sum(vlane) + FP.v_net)));      // wave-uniform: a scalar register
           }
         }
@@ -1758,9 +1817,17 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
 
         // ---- the float32 graph: CONV_2D blocks ping-pong between the two images, then FULLY_CONNECTED and SOFTMAX ----------
         float *cur = F, *oth = R1;
+#if KWS_FAST_WPS >= 3
+        int lane_n = KWS_LANE3(lane);
+        asm volatile("" : "+v"(lane_n));
+        int ws_off = FP.sink_off + lane_n;
+        asm volatile("" : "+v"(ws_off));
+        float *const wsink = shared + ws_off;
+#else
         float *const wsink = KWS_FAST_SINK + lane;
         int lane_n = lane;
         asm volatile("" : "+v"(lane_n));
+#endif
         for (int b = 0; b < n_blocks; ++b) {
             const KwsFastBlock &k = FP.blk[b];
             int lane_b = lane_n;
@@ -1786,15 +1853,18 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                 // split operands on v_mfma_f32_16x16x32_f16: row tiles 1 / 2 / 4 (an idle tile costs 16 cycles per instruction there)
                 const int zo = FP.zero_off;
                 const bool bgl = k.h_b_off < 0;
-                if (bgl && k.n_tiles == 1 && k.m_tiles == 1 && k.h_ks <= 8) cscale = fast_conv_small_h<1>(k, cur, stage, sstride, shared, zo, lane_b, wsink);
+                // (three waves per SIMD: cmvnw stored block 0's operands.  A constant of the build, NOT a read of KwsFastPlan::presplit: this build has one cmvnw,
+                // which always stores them, and its launchers refuse a plan without the field set)
+                const bool pre = KWS_FAST_WPS >= 3 && b == 0;
+                if (bgl && k.n_tiles == 1 && k.m_tiles == 1 && k.h_ks <= 8) cscale = fast_conv_small_h<1>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre);
                 else
                 switch ((k.m_tiles > 2 ? 4 : k.m_tiles) * 4 + k.n_tiles) {
-                case 4 * 4 + 2: cscale = bgl ? fast_conv_tiles_h<4, 2, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink) : fast_conv_tiles_h<4, 2, false, (DG > 4)>(k, cur, stage, sstride, shared, zo, lane_b, wsink); break;
-                case 4 * 4 + 1: cscale = bgl ? fast_conv_tiles_h<4, 1, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink) : fast_conv_tiles_h<4, 1, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink); break;
-                case 2 * 4 + 2: cscale = bgl ? fast_conv_tiles_h<2, 2, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink) : fast_conv_tiles_h<2, 2, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink); break;
-                case 2 * 4 + 1: cscale = bgl ? fast_conv_tiles_h<2, 1, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink) : fast_conv_tiles_h<2, 1, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink); break;
-                case 1 * 4 + 2: cscale = bgl ? fast_conv_tiles_h<1, 2, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink) : fast_conv_tiles_h<1, 2, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink); break;
-                default: cscale = bgl ? fast_conv_tiles_h<1, 1, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink) : fast_conv_tiles_h<1, 1, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink); break;
+                case 4 * 4 + 2: cscale = bgl ? fast_conv_tiles_h<4, 2, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre) : fast_conv_tiles_h<4, 2, false, (DG > 4)>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre); break;
+                case 4 * 4 + 1: cscale = bgl ? fast_conv_tiles_h<4, 1, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre) : fast_conv_tiles_h<4, 1, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre); break;
+                case 2 * 4 + 2: cscale = bgl ? fast_conv_tiles_h<2, 2, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre) : fast_conv_tiles_h<2, 2, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre); break;
+                case 2 * 4 + 1: cscale = bgl ? fast_conv_tiles_h<2, 1, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre) : fast_conv_tiles_h<2, 1, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre); break;
+                case 1 * 4 + 2: cscale = bgl ? fast_conv_tiles_h<1, 2, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre) : fast_conv_tiles_h<1, 2, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre); break;
+                default: cscale = bgl ? fast_conv_tiles_h<1, 1, true>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre) : fast_conv_tiles_h<1, 1, false>(k, cur, stage, sstride, shared, zo, lane_b, wsink, pre); break;
                 }
             } else
             switch (k.m_tiles * 4 + k.n_tiles) {
@@ -1914,7 +1984,7 @@ int kws_launch_fast(const KwsDspPlan &P, const KwsFastPlan &FP, const KwsFastPla
 #define KWS_FAST_ARGS P, FP, d_plan, pcm, n_clips, scores, features, q_out, in_scale, in_zp, flag_count, flag_list, n_cu, nullptr, stream
 #define KWS_FAST_NARGS KWS_FAST_ARGS, nullptr, nullptr, nullptr, tap_logits
 #if KWS_FAST_WPS >= 3
-    if (FP.wps != KWS_FAST_WPS || FP.qnet || FP.mfe || !FP.fuse) return (int)hipErrorInvalidValue;        // this build: the float32-network forms
+    if (FP.wps != KWS_FAST_WPS || FP.qnet || FP.mfe || !FP.fuse || !FP.presplit) return (int)hipErrorInvalidValue;        // this build: the float32-network forms, block 0's operands stored by cmvnw
 #define KWS_FAST_PLAIN(...) ((int)hipErrorInvalidValue)
 #else
 #define KWS_FAST_PLAIN(...) (__VA_ARGS__)
@@ -1987,7 +2057,7 @@ int kws_launch_fast_prof(const KwsDspPlan &P, const KwsFastPlan &FP, const KwsFa
     (void)hipGetLastError();
     if (FP.nz > 4) return (int)hipErrorInvalidValue;
 #if KWS_FAST_WPS >= 3
-    if (FP.wps != KWS_FAST_WPS) return (int)hipErrorInvalidValue;
+    if (FP.wps != KWS_FAST_WPS || !FP.fuse || !FP.presplit) return (int)hipErrorInvalidValue;
 #else
     if (FP.wps >= 3) return kws_launch_fast_prof_w3(P, FP, d_plan, pcm, n_clips, scores, flag_count, flag_list, n_cu, prof_out, stream);
 #endif

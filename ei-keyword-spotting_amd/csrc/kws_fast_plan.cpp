@@ -167,9 +167,11 @@ static void build_guard(kws_handle *h, KwsFastPlan &F, std::vector<float> &share
     F.g_c2 = (kGuardK / kGuardLogitCap) * (kGuardK / kGuardLogitCap);
     double tot2 = 0.0;
     for (float g : gain) tot2 += (double)g * (double)g * (double)nfr;
-    F.v_net = (float)((double)kRhoDev * (double)kRhoDev * tot2) + ((h->is_float && h->gain.calibrated) ? h->gain.sigma_net * h->gain.sigma_net : 0.0f);
+    // (a plan whose block 0 receives its operands from cmvnw: the network's noise measured with that block's input at the clip-independent scale, kws_gain.cpp)
+    const float sigma_net = F.presplit ? h->gain.sigma_net_pre : h->gain.sigma_net;
+    F.v_net = (float)((double)kRhoDev * (double)kRhoDev * tot2) + ((h->is_float && h->gain.calibrated) ? sigma_net * sigma_net : 0.0f);
     F.v_net *= scale * scale;
-    F.v_net_feat = ((h->is_float && h->gain.calibrated) ? h->gain.sigma_net * h->gain.sigma_net : 0.0f) * scale * scale;
+    F.v_net_feat = ((h->is_float && h->gain.calibrated) ? sigma_net * sigma_net : 0.0f) * scale * scale;
     F.lvl_inv = 1.0f / ((float)nfr * sqrtf((float)NF));      // level = mean over the frames of |mean over the filters of the log-mel energies|
     while (shared.size() & 3) shared.push_back(0.0f);
     for (int tier = 0; tier < 2; tier++) {
@@ -441,6 +443,7 @@ static EI_IMPULSE_ERROR finish_fast_plan(kws_handle *h, KwsFastPlan &F, std::vec
     const int nfr = P.n_frames;
     std::vector<int> pmap;
     h_pad_map(nfr, P.pad, pmap);
+    // (entry n_frames - 1 stays 0: row 0 leaves and enters -- what a lane's rows past the last frame read: their window stays the last live one, fast_cmvn)
     for (int r = 0; r + 1 < nfr; r++) {
         const int packed = (pmap[r] * F.fs) | ((pmap[r + P.win_size] * F.fs) << 16);       // both < 65536
         memcpy(&shared[(size_t)F.upd_off + r], &packed, sizeof(int));
@@ -457,7 +460,7 @@ static EI_IMPULSE_ERROR finish_fast_plan(kws_handle *h, KwsFastPlan &F, std::vec
     while (shared.size() & 3) shared.push_back(0.0f);
     if (F.wps >= 3) {
         F.sink_off = (int)shared.size();             // relative to the shared block in that build (kws_fast.hip: KWS_FAST_SINK)
-        shared.insert(shared.end(), KWS_FAST_WAVE, 0.0f);
+        shared.insert(shared.end(), KWS_FAST_WAVE + KWS_FAST_PRE_LO / 4, 0.0f);      // (+ the lo half of cmvnw's split store, KWS_FAST_PRE_LO bytes behind a lane's slot)
     }
     F.shared_floats = (int)shared.size();
     fast_wave_floats(h, F, need_f, need_r1);
@@ -534,6 +537,15 @@ static EI_IMPULSE_ERROR build_fast_fused(kws_handle *h, int wps, KwsFastPlan &F)
     if (!h->is_float) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: the fused network is float32 (int8 graphs keep their exact kernels)");
     if (h->fast_plain.mfe) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: the MFE block's normalisation sits between the front end and the network (not fused)");
     const KwsNnPlanF32 &N = h->nnf;
+    const bool hconv_on = !KWS_DEV_ENV("KWS_DEV_FAST_F32_CONV");          // development aid: the fp32 matrix instruction for every block (A/B runs)
+    // The three-waves-per-SIMD build has ONE cmvnw, which stores block 0's image as that block's split operands (KwsFastPlan::presplit): a graph whose first
+    // block does not contract split operands, a cmvnw window too long for the clip-independent scale or a row without room for the lo halves is laid out for
+    // two waves (build_fast_plans asks again).
+    if (wps >= 3) {
+        if (N.n_blocks < 1 || !hconv_on || !kws_fast_block0_presplit(N.blk[0], h->model.dsp.win_size, h->dsp.n_filters + 4))
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: the first block cannot take its operands from cmvnw (three waves per SIMD)");
+        F.presplit = 1;
+    }
     if (N.n_blocks > KWS_FAST_MAX_BLOCKS) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: %d conv blocks", N.n_blocks);
     if (N.fc_out > KWS_FAST_WAVE) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: %d outputs", N.fc_out);
     std::vector<float> shared;
@@ -548,7 +560,6 @@ static EI_IMPULSE_ERROR build_fast_fused(kws_handle *h, int wps, KwsFastPlan &F)
     int need[2] = { 0, 0 };                     // floats each image region must hold beyond its first use
     // split-operand blocks (KwsFastBlock::hconv): their weight fragments, placed in LDS once everything else has its place
     std::vector<uint16_t> hfrag[KWS_FAST_MAX_BLOCKS];
-    const bool hconv_on = !KWS_DEV_ENV("KWS_DEV_FAST_F32_CONV");          // development aid: the fp32 matrix instruction for every block (A/B runs)
     while (shared.size() & 3) shared.push_back(0.0f);
     F.zero_off = (int)shared.size();
     shared.resize(shared.size() + 64, 0.0f);      // 16 bytes of zeros and 16 more up to 240 bytes further (the lo halves of a row sit 2 in_cp bytes behind the hi halves)
@@ -612,7 +623,9 @@ static EI_IMPULSE_ERROR build_fast_fused(kws_handle *h, int wps, KwsFastPlan &F)
             for (int ks = 0; ks < k.h_ks + 2; ks++)
                 for (int lq = 0; lq < 4; lq++) {
                     const int g = 4 * ks + lq;
-                    const int ent[2] = { g < G ? (g / ncg) * k.in_stride * 4 + 16 * (g % ncg) : 0, g < G ? g / ncg : (1 << 20) };
+                    // (block 0 of a presplit plan: cmvnw's row layout -- the two groups of a 16-column block side by side, the next block 64 bytes on)
+                    const int cgi = g % ncg, goff = (b == 0 && F.presplit) ? 64 * (cgi / 2) + 16 * (cgi % 2) : 16 * cgi;
+                    const int ent[2] = { g < G ? (g / ncg) * k.in_stride * 4 + goff : 0, g < G ? g / ncg : (1 << 20) };
                     for (int j = 0; j < 2; j++) { float f; memcpy(&f, &ent[j], sizeof f); shared.push_back(f); }
                 }
         }
@@ -669,7 +682,7 @@ static EI_IMPULSE_ERROR build_fast_fused(kws_handle *h, int wps, KwsFastPlan &F)
         k.h_b_global = dev;
         while (shared.size() & 3) shared.push_back(0.0f);
         const size_t fl = hfrag[b].size() / 2;
-        if ((shared.size() + fl + 4 + (F.wps >= 3 ? KWS_FAST_WAVE : 0)) + (size_t)(4 * F.wps) * F.wave_floats <= (size_t)kLdsBytes / 4 && !KWS_DEV_ENV("KWS_DEV_FAST_B_GLOBAL")) {
+        if ((shared.size() + fl + 4 + (F.wps >= 3 ? KWS_FAST_WAVE + KWS_FAST_PRE_LO / 4 : 0)) + (size_t)(4 * F.wps) * F.wave_floats <= (size_t)kLdsBytes / 4 && !KWS_DEV_ENV("KWS_DEV_FAST_B_GLOBAL")) {
             k.h_b_off = (int)shared.size();
             shared.resize(shared.size() + fl);
             memcpy(&shared[(size_t)k.h_b_off], hfrag[b].data(), fl * sizeof(float));

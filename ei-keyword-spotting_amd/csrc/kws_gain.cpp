@@ -127,13 +127,15 @@ float half_rn(float v)
     const float m = frexpf(v, &e);                                                      // v = m 2^e, 0.5 <= |m| < 1: 11 bits = multiples of 2^-11
     return ldexpf(nearbyintf(ldexpf(m, 11)), e - 11);
 }
-void split22(const std::vector<float> &v, std::vector<float> &out, float *scale)
+// fixed_exp >= 0: s = 2^fixed_exp whatever the values (block 0's input where cmvnw stores the operands: KwsFastPlan::presplit, kws_split22.h)
+void split22(const std::vector<float> &v, std::vector<float> &out, float *scale, int fixed_exp = -1)
 {
     float mx = 0.0f;
     for (float a : v) mx = std::max(mx, fabsf(a));
     int e = 0;
     if (mx > 0.0f && std::isfinite(mx)) (void)frexpf(mx, &e);
     e = std::max(-100, std::min(100, e));
+    if (fixed_exp >= 0) e = 14 - fixed_exp;
     const float s = ldexpf(1.0f, 14 - e);
     out.resize(v.size());
     for (size_t i = 0; i < v.size(); i++) {
@@ -143,7 +145,8 @@ void split22(const std::vector<float> &v, std::vector<float> &out, float *scale)
     *scale = ldexpf(1.0f, e - 14);
 }
 
-void forward_f32(const KwsNnPlanF32 &N, const kws_handle::HostF32 &W, const std::vector<float> &x, bool blocked, std::vector<float> &logits)
+// pre: block 0's input at cmvnw's clip-independent scale
+void forward_f32(const KwsNnPlanF32 &N, const kws_handle::HostF32 &W, const std::vector<float> &x, bool blocked, std::vector<float> &logits, bool pre = false)
 {
     std::vector<float> cur = x, nxt, val, cs, ws;
     for (int b = 0; b < N.n_blocks; b++) {
@@ -156,7 +159,7 @@ void forward_f32(const KwsNnPlanF32 &N, const kws_handle::HostF32 &W, const std:
             // matrix instruction is thirty-two in three passes: sigma_net is an estimate of the ORDER of the network's own noise (it enters V next to
             // terms ten times its size), not a model of the instruction
             float s1, s2;
-            split22(cur, cs, &s1);
+            split22(cur, cs, &s1, (pre && b == 0) ? KWS_SPLIT22_PRE_EXP : -1);
             split22(W.w[b], ws, &s2);
             cur.swap(cs);
             wp = &ws;
@@ -217,7 +220,7 @@ void kws_calibrate_gain(kws_handle *h)
     const kws_handle::HostF32 &W = h->hostf;
     const int nfr = N.blk[0].in_w, ncep = N.blk[0].in_c, L = N.fc_out, F = nfr * ncep;
     G.col.assign((size_t)ncep, 0.0f);
-    G.sigma_net = 0.0f;
+    G.sigma_net = G.sigma_net_pre = 0.0f;
     G.n_inputs = KWS_GAIN_INPUTS;
     G.calibrated = 1;
     std::mt19937 rng(0x6b7773u);                            // fixed: the same model always gets the same guard
@@ -227,8 +230,11 @@ void kws_calibrate_gain(kws_handle *h)
     std::vector<BlockTrace> tr((size_t)N.n_blocks);
     std::vector<double> colmax((size_t)ncep, 0.0), x((size_t)F), g, g2;
     std::vector<float> xf((size_t)F), z0, z1;
-    double net2 = 0.0;
+    double net2 = 0.0, net2_pre = 0.0;
     long net_n = 0;
+    // a plan laid out for three waves per SIMD carries block 0's input at a clip-independent scale (the plan builder asks the same predicate)
+    const bool pre = kws_fast_block0_presplit(N.blk[0], h->model.dsp.win_size, h->dsp.n_filters + 4);
+    std::vector<float> z2;
     for (int it = 0; it < KWS_GAIN_INPUTS; it++) {
         const double rho = kRho[it & 3], nz = sqrt(1.0 - rho * rho);
         for (int c = 0; c < ncep; c++) {
@@ -266,11 +272,16 @@ void kws_calibrate_gain(kws_handle *h)
         for (int i = 0; i < F; i++) xf[(size_t)i] = (float)x[(size_t)i];
         forward_f32(N, W, xf, false, z0);
         forward_f32(N, W, xf, true, z1);
+        if (pre) forward_f32(N, W, xf, true, z2, true);
         for (int a = 0; a < L; a++)
             for (int b2 = a + 1; b2 < L; b2++) {
                 const double d = ((double)z1[(size_t)a] - (double)z0[(size_t)a]) - ((double)z1[(size_t)b2] - (double)z0[(size_t)b2]);
                 net2 += d * d;
                 net_n++;
+                if (pre) {
+                    const double dp = ((double)z2[(size_t)a] - (double)z0[(size_t)a]) - ((double)z2[(size_t)b2] - (double)z0[(size_t)b2]);
+                    net2_pre += dp * dp;
+                }
             }
     }
     double tot = 0.0;
@@ -288,9 +299,10 @@ void kws_calibrate_gain(kws_handle *h)
     }
     G.total = (float)((double)KWS_GAIN_HEADROOM * sqrt(tot));
     G.sigma_net = net_n ? (float)(2.0 * sqrt(net2 / (double)net_n)) : 0.0f;      // twice the measured rms: two orders are one sample of the spread
-    if (!finite || !std::isfinite(G.total) || !std::isfinite(G.sigma_net)) {
+    G.sigma_net_pre = (pre && net_n) ? (float)(2.0 * sqrt(net2_pre / (double)net_n)) : G.sigma_net;
+    if (!finite || !std::isfinite(G.total) || !std::isfinite(G.sigma_net) || !std::isfinite(G.sigma_net_pre)) {
         for (float &v : G.col) v = INFINITY;
         G.total = INFINITY;
-        G.sigma_net = INFINITY;
+        G.sigma_net = G.sigma_net_pre = INFINITY;
     }
 }

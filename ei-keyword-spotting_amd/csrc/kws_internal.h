@@ -218,7 +218,8 @@ struct kws_handle {
     // and the list of clips the fast kernel hands back to the exact kernels
     struct HostF32 { std::vector<float> w[KWS_MAX_BLOCKS], bias[KWS_MAX_BLOCKS], addc[KWS_MAX_BLOCKS], fc_w, fc_b; } hostf;
     // kws_gain.cpp: logit gain per cepstral column of a float32 graph (calibrated at kws_create), the fused network's re-ordering noise
-    struct Gain { std::vector<float> col; float sigma_net = 0.0f, total = 0.0f; int calibrated = 0, n_inputs = 0; } gain;
+    // sigma_net_pre: sigma_net with block 0's input carried at cmvnw's clip-independent scale (KwsFastPlan::presplit) -- what a plan that takes that path adds to V
+    struct Gain { std::vector<float> col; float sigma_net = 0.0f, sigma_net_pre = 0.0f, total = 0.0f; int calibrated = 0, n_inputs = 0; } gain;
     KwsFastPlan fast_plain{}, fast_fused{}, fast_q{};   // features / int8 tensor to HBM; float32 graph fused; int8 two-block graph fused
     const KwsFastPlan *d_fast_plain = nullptr, *d_fast_fused = nullptr, *d_fast_q = nullptr;     // the same plans in device memory
     // the fused plan of the launches that start from cepstra or features (continuous mode, the second tier of a batch call, the features-in route): always
@@ -296,6 +297,15 @@ static inline bool kws_fast_block_splits(const KwsConvBlockF32 &s)
 {
     const int in_cp = (s.in_c + 7) / 8 * 8;
     return !s.depthwise && s.in_w * (in_cp / 2) <= 16 * KWS_FAST_WAVE && in_cp <= 64 && (s.out_w + 15) / 16 <= 4 && (s.out_c + 15) / 16 <= 2;
+}
+// May cmvnw store block 0's image as that block's split operands (KwsFastPlan::presplit: what the three-waves-per-SIMD build of the fast kernel runs)?  One
+// predicate again, for the plan builder and for kws_gain.cpp's model of block 0's operands: a block that splits, a cmvnw window short enough for the
+// clip-independent scale (kws_split22.h), and a row that holds the last column block's lo halves (row_floats = the image's row stride).
+static inline bool kws_fast_block0_presplit(const KwsConvBlockF32 &s, int win_size, int row_floats)
+{
+    if (!kws_fast_block_splits(s) || win_size > KWS_SPLIT22_PRE_WIN) return false;
+    const int in_cp = (s.in_c + 7) / 8 * 8, cb = (in_cp - 1) / 16 * 16;          // the last column block: columns cb .., 8 or 16 of them
+    return 4 * cb + KWS_FAST_PRE_LO + 2 * (in_cp - cb) <= 4 * row_floats;
 }
 
 // kws_api.cpp: stage launchers shared with the stream / SDK entry points (kws_sdk.cpp); internal, not exported
