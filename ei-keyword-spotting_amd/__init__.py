@@ -367,6 +367,8 @@ class Model:
         _check(self.L.kws_mfe_batch_device(self.h, pcm_ptr, B, mel_ptr, energy_ptr, stream))
 
     def extract_mfe_batch_device(self, pcm_ptr, B, features_ptr, stream=None):
+        """extract_mfe_features (the MFE DSP block) for B clips at the model's DSP settings: any shape kws_create accepts, tuned or general
+        (include/kws/kws.h); features [B][frames * filters] float32"""
         _check(self.L.kws_extract_mfe_batch_device(self.h, pcm_ptr, B, features_ptr, stream))
 
     def mfcc_batch_device(self, pcm_ptr, B, mfcc_ptr, stream=None):

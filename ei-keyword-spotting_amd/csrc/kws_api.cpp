@@ -295,11 +295,16 @@ static void generic_chunk_end(kws_handle *h, hipStream_t s, bool mine)
 static int launch_spectral_tuned_chunks(kws_handle *h, const KwsDspPlan &P, const void *pcm, int is_float, size_t B, float *mfcc, const float *wrap,
                                         int out_stride, hipStream_t s)
 {
-    if (!P.spectral_tuned || is_float || P.mfe_mel || P.ring_rows != 0 || !mfcc || ((uintptr_t)pcm & 15) != 0 || KWS_DEV_ENV("KWS_DEV_GENERIC_NO_TUNED_SPECTRAL")) return -1;
+    // (MFE block: the chunks write mel rows through kws_launch_mfe; its frames have no predecessor sample, so every chunk is launched alike.  The frame
+    // energies are indexed by the launch's own frame count: a caller who wants them keeps the cooperative kernel.  A window of another length -- ragged
+    // batches, the SDK's run_classifier -- must keep the 16-byte rows the plan was admitted for.)
+    const bool mfe = h->model.dsp.block == DSP_BLOCK_MFE;
+    if (!P.spectral_tuned || is_float || (P.mfe_mel ? (!mfe || P.mfe_energy != nullptr) : !mfcc) || P.ring_rows != 0 || ((uintptr_t)pcm & 15) != 0 ||
+        (P.n_samples * 2) % 16 != 0 || KWS_DEV_ENV("KWS_DEV_GENERIC_NO_TUNED_SPECTRAL")) return -1;
     const int nfr = P.n_frames, maxf = std::min(kws_mfcc_max_frames(P.n_filters), 49);      // (49 = six passes of eight frames + the tail pass: 98 frames are two such chunks)
     const int k = (nfr + maxf - 1) / maxf, base = nfr / k, rem = nfr % k;
     if (k > 1 && base < 16) return -1;                                    // (chunks below sixteen frames would take kws_mfcc_kernel, which has no wrap_index)
-    const int stride_out = out_stride ? out_stride : nfr * P.n_cepstral;
+    const int stride_out = out_stride ? out_stride : nfr * P.n_cepstral;                       // (MFE block: n_cepstral is the filter count)
     int f0 = 0;
     for (int c = 0; c < k; c++) {
         const int n = base + (c < rem ? 1 : 0);
@@ -308,8 +313,9 @@ static int launch_spectral_tuned_chunks(kws_handle *h, const KwsDspPlan &P, cons
         Pc.n_frames = n;
         Pc.pad = 0; Pc.win_size = 1;                                        // (the kernel stages its cmvnw pad map even when it stops at the cepstra)
         Pc.wrap_index = c == 0 ? P.n_samples - 1 : -1;
-        const int rc = kws_launch_spectral(Pc, (const int16_t *)pcm + (size_t)f0 * P.frame_stride, 0, (int)B, mfcc + (size_t)f0 * P.n_cepstral,
-                                           c == 0 ? wrap : nullptr, stride_out, grid_cap_mfcc(h), s);
+        const int16_t *const src = (const int16_t *)pcm + (size_t)f0 * P.frame_stride;
+        const int rc = P.mfe_mel ? kws_launch_mfe(Pc, src, 0, (int)B, P.mfe_mel + (size_t)f0 * P.n_filters, nullptr, nullptr, stride_out, grid_cap_mfcc(h), s)
+                                 : kws_launch_spectral(Pc, src, 0, (int)B, mfcc + (size_t)f0 * P.n_cepstral, c == 0 ? wrap : nullptr, stride_out, grid_cap_mfcc(h), s);
         if (rc) return rc;
         f0 += n;
     }
@@ -367,6 +373,13 @@ EI_IMPULSE_ERROR spectral_device(kws_handle *h, const KwsDspPlan &P, const void 
     if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
     if (h->model.dsp.block == DSP_BLOCK_MFE && !P.mfe_mel) {
         // the MFE block's per-window stage is speechpy::feature::mfe itself (extract_mfe_per_slice_features, L432 ei_run_dsp.h:420-470)
+        if (P.generic) {
+            // a general plan: the general spectral route with mel output -- mel rows where it writes cepstra for an MFCC block, the same out_stride
+            // and ring rows; pre_cof is 0, so the predecessor sample (`wrap`) is multiplied by zero
+            KwsDspPlan PM = P;
+            PM.mfe_mel = mfcc;
+            return spectral_device(h, PM, pcm, is_float, B, nullptr, wrap, s, out_stride);
+        }
         if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
         int rc = kws_launch_mfe(P, pcm, is_float, (int)B, mfcc, nullptr, wrap, out_stride, grid_cap_mfcc(h), s);
         if (rc) return fail(KWS_ERROR_HIP, "MFE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -386,20 +399,51 @@ EI_IMPULSE_ERROR spectral_device(kws_handle *h, const KwsDspPlan &P, const void 
     return EI_IMPULSE_OK;
 }
 
+// The MFE block's normalisation -- cmvnw(win, false, true) + numpy::normalize -- of B mel matrices, + the input quantisation of an int8 graph
+// (q != NULL).  Tuned plan: kws_mfe_norm_kernel in place on `features` (mel is ignored) and the quantise launch; general plan: kws_launch_mfe_norm_generic
+// from `mel` (NULL: the matrices are in `features`, which only the LDS form can read in place -- a caller that may meet the global-memory form
+// hands over another buffer).
+static EI_IMPULSE_ERROR mfe_norm_device(kws_handle *h, const KwsDspPlan &P, const float *mel, size_t B, float *features, int8_t *q, hipStream_t s)
+{
+    int rc;
+    if (P.generic) {
+        rc = kws_launch_mfe_norm_generic(P, mel ? mel : features, (int)B, features, q, h->nn.in_scale, h->nn.in_zp, s);
+    } else {
+        rc = kws_launch_mfe_norm(features, (int)B, P.n_frames, P.n_filters, P.win_size, P.pad_map, P.n_frames + 2 * P.pad, grid_cap_nn(h), s);
+        if (!rc && q) rc = kws_launch_quantize(features, q, B * (size_t)P.n_frames * P.n_filters, h->nn.in_scale, h->nn.in_zp, s);
+    }
+    if (rc) return fail(KWS_ERROR_HIP, "MFE normalisation launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return EI_IMPULSE_OK;
+}
+
+// extract_mfe_features (L432 classifier/ei_run_dsp.h:369-418) for B windows: feature::mfe, the block's normalisation, then the input quantisation
+// of an int8 graph.  Tuned plan: kws_launch_mfe into `features`; general plan: the general spectral route with mel output into the stream's
+// buffer (tuned kernel over chunks of frames where the plan allows it, else the cooperative kernel), then the general normalisation kernel.
+static EI_IMPULSE_ERROR mfe_block_device(kws_handle *h, const KwsDspPlan &P, const void *pcm, int is_float, size_t B, float *features, int8_t *q, hipStream_t s)
+{
+    if (!features) return fail(KWS_ERROR_BAD_ARGUMENT, "the MFE block needs a float feature buffer");
+    const float *mel = nullptr;
+    if (P.generic) {
+        kws_handle::GenericBuf *g = nullptr;
+        EI_IMPULSE_ERROR e = generic_for(h, s, B, &g);
+        if (e) return e;
+        mel = g->mfcc;
+        if ((e = spectral_device(h, P, pcm, is_float, B, g->mfcc, nullptr, s, 0))) return e;
+    } else {
+        if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
+        int rc = kws_launch_mfe(P, pcm, is_float, (int)B, features, nullptr, nullptr, 0, grid_cap_mfcc(h), s);
+        if (rc) return fail(KWS_ERROR_HIP, "MFE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    return mfe_norm_device(h, P, mel, B, features, q, s);
+}
+
 // extract_mfcc_features + quantisation in one launch (fused kernel)
 EI_IMPULSE_ERROR mfcc_fused_device_plan(kws_handle *h, const KwsDspPlan &P, const void *pcm, int is_float, size_t B, float *features, int8_t *q, hipStream_t s)
 {
     if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
     if (h->model.dsp.block == DSP_BLOCK_MFE) {
-        // extract_mfe_features (L432 classifier/ei_run_dsp.h:369-418): feature::mfe, cmvnw(win, false, true) + numpy::normalize, then
-        // the input quantisation of an int8 graph.  The float feature matrix is needed either way.
-        if (!features) return fail(KWS_ERROR_BAD_ARGUMENT, "the MFE block needs a float feature buffer");
-        if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
-        int rc = kws_launch_mfe(P, pcm, is_float, (int)B, features, nullptr, nullptr, 0, grid_cap_mfcc(h), s);
-        if (!rc) rc = kws_launch_mfe_norm(features, (int)B, P.n_frames, P.n_filters, P.win_size, P.pad_map, P.n_frames + 2 * P.pad, grid_cap_nn(h), s);
-        if (!rc && q) rc = kws_launch_quantize(features, q, B * h->model.nn_input_frame_size, h->nn.in_scale, h->nn.in_zp, s);
-        if (rc) return fail(KWS_ERROR_HIP, "MFE block launch failed: %s", hipGetErrorString((hipError_t)rc));
-        return EI_IMPULSE_OK;
+        // extract_mfe_features: the float feature matrix is needed either way
+        return mfe_block_device(h, P, pcm, is_float, B, features, q, s);
     }
     if (P.generic) {
         // cepstra -> g_mfcc, then cmvnw + quantisation (the general kernels are two launches; the cepstra go through HBM)
@@ -445,14 +489,18 @@ EI_IMPULSE_ERROR cmvn_nn_device(kws_handle *h, const float *mfcc, size_t B, floa
         // calc_cepstral_mean_and_var_normalization_mfe on a copy of the mel matrices (L432 classifier/ei_run_classifier.h:745-775)
         if (h->is_float && (q || tap_pooled || tap_fc || tap_out)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "int8 outputs requested from a float32 model");
         const KwsDspPlan &P = h->dsp;
-        const size_t F = h->model.nn_input_frame_size;
         float *f = features ? features : h->s_mfcc;
         int8_t *qq = h->is_float ? nullptr : (q ? q : h->s_q);
-        int rc = kws_launch_unring(mfcc, f, (int)B, P.n_frames, P.n_filters, ring_rows, ring_head, s);      // the reference normalises a COPY
+        float *copy = f;                                                                                    // the reference normalises a COPY
+        if (P.generic) {
+            kws_handle::GenericBuf *g = nullptr;
+            EI_IMPULSE_ERROR e = generic_for(h, s, B, &g);
+            if (e) return e;
+            copy = g->mfcc;
+        }
+        int rc = kws_launch_unring(mfcc, copy, (int)B, P.n_frames, P.n_filters, ring_rows, ring_head, s);
         if (rc) return fail(KWS_ERROR_HIP, "copy kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        rc = kws_launch_mfe_norm(f, (int)B, P.n_frames, P.n_filters, P.win_size, P.pad_map, P.n_frames + 2 * P.pad, grid_cap_nn(h), s);
-        if (!rc && qq) rc = kws_launch_quantize(f, qq, B * F, h->nn.in_scale, h->nn.in_zp, s);
-        if (rc) return fail(KWS_ERROR_HIP, "MFE normalisation launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (EI_IMPULSE_ERROR e = mfe_norm_device(h, P, copy, B, f, qq, s)) return e;
         if (!scores) return EI_IMPULSE_OK;
         if (h->is_float) return nn_f32_device(h, f, B, scores, nullptr, s);
         rc = kws_launch_nn(h->nn, qq, (int)B, scores, tap_pooled, h->pooled_tap_bytes, tap_fc, tap_out, grid_cap_nn(h), s);
@@ -577,22 +625,31 @@ EI_IMPULSE_ERROR kws_extract_mfe_batch_device(kws_handle *h, const int16_t *pcm,
 {
     if (!h || !pcm || !features) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
-    if (h->dsp.generic) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "the MFE block's normalisation kernel serves the tuned configurations only");
-    if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
     HIP_TRY(hipSetDevice(h->device));
     // the MFE block hands the raw signal to feature::mfe (ei_run_dsp.h:398-400; extract_mfcc_features wraps it in the
     // pre-emphasis class first): coefficient 0 makes the kernel's y = x - cof * prev the identity, bit for bit
     KwsDspPlan P = h->dsp;
     P.pre_cof = 0.0f;
-    const int rows = P.n_frames, cols = P.n_filters;
-    // cmvn_columns<17, 20> (more than 16 columns) walks 3 x 17 rows and needs a window of at least 17 rows; <13, 16>: 4 x 13, 13
-    if (rows > (cols > 16 ? 51 : 52) || P.win_size < (cols > 16 ? 17 : 13))
-        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%d frames x %d filters, window %d outside the MFE normalisation kernel's limits", rows, cols, P.win_size);
-    int rc = kws_launch_mfe(P, pcm, 0, (int)B, features, nullptr, nullptr, 0, grid_cap_mfcc(h), (hipStream_t)stream);
-    if (rc) return fail(KWS_ERROR_HIP, "MFE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    rc = kws_launch_mfe_norm(features, (int)B, rows, cols, P.win_size, P.pad_map, rows + 2 * P.pad, grid_cap_nn(h), (hipStream_t)stream);
-    if (rc) return fail(KWS_ERROR_HIP, "MFE normalisation kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EI_IMPULSE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (h->model.dsp.block == DSP_BLOCK_MFE) return mfe_block_device(h, P, pcm, 0, B, features, nullptr, s);
+    // An MFCC-block model asked for the MFE block's features of its own DSP configuration: its buffers are sized for cepstra, so the mel rows go
+    // straight to `features` and are normalised in place -- by the tuned kernel within its limits (cmvn_columns<17, 20>, more than 16 columns: 3 x 17
+    // rows and a window of at least 17; <13, 16>: 4 x 13, 13), else by the general kernel's LDS form
+    KwsDspPlan PN = P;
+    if (P.n_frames > (P.n_filters > 16 ? 51 : 52) || P.win_size < (P.n_filters > 16 ? 17 : 13)) PN.generic = 1;
+    if (PN.generic && !kws_mfe_norm_uses_lds(PN))
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%d frames x %d filters, window %d: an MFCC-block model has no buffer for the MFE normalisation's global-memory form",
+                    P.n_frames, P.n_filters, P.win_size);
+    if (P.generic) {
+        KwsDspPlan PM = P;
+        PM.mfe_mel = features;
+        if (EI_IMPULSE_ERROR e = spectral_device(h, PM, pcm, 0, B, nullptr, nullptr, s, 0)) return e;
+    } else {
+        if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
+        int rc = kws_launch_mfe(P, pcm, 0, (int)B, features, nullptr, nullptr, 0, grid_cap_mfcc(h), s);
+        if (rc) return fail(KWS_ERROR_HIP, "MFE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    return mfe_norm_device(h, PN, nullptr, B, features, nullptr, s);
 }
 
 EI_IMPULSE_ERROR kws_cmvn_inference_batch_device(kws_handle *h, const float *mfcc, size_t B, float *scores, float *features,
@@ -770,9 +827,7 @@ static EI_IMPULSE_ERROR classify_fast_device(kws_handle *h, const int16_t *pcm, 
             return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%d frames x %d filters, window %d outside the MFE normalisation kernel's limits", rows, cols, P.win_size);
         rc = kws_launch_fast(P, h->fast_plain, h->d_fast_plain, pcm, (int)B, nullptr, fx, nullptr, h->nn.in_scale, h->nn.in_zp, h->d_flags, h->d_flags + 1, h->n_cu, s);
         if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
-        rc = kws_launch_mfe_norm(fx, (int)B, rows, cols, P.win_size, P.pad_map, rows + 2 * P.pad, grid_cap_nn(h), s);
-        if (!rc && q) rc = kws_launch_quantize(fx, q, B * h->model.nn_input_frame_size, h->nn.in_scale, h->nn.in_zp, s);
-        if (rc) return fail(KWS_ERROR_HIP, "MFE block launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if ((e = mfe_norm_device(h, P, nullptr, B, fx, q, s))) return e;
         if (!scores) return EI_IMPULSE_OK;
         if (h->is_float) return nn_f32_device(h, fx, B, scores, h->tap_logits, s);
         rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s);

@@ -877,6 +877,171 @@ __global__ __launch_bounds__(64) void kws_cmvn_lds_kernel(KwsDspPlan P, const fl
 }
 
 // ---------------------------------------------------------------------------------------------------------
+//  The MFE block's normalisation at any shape (the tuned one is kws_mfe_norm_kernel, kws_misc.hip): processing::cmvnw(win_size, false, true)
+//  + numpy::normalize of the newer SDK copy (L432 dsp/speechpy/processing.hpp:327-399, dsp/numpy.hpp:1391-1429) on a plain
+//  [clip][frames x filters] mel matrix.  Per element the window sum is `win` sequential fp32 additions over the symmetric-padded rows in
+//  the reference's order, mean = sum / (float)win, o = x - mean; then min and max over the clip's whole matrix (they start at FLT_MAX /
+//  -FLT_MAX with strict comparisons: exact in any reduction order, and x - mean never produces -0), o - min, and the product with
+//  1.0f / (max - min) unless that is exactly 1.0f.  A constant clip comes out as the reference's 0 x inf.  The int8 input tensor of an
+//  int8 graph is written in the same pass.
+//  LDS form: a workgroup of 1 - 4 waves per clip stages the padded matrix through the plan's pad map as kws_cmvn_lds_kernel does (lanes on
+//  consecutive elements: consecutive addresses, no bank conflict) and keeps the un-scaled outputs behind it.  mel may be `features`: the
+//  clip is staged whole before anything is written.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int KWS_MFE_GEN_WAVES = 4;                      // most waves of a workgroup
+__global__ __launch_bounds__(KWS_WAVE * KWS_MFE_GEN_WAVES) void kws_mfe_norm_lds_kernel(KwsDspPlan P, const float *mel, int n_clips, float *features,
+                                                                                       int8_t *__restrict__ q_out, float in_scale, int in_zp)
+{
+    extern __shared__ __attribute__((aligned(16))) float mpm[];
+    const int nfr = P.n_frames, cols = P.n_filters, win = P.win_size, tid = threadIdx.x, nt = blockDim.x;
+    const int per_clip = nfr * cols, padded = (nfr + 2 * P.pad) * cols;
+    float *cen = mpm + padded;                                         // x - mean, [frames][filters]
+    float *red = cen + per_clip;                                       // a (min, max) pair per wave
+    const float fwin = (float)win;
+    for (int clip = blockIdx.x; clip < n_clips; clip += gridDim.x) {
+        const float *src = mel + (size_t)clip * per_clip;
+        for (int i = tid; i < padded; i += nt) {
+            const int row = i / cols, c = i - row * cols;
+            mpm[i] = src[P.pad_map[row] * cols + c];
+        }
+        __syncthreads();
+        float mn = FLT_MAX, mx = -FLT_MAX;                              // numpy::min / max (numpy.hpp:842-905): strict comparisons
+        for (int e = tid; e < per_clip; e += nt) {
+            const float *w0 = mpm + e;                                  // padded row r, column c of element e = r cols + c
+            float sum = 0.0f;
+#pragma unroll 8
+            for (int j = 0; j < win; j++) sum += w0[j * cols];
+            const float mean = sum / fwin;
+            const float o = w0[P.pad * cols] - mean;                    // the row itself: padded row r + pad
+            cen[e] = o;
+            if (o < mn) mn = o;
+            if (o > mx) mx = o;
+        }
+#pragma unroll
+        for (int sft = 32; sft >= 1; sft >>= 1) {
+            const float a = __shfl_xor(mn, sft), b = __shfl_xor(mx, sft);
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+        }
+        if ((tid & 63) == 0) { red[2 * (tid >> 6)] = mn; red[2 * (tid >> 6) + 1] = mx; }
+        __syncthreads();
+        for (int w = 0; w < (nt >> 6); w++) {
+            const float a = red[2 * w], b = red[2 * w + 1];
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+        }
+        const float row_scale = 1.0f / (mx - mn);                       // numpy.hpp:1416
+        for (int e = tid; e < per_clip; e += nt) {
+            float o = cen[e] - mn;                                      // numpy::subtract, then numpy::scale (skipped for 1.0f)
+            if (row_scale != 1.0f) o = o * row_scale;
+            const size_t out = (size_t)clip * per_clip + e;
+            if (features) features[out] = o;
+            if (q_out) q_out[out] = quantize_feature(o, in_scale, in_zp);
+        }
+        __syncthreads();                                                // the next clip overwrites the matrix
+    }
+}
+
+// Global-memory form, for matrices the LDS form's budget does not hold (188 x 64 with a window of 151 rows: 135 KB): one thread per element
+// writes x - mean to the output buffer (mel must be another buffer: a window reads its neighbours' rows) ...
+__global__ void kws_mfe_center_generic_kernel(KwsDspPlan P, const float *__restrict__ mel, size_t n_elems, float *__restrict__ features)
+{
+    const int nfr = P.n_frames, cols = P.n_filters, win = P.win_size;
+    const size_t per_clip = (size_t)nfr * cols;
+    const float fwin = (float)win;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_elems; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t clip = e / per_clip;
+        const int rc = (int)(e - clip * per_clip);
+        const int r = rc / cols, c = rc - r * cols;
+        const float *m = mel + clip * per_clip + c;
+        float sum = 0.0f;
+        for (int j = 0; j < win; j++) sum += m[(size_t)P.pad_map[r + j] * cols];
+        const float mean = sum / fwin;
+        features[e] = m[(size_t)r * cols] - mean;
+    }
+}
+
+// ... and a workgroup per clip takes the minimum and maximum of its clip's values, then scales them in place (+ the int8 tensor)
+__global__ __launch_bounds__(256) void kws_mfe_scale_generic_kernel(int per_clip, int n_clips, float *__restrict__ features, int8_t *__restrict__ q_out,
+                                                                    float in_scale, int in_zp)
+{
+    __shared__ float red[2 * 4];
+    const int tid = threadIdx.x;
+    for (int clip = blockIdx.x; clip < n_clips; clip += gridDim.x) {
+        float *f = features + (size_t)clip * per_clip;
+        float mn = FLT_MAX, mx = -FLT_MAX;
+        for (int e = tid; e < per_clip; e += 256) {
+            const float o = f[e];
+            if (o < mn) mn = o;
+            if (o > mx) mx = o;
+        }
+#pragma unroll
+        for (int sft = 32; sft >= 1; sft >>= 1) {
+            const float a = __shfl_xor(mn, sft), b = __shfl_xor(mx, sft);
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+        }
+        if ((tid & 63) == 0) { red[2 * (tid >> 6)] = mn; red[2 * (tid >> 6) + 1] = mx; }
+        __syncthreads();
+        for (int w = 0; w < 4; w++) {
+            const float a = red[2 * w], b = red[2 * w + 1];
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+        }
+        const float row_scale = 1.0f / (mx - mn);
+        for (int e = tid; e < per_clip; e += 256) {
+            float o = f[e] - mn;
+            if (row_scale != 1.0f) o = o * row_scale;
+            f[e] = o;
+            if (q_out) q_out[(size_t)clip * per_clip + e] = quantize_feature(o, in_scale, in_zp);
+        }
+        __syncthreads();                                                // the next clip overwrites the pairs
+    }
+}
+
+// the LDS form's need for one clip: padded matrix + un-scaled outputs + the waves' (min, max) pairs
+size_t kws_mfe_norm_lds_bytes(const KwsDspPlan &P)
+{
+    return ((size_t)(P.n_frames + 2 * P.pad) * P.n_filters + (size_t)P.n_frames * P.n_filters + 2 * KWS_MFE_GEN_WAVES) * sizeof(float);
+}
+// 64 KB: what a kernel may ask for without raising its ceiling, and at least two clips per CU (kws_launch_cmvn_generic's rule);
+// KWS_DEV_MFE_NORM_GLOBAL=1 keeps the global-memory form (same-box comparisons, tests)
+bool kws_mfe_norm_uses_lds(const KwsDspPlan &P)
+{
+    return kws_mfe_norm_lds_bytes(P) <= 64 * 1024 && !KWS_DEV_ENV("KWS_DEV_MFE_NORM_GLOBAL");
+}
+// workgroups a CU holds and waves per workgroup: as many clips as the LDS lets a CU hold (up to 16), and the waves the CU has left for each (up to four)
+void kws_mfe_norm_lds_shape(const KwsDspPlan &P, int *per_cu, int *waves)
+{
+    const size_t smem = kws_mfe_norm_lds_bytes(P);
+    *per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / smem));
+    *waves = std::max(1, std::min(KWS_MFE_GEN_WAVES, 16 / *per_cu));
+}
+
+int kws_launch_mfe_norm_generic(const KwsDspPlan &P, const float *mel, int n_clips, float *features, int8_t *q_out, float in_scale, int in_zp,
+                                hipStream_t stream)
+{
+    (void)hipGetLastError();
+    if (n_clips <= 0) return 0;
+    if (kws_mfe_norm_uses_lds(P)) {
+        int per_cu, waves;
+        kws_mfe_norm_lds_shape(P, &per_cu, &waves);
+        const int grid = std::min(n_clips, 256 * per_cu);
+        hipLaunchKernelGGL(kws_mfe_norm_lds_kernel, dim3(grid), dim3(KWS_WAVE * waves), kws_mfe_norm_lds_bytes(P), stream, P, mel, n_clips, features, q_out,
+                           in_scale, in_zp);
+        return (int)hipGetLastError();
+    }
+    if (!features || features == mel) return (int)hipErrorInvalidValue;
+    const size_t n = (size_t)n_clips * P.n_frames * P.n_filters;
+    hipLaunchKernelGGL(kws_mfe_center_generic_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, stream, P, mel, n, features);
+    int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    hipLaunchKernelGGL(kws_mfe_scale_generic_kernel, dim3(std::min(n_clips, 256 * 8)), dim3(256), 0, stream, P.n_frames * P.n_filters, n_clips, features, q_out,
+                       in_scale, in_zp);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // the LDS-resident kernel serves every general configuration whose arrays fit a CU's LDS twice over (fft up to 2048 with 64 filters);
 // KWS_DEV_GENERIC_SCRATCH=1 keeps the round-1 kernel with its scratch in HBM (same-box comparisons)
 bool kws_generic_uses_lds(const KwsDspPlan &P)

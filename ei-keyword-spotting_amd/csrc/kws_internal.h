@@ -61,6 +61,12 @@ int kws_launch_spectral_generic(const KwsDspPlan &P, const void *pcm, int pcm_is
                                 int out_stride, float *ws, int grid, int lch /* frames per chunk of the LDS kernel: 4 or 8 */, hipStream_t stream);
 int kws_launch_cmvn_generic(const KwsDspPlan &P, const float *mfcc, int n_clips, float *features, int8_t *q_out, float in_scale, int in_zp,
                             hipStream_t stream);
+// the MFE block's normalisation (cmvnw(win, false, true) + numpy::normalize, + the int8 input tensor) at any shape: the LDS form where a clip's padded
+// matrix and outputs fit its budget (mel may be features), else the global-memory form (mel must be another buffer, features is required)
+bool kws_mfe_norm_uses_lds(const KwsDspPlan &P);
+void kws_mfe_norm_lds_shape(const KwsDspPlan &P, int *per_cu, int *waves);
+int kws_launch_mfe_norm_generic(const KwsDspPlan &P, const float *mel, int n_clips, float *features, int8_t *q_out, float in_scale, int in_zp,
+                                hipStream_t stream);
 int kws_launch_synth(uint32_t seed, uint32_t first_clip, uint32_t n_clips, uint32_t clip_len, int16_t *out, hipStream_t stream);
 size_t kws_nn_smem_bytes(const KwsNnPlan &N, int n_waves);
 extern int kws_force_scalar_nn;

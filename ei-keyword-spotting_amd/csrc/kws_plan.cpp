@@ -84,13 +84,20 @@ EI_IMPULSE_ERROR build_dsp_plan(kws_handle *h)
                        (stride * 2) % 16 == 0 && (P.n_samples * 2) % 16 == 0 && nfr + 2 * P.pad <= kws_mfcc_max_prow() &&
                        c.win_size <= kws_mfcc_max_win(ncep) && nfr <= kws_mfcc_max_frames_for(N, ncep) &&
                        c.win_size >= ((N == 40 && ncep > 16) ? 17 : 13) && nfr <= 4 * kws_mfcc_cmvn_rows();
-    P.generic = tuned ? 0 : 1;
-    P.spectral_tuned = (!tuned && !mfe && c.fft_length == 256 && (N == 32 || N == 40) && frame_len >= c.fft_length && (stride * 2) % 16 == 0 &&
+    // the MFE block's tuned normalisation (kws_mfe_norm_kernel) walks cmvn_columns<17, 20> (more than 16 columns: 3 x 17 rows, a window of at least
+    // 17 rows) or <13, 16> (4 x 13, 13); an MFE block outside it, or outside the tuned kernel altogether, is a general plan like any other:
+    // the general spectral kernels write its mel rows and kws_mfe_norm_lds_kernel / the global-memory form normalise them (kws_generic.hip)
+    const bool mfe_norm_tuned = nfr <= (N > 16 ? 51 : 52) && c.win_size >= (N > 16 ? 17 : 13);
+    P.generic = (tuned && (!mfe || mfe_norm_tuned)) ? 0 : 1;
+    // A general MFE plan is admitted from 32 filters up: the filter counts at which the restated block is pinned against the compiled reference
+    // (32, 40, 64).  Below that an MFE block outside the tuned shape stays refused, as it always was.
+    if (mfe && P.generic && N < 32)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "MFE block: %d frames x %d filters, window %d: a general-shape MFE plan needs at least 32 filters", nfr, N,
+                    c.win_size);
+    // (MFE: frames have no predecessor sample, so any general MFE plan whose spectral stage fits the tuned kernel is chunkable)
+    P.spectral_tuned = (P.generic && c.fft_length == 256 && (N == 32 || N == 40) && frame_len >= c.fft_length && (stride * 2) % 16 == 0 &&
                         (P.n_samples * 2) % 16 == 0) ? 1 : 0;
     P.wrap_index = P.n_samples - 1;
-    if (mfe && (!tuned || nfr > (N > 16 ? 51 : 52) || c.win_size < (N > 16 ? 17 : 13)))
-        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "MFE block: %d frames x %d filters, window %d outside the normalisation kernel's limits (tuned "
-                    "configurations only)", nfr, N, c.win_size);
 
     std::vector<float2> tw, stw, dtw, dstw;
     h_twiddles(c.fft_length / 2, tw);

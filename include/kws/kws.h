@@ -45,7 +45,7 @@ int kws_frame_count(const kws_handle *h);                /* MFCC rows (49) */
 int kws_filter_count(const kws_handle *h);               /* mel filters of the DSP block (32) */
 int kws_pooled_tap_bytes(const kws_handle *h);           /* bytes/clip of the pooled-activation tap */
 const char *kws_nn_kernel_name(const kws_handle *h);    /* which network kernel serves this model (diagnostics) */
-const char *kws_mfcc_kernel_name(const kws_handle *h);  /* "kws_mfcc8_kernel" / "kws_mfcc_kernel" (tuned shapes), "kws_spectral_lds_kernel" (general shapes), "kws_spectral_generic_kernel" (those whose arrays exceed the LDS) */
+const char *kws_mfcc_kernel_name(const kws_handle *h);  /* the spectral kernel of int16 batches, MFCC and MFE blocks alike: "kws_mfcc8_kernel" / "kws_mfcc_kernel" (tuned shapes), "kws_mfcc8_kernel (chunked)" (general plans whose spectral stage fits the tuned kernel: chunks of at most 49 frames), "kws_spectral_lds_kernel" (general shapes), "kws_spectral_generic_kernel" (those whose arrays exceed the LDS) */
 int kws_model_is_float(const kws_handle *h);             /* 1: float32 graph (EI_CLASSIFIER_TFLITE_INPUT_QUANTIZED == 0) */
 
 /* ---- arithmetic mode of the device-resident batch hot path (kws_run_classifier_batch_device, kws_extract_mfcc_batch_device,
@@ -65,7 +65,10 @@ int kws_model_is_float(const kws_handle *h);             /* 1: float32 graph (EI
  *   KissFFT's order, fp32 power, fused mel products -- in the fast kernel and keeps the block's normalisation (it divides by the
  *   matrix's range, not by a deviation: nothing is ill-conditioned, no clip is handed back) and the network on their exact kernels;
  *   kws_run_classifier_batch_device and kws_extract_mfcc_batch_device follow the mode, the entry points that start from mel matrices
- *   (streams, kws_cmvn_inference_batch_device) have nothing left to relax. */
+ *   (streams, kws_cmvn_inference_batch_device) have nothing left to relax.  That is the tuned MFE shape (fft 256, 32 or 40 filters, at most
+ *   51 frames -- 52 up to 16 filters --, a window of at least 17 / 13 rows, 16-byte aligned frames); an MFE block at any other shape the
+ *   general MFCC path accepts (below) runs on the general kernels, exact mode only: kws_set_mode(KWS_MODE_FAST) returns
+ *   KWS_ERROR_UNSUPPORTED_MODEL with the reason, as for a general MFCC plan. */
 #define KWS_MODE_EXACT 0
 #define KWS_MODE_FAST 1
 EI_IMPULSE_ERROR kws_set_mode(kws_handle *h, int mode);   /* KWS_ERROR_UNSUPPORTED_MODEL if the model's DSP configuration is outside the fast kernel (general-shape kernels) */
@@ -180,7 +183,14 @@ EI_IMPULSE_ERROR kws_mfe_batch_device(kws_handle *h, const int16_t *pcm, size_t 
 /* extract_mfe_features for B clips -- the MFE DSP block of the newer SDK copy (nucleo-l432 .../edge-impulse-sdk/classifier/
  * ei_run_dsp.h:369-418): speechpy::feature::mfe on the raw signal (no pre-emphasis), processing::cmvnw(win_size, false, true)
  * (dsp/speechpy/processing.hpp:327-399) and numpy::normalize (dsp/numpy.hpp:1391-1429).  Frame / filter / window settings are
- * the model's DSP settings; features [B][frames * filters] float, device. */
+ * the model's DSP settings; features [B][frames * filters] float, device.
+ * Shapes: every DSP configuration kws_create accepts -- for an MFE-block model that is what a general MFCC plan meets with columns = filters:
+ * an even fft_length whose half factors into 2, 3, 4, 5 (128 ... 2048), an even filter count of 32 to 128 whose half factors likewise (fewer than 32 filters: the tuned shape only), an odd
+ * win_size, any frame count, stride and window length, frames x filters == the network's input size.  The tuned shape keeps its kernels; the
+ * others run the general spectral kernels (the tuned one over chunks of frames where fft 256, 32 / 40 filters and 16-byte aligned frames
+ * allow it) and a normalisation kernel that keeps a clip's padded matrix in LDS -- or, past 64 KB, works through global memory: no shape is
+ * refused for its size.  A constant clip (range 0) comes out as the reference's 0 x inf NaNs.  (Called on an MFCC-block model, the call
+ * normalises in place in `features` and refuses the few shapes whose padded matrix exceeds the LDS form.) */
 EI_IMPULSE_ERROR kws_extract_mfe_batch_device(kws_handle *h, const int16_t *pcm, size_t B, float *features, void *stream);
 /* extract_mfcc_features for B clips (classifier/ei_run_dsp.h:256-308) */
 EI_IMPULSE_ERROR kws_extract_mfcc_batch_device(kws_handle *h, const int16_t *pcm, size_t B, float *features,
@@ -237,7 +247,7 @@ EI_IMPULSE_ERROR kws_streams_step_device(kws_stream_batch *sb, const int16_t *sl
  *   offsets, lengths  [R], HOST arrays
  *   scores      [sum_r W_r][label_count] float, device: what run_classifier_continuous returns (after the moving average)
  *   raw_scores  [sum_r W_r][label_count] float, device, optional (NULL): the same windows before the moving average
- * Slicings and models: exactly what kws_streams_step_device accepts (int8, float32 and MFE-block models, general-shape DSP
+ * Slicings and models: exactly what kws_streams_step_device accepts (int8, float32 and MFE-block models -- tuned or general shape --, general-shape DSP
  * configurations); a slicing that the stream API refuses at any step is refused with the same error code, whatever the lengths.
  * R = 0, or no recording long enough for a window: EI_IMPULSE_OK, nothing written.  scores == NULL: KWS_ERROR_BAD_ARGUMENT.
  * Mode: KWS_MODE_EXACT is bit-identical to the stream API; KWS_MODE_FAST follows its rule (exact slice cepstra, then the fast cmvnw +
@@ -271,7 +281,7 @@ EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, c
  *               per window (MFE block: no pre-emphasis, frame 0 is shared too).  Both run the one-shot path's own spectral kernels and the
  *               same cmvnw + network launches: the paths are bit-identical to each other in either mode.
  *               AUTO takes SHARED where rows_shared + rows_first < rows_direct (kws_slide_plan reports all three, and the path).
- * Models: those of the scan (int8, float32 and MFE-block graphs, general-shape DSP configurations).
+ * Models: those of the scan (int8, float32 and MFE-block graphs, general-shape DSP configurations, MFE blocks among them).
  * hop_samples == 0, scores == NULL, unknown flags, a recording, offset or hop beyond 2^56 samples: KWS_ERROR_BAD_ARGUMENT.  R = 0, or no
  * recording long enough for a window: EI_IMPULSE_OK, nothing written.
  * Mode: KWS_MODE_EXACT as above; KWS_MODE_FAST follows the scan's rule (exact cepstral rows, then the fast cmvnw + network behind the
@@ -376,7 +386,7 @@ EI_IMPULSE_ERROR kws_bank_slide_recordings_device(kws_bank *b, const int16_t *pc
  * nothing written.
  * Mode.  The call always runs the exact kernels, like bank calls: it neither reads nor changes kws_set_mode state, the fast counters
  * (kws_fast_fallback_count / kws_fast_exact_count) or the logits tap, and writes no tap.
- * Models.  Everything the batch call serves: int8 and float32 graphs, MFCC and MFE blocks, tuned and general-shape DSP plans.
+ * Models.  Everything the batch call serves: int8 and float32 graphs, MFCC and MFE blocks, tuned and general-shape DSP plans (either block).
  *   MFCC block on the tuned shapes (fft 256, 32 or 40 filters): the whole DSP block of the batch is ONE launch, however many distinct
  *     lengths it holds (the ragged form of kws_mfcc8_kernel: frame count, length, base address and pad map per clip).  A clip whose first
  *     sample lies on a 16-byte boundary (pcm 16-byte aligned, offset a multiple of 8 samples) is read in place, no copy of its audio is
