@@ -52,6 +52,7 @@ void kws_destroy(kws_handle *h)
     (void)hipSetDevice(h->device);
     if (h->scratch_ev) { (void)hipEventSynchronize(h->scratch_ev); (void)hipEventDestroy(h->scratch_ev); }
     for (void *p : h->dev_allocs) (void)hipFree(p);
+    for (auto &hs : h->handoff.set) if (hs.buf) (void)hipFree(hs.buf);
     if (h->s_mfcc) (void)hipFree(h->s_mfcc);
     if (h->s_q) (void)hipFree(h->s_q);
     if (h->d_flags) (void)hipFree(h->d_flags);
@@ -83,6 +84,7 @@ int kws_clip_samples(const kws_handle *h) { return (int)h->model.raw_sample_coun
 int kws_frame_count(const kws_handle *h) { return h->dsp.n_frames; }
 int kws_filter_count(const kws_handle *h) { return h->dsp.n_filters; }
 int kws_pooled_tap_bytes(const kws_handle *h) { return h->pooled_tap_bytes; }
+int kws_dense_layer_count(const kws_handle *h) { return h ? h->n_dense : 0; }
 int kws_model_is_float(const kws_handle *h) { return h->is_float ? 1 : 0; }
 // (the tuned kernel of the int16 batch paths; float samples -- the SDK's signal_t callback -- run kws_mfcc_kernel, the same arithmetic on
 // the older lane layout)
@@ -95,6 +97,7 @@ const char *kws_mfcc_kernel_name(const kws_handle *h)
 }
 const char *kws_nn_kernel_name(const kws_handle *h)
 {
+    if (h->is_float ? kws_nnf_dense(h->nnf) != nullptr : kws_nn_dense(h->nn) != nullptr) return h->is_float ? "kws_dense_f32_kernel" : "kws_dense_i8_kernel";
     return h->is_float ? "kws_nn_f32_kernel" : kws_nn_uses_mfma(h->nn) ? "kws_nn_mfma_kernel" : "kws_nn_kernel";
 }
 
@@ -114,6 +117,8 @@ EI_IMPULSE_ERROR ensure_scratch(kws_handle *h, size_t B)
 EI_IMPULSE_ERROR kws_set_mode(kws_handle *h, int mode)
 {
     if (!h || (mode != KWS_MODE_EXACT && mode != KWS_MODE_FAST)) return fail(KWS_ERROR_BAD_ARGUMENT, "kws_set_mode: bad argument");
+    if (mode == KWS_MODE_FAST && h->is_float && kws_nnf_dense(h->nnf))
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a float32 graph with a dense stack has no calibrated logit gain (the guard needs one); it keeps the exact kernels");
     if (mode == KWS_MODE_FAST && !h->fast_plain_ok) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%s", h->fast_why.c_str());
     std::lock_guard<std::mutex> lk(h->mu);
     h->mode = mode;

@@ -537,6 +537,7 @@ static EI_IMPULSE_ERROR build_fast_fused(kws_handle *h, int wps, KwsFastPlan &F)
     if (!h->is_float) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: the fused network is float32 (int8 graphs keep their exact kernels)");
     if (h->fast_plain.mfe) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: the MFE block's normalisation sits between the front end and the network (not fused)");
     const KwsNnPlanF32 &N = h->nnf;
+    if (kws_nnf_dense(N)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: the fused network has no dense stack");
     const bool hconv_on = !KWS_DEV_ENV("KWS_DEV_FAST_F32_CONV");          // development aid: the fp32 matrix instruction for every block (A/B runs)
     // The three-waves-per-SIMD build has ONE cmvnw, which stores block 0's image as that block's split operands (KwsFastPlan::presplit): a graph whose first
     // block does not contract split operands, a cmvnw window too long for the clip-independent scale or a row without room for the lo halves is laid out for
@@ -704,7 +705,7 @@ static EI_IMPULSE_ERROR build_fast_fused(kws_handle *h, int wps, KwsFastPlan &F)
 EI_IMPULSE_ERROR build_fast_plans(kws_handle *h)
 {
     // float32 graphs of the tuned DSP shapes: the guard needs the graph's logit gain (kws_gain.cpp), ~50 ms of host work per model
-    if (h->is_float && !h->dsp.generic && h->nnf.n_blocks > 0 && h->nnf.blk[0].in_w == h->dsp.n_frames && h->nnf.blk[0].in_c == h->dsp.n_cepstral)
+    if (h->is_float && !h->dsp.generic && !kws_nnf_dense(h->nnf) && h->nnf.n_blocks > 0 && h->nnf.blk[0].in_w == h->dsp.n_frames && h->nnf.blk[0].in_c == h->dsp.n_cepstral)
         kws_calibrate_gain(h);
     record_silent_row(h);
     h->fast_plain_ok = build_fast_plain(h) == EI_IMPULSE_OK;

@@ -164,6 +164,11 @@ struct kws_handle {
     KwsNnPlanF32 nnf{};
     const KwsNnPlanF32 *d_nnf = nullptr;   // the same plan in device memory (the float kernel reads it from there)
     int pooled_tap_bytes = 0;
+    // dense stacks (kws_plan.h): the plans nn.dense / nnf.dense point to, the trunk's hand-off buffers, FULLY_CONNECTED layers of the graph
+    KwsDensePlan dense{};
+    KwsDensePlanF32 densef{};
+    KwsHandoff handoff{};
+    int n_dense = 1;
     std::vector<void *> dev_allocs;
     // kws_spectral_lds_kernel's frames per chunk, measured per handle on its own first large calls (kws_api.cpp generic_chunk_begin / _end)
     struct GenericTune { int choice = 0, phase = 0, armed = 0; size_t clips = 0; hipEvent_t ev[2] = { nullptr, nullptr }; double ms_per_clip[2] = { 0.0, 0.0 };

@@ -272,212 +272,115 @@ __host__ __device__ __forceinline__ NnfLayout nnf_layout(const KwsNnPlanF32 &N)
     return L;
 }
 
-template <int MAXT>     // threads per workgroup the build allows: 1024 (<= 128 VGPRs) or 512 (<= 256 VGPRs, vectorised conv steps)
-__global__ __launch_bounds__(MAXT) void kws_nn_f32_kernel(const KwsNnPlanF32 *__restrict__ Np, const float *__restrict__ features,
-                                                          int n_clips, float *__restrict__ scores,
-                                                          float *__restrict__ tap_logits, long long *__restrict__ prof,
-                                                          const int *__restrict__ sel)
-{
-    // the plan is read from memory (scalar loads, any block index); by value in the kernel arguments the compiler copies it to
-    // scratch as soon as a block is indexed dynamically
-    const KwsNnPlanF32 &N = *Np;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = blockDim.x >> 6;
-    // development aid: shader-clock totals per phase of wave 0 of workgroup 0 (input, each block, head)
-    const bool profiling = prof != nullptr && blockIdx.x == 0 && wave == 0;
-    long long ph[KWS_MAX_BLOCKS + 2] = { 0 }, tlast = profiling ? clock64() : 0;
-    auto mark = [&](int i) { if (profiling) { const long long now = clock64(); ph[i] += now - tlast; tlast = now; } };
-    // a workgroup none of whose waves has a clip (the empty re-run list of a KWS_MODE_FAST call, a short list) leaves before
-    // the weights are staged: 16.5 us -> launch overhead for the empty list
-    const int n_sel = sel_count(sel, n_clips);
-    if ((int)blockIdx.x * n_waves >= n_sel) return;
-    float *sp = (float *)smem_raw;
-    int s_w_off[KWS_MAX_BLOCKS];     // float offsets into the LDS block: pointers kept in an array lose their address space (flat loads)
-    for (int b = 0; b < N.n_blocks; ++b) {
-        const KwsConvBlockF32 &k = N.blk[b];
-        const int J = k.depthwise ? k.taps : k.taps * k.in_c, ocp = nnf_ocp(k);
-        for (int i = threadIdx.x; i < J * ocp; i += blockDim.x) {      // [oc][j] -> [j][oc], zero in the padding channels
-            const int j = i / ocp, oc = i - j * ocp;
-            sp[nnf_w_index(k, J, j, oc)] = oc < k.out_c ? (k.depthwise ? k.w[j * k.out_c + oc] : k.w[oc * J + j]) : 0.0f;
-        }
-        s_w_off[b] = (int)(sp - (float *)smem_raw);
-        sp += J * ocp;
-    }
-    const NnfLayout L = nnf_layout(N);
-    const float *s_fcw = sp, *s_fcb = sp + N.fc_out * N.fc_in;
-    for (int i = threadIdx.x; i < N.fc_out * N.fc_in; i += blockDim.x) sp[i] = N.fc_w[i];
-    for (int i = threadIdx.x; i < N.fc_out; i += blockDim.x) sp[N.fc_out * N.fc_in + i] = N.fc_bias[i];
-    sp += L.fc_floats;
-    float *A = sp + wave * (L.a_floats + L.b_floats + L.y_floats + L.vec_floats);
-    float *B = A + L.a_floats;
-    float *Y = B + L.b_floats;
-    float *vec = Y + L.y_floats;
-    __syncthreads();
+#define KWS_NNF_TRUNK 0
+#define KWS_NNF_NAME kws_nn_f32_kernel
+#include "kws_nn_f32_generic.h"
+#undef KWS_NNF_TRUNK
+#undef KWS_NNF_NAME
+#define KWS_NNF_TRUNK 1
+#define KWS_NNF_NAME kws_nn_f32_trunk_kernel
+#include "kws_nn_f32_generic.h"
+#undef KWS_NNF_TRUNK
+#undef KWS_NNF_NAME
 
-    // next-clip prefetch registers (256-register build only): NNF_PF x 64 float4 cover the first block's padded input image
-    constexpr int NNF_PF = 9;
-    float4 pf[NNF_PF];
+// ---------------------------------------------------------------------------------------------------------
+//  kws_dense_f32_kernel: the dense stack of a float32 graph (1 .. 4 FULLY_CONNECTED, fully_connected.h:26-60, then SOFTMAX, softmax.h:31-63).
+//  Every output is ONE chain -- total += x[d] * w[o][d] for d = 0 .. K - 1, product and sum rounded separately, then + bias, then the clamp --
+//  and only the order inside a chain is fixed.  So a lane owns a CLIP (a workgroup 64 of them) and the workgroup's waves share a layer's units,
+//  KWS_DENSEF_UB chains per lane side by side: a weight is the same for all 64 clips (a uniform address: one broadcast read per wave and
+//  step), i.e. the weights are read once per tile of 64 clips instead of once per clip.  Layer 0 reads its clip's row from HBM (the feature
+//  matrix or the trunk's hand-off); hidden outputs live in LDS as [unit][64 clips] (conflict-free: lane = clip), ping-pong.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int KWS_DENSEF_WAVES = 4;
+constexpr int KWS_DENSEF_UB = 4;
+
+template <bool FIRST>
+__device__ __forceinline__ void densef_layer(const KwsDenseLayerF32 &L, const float *__restrict__ xrow, const float *src, float *dst, int lane, int wave)
+{
+    const int K = L.k;
+    for (int o0 = wave * KWS_DENSEF_UB; o0 < L.units; o0 += KWS_DENSEF_WAVES * KWS_DENSEF_UB) {
+        const float *wr[KWS_DENSEF_UB];
 #pragma unroll
-    for (int u = 0; u < NNF_PF; ++u) pf[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool have_pf = false;
-    const bool pf_ok = [&]() {
-        const KwsConvBlockF32 &k = N.blk[0];
-        const int lo = k.pad_left * k.in_c, hi = lo + k.in_w * k.in_c, tot = nnf_rows(k) * k.in_c;
-        return ((lo | hi | N.n_features) & 3) == 0 && ((tot + 3) >> 2) <= 64 * NNF_PF && N.n_blocks > 1;
-    }();
-    for (int ci = blockIdx.x * n_waves + wave; ci < n_sel; ci += gridDim.x * n_waves) {
-        const int clip = sel_clip(sel, ci);
-        {
-            const KwsConvBlockF32 &k = N.blk[0];
-            const int lo = k.pad_left * k.in_c, hi = lo + k.in_w * k.in_c, tot = nnf_rows(k) * k.in_c;
-            const float *src = features + (size_t)clip * N.n_features;
-            if (have_pf) {
-                // the feature vector was requested while the previous clip's tail blocks ran (see below): it only has to be
-                // placed, zero padding rows included
-                float4 *A4 = (float4 *)A;
-                const int lo4 = lo >> 2, hi4 = hi >> 2, tot4 = (tot + 3) >> 2;
+        for (int u = 0; u < KWS_DENSEF_UB; ++u) wr[u] = L.w + (size_t)min(o0 + u, L.units - 1) * K;     // (units past the layer: a copy of the last, not stored)
+        float total[KWS_DENSEF_UB];
 #pragma unroll
-                for (int u = 0; u < NNF_PF; ++u) {
-                    const int i = lane + 64 * u;
-                    if (i < tot4) A4[i] = (i >= lo4 && i < hi4) ? pf[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int u = 0; u < KWS_DENSEF_UB; ++u) total[u] = 0.0f;
+        int d = 0;
+        for (; d + 4 <= K; d += 4) {                      // four steps' operands in flight; every chain stays in order
+            float xv[4], wv[KWS_DENSEF_UB][4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) xv[q] = FIRST ? xrow[d + q] : src[(d + q) * 64 + lane];
+#pragma unroll
+            for (int u = 0; u < KWS_DENSEF_UB; ++u)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wv[u][q] = wr[u][d + q];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int u = 0; u < KWS_DENSEF_UB; ++u) {
+                    const float prod = xv[q] * wv[u][q];
+                    total[u] += prod;
                 }
-            } else if (((lo | hi | N.n_features) & 3) == 0) {
-                // 16-byte copies (the feature vector of a clip and its place in the image are both 16-byte aligned)
-                const float4 *src4 = (const float4 *)src;
-                float4 *A4 = (float4 *)A;
-                const int lo4 = lo >> 2, hi4 = hi >> 2, tot4 = (tot + 3) >> 2;
-                for (int i0 = lane; i0 < tot4; i0 += 64 * 4) {
-                    float4 v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int i = i0 + 64 * u;
-                        v[u] = (i >= lo4 && i < hi4) ? src4[i - lo4] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int i = i0 + 64 * u;
-                        if (i < tot4) A4[i] = v[u];
-                    }
-                }
-            } else {
-                // 8 loads per lane in flight (one at a time this stage is a chain of global-memory round trips)
-                for (int i0 = lane; i0 < tot; i0 += 64 * 8) {
-                    float v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int i = i0 + 64 * u;
-                        v[u] = (i >= lo && i < hi) ? src[i - lo] : 0.0f;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int i = i0 + 64 * u;
-                        if (i < tot) A[i] = v[u];
-                    }
-                }
-            }
-            WAVE_SYNC();
         }
-        mark(0);
-        for (int b = 0; b < N.n_blocks; ++b) {
-            // a COPY of the block's parameters (scalar registers): through the reference every epilogue step reloads its clamp
-            // bounds and strides from memory, because the LDS stores in between might alias the plan
-            const KwsConvBlockF32 k = N.blk[b];
-            const bool last = (b + 1 == N.n_blocks);
-            const float *cur = (b & 1) ? B : A;
-            NnfDst dst;
-            const int n_out = k.pool_w * k.out_c;
-            if (last) { dst.p = vec; dst.row0 = 0; dst.stride = k.out_c; }
-            else {
-                const KwsConvBlockF32 &nk = N.blk[b + 1];
-                dst.p = (b & 1) ? A : B; dst.row0 = nk.pad_left; dst.stride = nk.in_c;
-                // the zero padding rows of the next block's input image (its real rows are written below)
-                const int lo = nk.pad_left * nk.in_c, hi = lo + n_out, tot = nnf_rows(nk) * nk.in_c;
-                for (int i = lane; i < tot; i += 64)
-                    if (i < lo || i >= hi) dst.p[i] = 0.0f;
-            }
-            switch (k.tb) {
-            case 8: nnf_conv_ob<8, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            case 7: nnf_conv_ob<7, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            case 4: nnf_conv_ob<4, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            case 2: nnf_conv_ob<2, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            default: nnf_conv_ob<1, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            }
-            WAVE_SYNC();
-            if (b == 0 && MAXT <= 512 && pf_ok) {
-                // block 0 (most of the clip's time) is done: request the NEXT clip's feature vector now, so that it arrives
-                // while the short tail blocks, FC and softmax run (phases with little VALU work and nothing to prefetch)
-                const int nci = ci + gridDim.x * n_waves;
-                have_pf = nci < n_sel;
-                if (have_pf) {
-                    const int nclip = sel_clip(sel, nci);
-                    const KwsConvBlockF32 &k0 = N.blk[0];
-                    const int lo4 = (k0.pad_left * k0.in_c) >> 2, hi4 = lo4 + ((k0.in_w * k0.in_c) >> 2);
-                    const float4 *src4 = (const float4 *)(features + (size_t)nclip * N.n_features);
+        for (; d < K; ++d) {
+            const float xv = FIRST ? xrow[d] : src[d * 64 + lane];
 #pragma unroll
-                    for (int u = 0; u < NNF_PF; ++u) {
-                        const int i = lane + 64 * u;
-                        if (i >= lo4 && i < hi4) pf[u] = src4[i - lo4];
-                    }
-                }
+            for (int u = 0; u < KWS_DENSEF_UB; ++u) {
+                const float prod = xv * wr[u][d];
+                total[u] += prod;
             }
-            if (nnf_staged(k)) {
-                // MAX_POOL_2D over time (pooling.h:189-237) from the staged conv output
-                for (int idx = lane; idx < n_out; idx += 64) {
-                    const int pw = nnf_div(idx, k.out_c, k.inv_outc20), oc = idx - pw * k.out_c;
-                    float mx = -FLT_MAX;
-                    for (int q = 0; q < k.pool && pw * k.pool_stride + q < k.out_w; ++q) {      // the last window may be ragged (SAME)
-                        const float v = Y[(pw * k.pool_stride + q) * k.out_c + oc];
-                        mx = mx < v ? v : mx;                          // std::max(max, v)
-                    }
-                    dst.p[(dst.row0 + pw) * dst.stride + oc] = act_clamp(mx, k.pool_min, k.pool_max);
-                }
-                WAVE_SYNC();
-            }
-            mark(1 + b);
         }
-        // FULLY_CONNECTED (fully_connected.h:26-60) + SOFTMAX (softmax.h:31-63)
-        float *lg = vec + (L.vec_floats - 64), *ex = vec;          // ex overwrites the FC input once every lane is done with it
-        const int fc_in = N.fc_in, fc_out = N.fc_out;
-        const float beta = N.beta;
-        if (lane < fc_out) {
-            const float *fw = s_fcw + lane * fc_in;
-            float total = 0.0f;
-            int d = 0;
-            for (; d + 4 <= fc_in; d += 4) {                  // four weights in flight per round trip; the chain stays in order
-                const float w0 = fw[d], w1 = fw[d + 1], w2 = fw[d + 2], w3 = fw[d + 3];
-                const float x0 = vec[d], x1 = vec[d + 1], x2 = vec[d + 2], x3 = vec[d + 3];
-                const float p0 = x0 * w0, p1 = x1 * w1, p2 = x2 * w2, p3 = x3 * w3;
-                total += p0; total += p1; total += p2; total += p3;
-            }
-            for (; d < fc_in; ++d) {
-                const float prod = vec[d] * fw[d];
-                total += prod;
-            }
-            const float lgt = act_clamp(total + s_fcb[lane], N.fc_min, N.fc_max);
-            lg[lane] = lgt;
-            if (tap_logits) tap_logits[(size_t)clip * fc_out + lane] = lgt;
-        }
-        WAVE_SYNC();
-        // softmax.h:31-63: max, then sum += exp((x - max) * beta) in class order, then exp(...) / sum.  Each lane evaluates
-        // its own class's exponential once; the sum adds the same values in the same order
-        float e_own = 0.0f;
-        if (lane < fc_out) {
-            float mx = -FLT_MAX;
-            for (int c = 0; c < fc_out; ++c) mx = mx < lg[c] ? lg[c] : mx;
-            e_own = expf((lg[lane] - mx) * beta);
-            ex[lane] = e_own;
-        }
-        WAVE_SYNC();
-        if (lane < fc_out) {
-            float sum = 0.0f;
-            for (int c = 0; c < fc_out; ++c) sum += ex[c];
-            scores[(size_t)clip * fc_out + lane] = e_own / sum;
-        }
-        WAVE_SYNC();
-        mark(1 + KWS_MAX_BLOCKS);
+#pragma unroll
+        for (int u = 0; u < KWS_DENSEF_UB; ++u)
+            if (o0 + u < L.units) dst[(o0 + u) * 64 + lane] = act_clamp(total[u] + L.bias[o0 + u], L.lo, L.hi);
     }
-    if (profiling && lane == 0)
-        for (int i = 0; i < KWS_MAX_BLOCKS + 2; ++i) prof[i] = ph[i];
+}
+
+__host__ __device__ inline size_t kws_dense_f32_smem_bytes(const KwsDensePlanF32 &D) { return (size_t)(D.buf_floats[0] + D.buf_floats[1]) * 64 * sizeof(float); }
+
+// x: by_clip = 1: the feature matrices [n_clips][K]; 0: the trunk's hand-off [ci - ci0][K].  List entries ci0 .. ci1 - 1 are served.
+__global__ __launch_bounds__(KWS_WAVE * KWS_DENSEF_WAVES) void kws_dense_f32_kernel(KwsDensePlanF32 D, const float *__restrict__ x, int by_clip, int ci0,
+                                                                                   int ci1, int n_clips, float *__restrict__ scores,
+                                                                                   float *__restrict__ tap_logits, const int *__restrict__ sel)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n_end = min(sel_count(sel, n_clips), ci1);
+    float *buf0 = (float *)smem_raw, *buf1 = buf0 + D.buf_floats[0] * 64;
+    const int n_labels = D.n_labels;
+    for (int cb = ci0 + (int)blockIdx.x * 64; cb < n_end; cb += (int)gridDim.x * 64) {
+        // lanes past the batch repeat the last clip (computed, never stored)
+        const int ci = min(cb + lane, n_end - 1);
+        const bool valid = cb + lane < n_end;
+        const int clip = sel_clip(sel, ci);
+        const float *xrow = x + (size_t)(by_clip ? clip : ci - ci0) * D.l[0].k;
+        densef_layer<true>(D.l[0], xrow, nullptr, buf0, lane, wave);
+        __syncthreads();
+#pragma unroll
+        for (int l = 1; l < KWS_DENSE_MAX; ++l) {
+            if (l < D.n_layers) {
+                densef_layer<false>(D.l[l], nullptr, (l & 1) ? buf0 : buf1, (l & 1) ? buf1 : buf0, lane, wave);
+                __syncthreads();
+            }
+        }
+        float *lg = ((D.n_layers - 1) & 1) ? buf1 : buf0;
+        if (wave == 0) {
+            // softmax.h:31-63: max, then sum += exp((x - max) * beta) in class order, then exp(...) / sum
+            float mx = -FLT_MAX;
+            for (int c = 0; c < n_labels; ++c) { const float v = lg[c * 64 + lane]; mx = mx < v ? v : mx; }
+            float sum = 0.0f;
+            for (int c = 0; c < n_labels; ++c) {
+                const float v = lg[c * 64 + lane];
+                if (tap_logits && valid) tap_logits[(size_t)clip * n_labels + c] = v;
+                const float e = expf((v - mx) * D.beta);
+                lg[c * 64 + lane] = e;
+                sum += e;
+            }
+            if (valid)
+                for (int c = 0; c < n_labels; ++c) scores[(size_t)clip * n_labels + c] = lg[c * 64 + lane] / sum;
+        }
+        __syncthreads();
+    }
 }
 
 size_t kws_nn_f32_smem_bytes(const KwsNnPlanF32 &N, int n_waves)
@@ -538,11 +441,58 @@ int kws_nn_f32_waves(const KwsNnPlanF32 &N)
     return 4;
 }
 
+// A graph with a dense stack: the conv blocks (if any) in the trunk form of kws_nn_f32_kernel, chunk by chunk of the hand-off buffer, each chunk followed
+// by kws_dense_f32_kernel over the same list entries.
+static int launch_dense_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, const float *features, int n_clips, float *scores, float *tap_logits,
+                            int n_cu, hipStream_t stream, const int *sel)
+{
+    const KwsDensePlanF32 &D = *N.dense;
+    const size_t dsmem = kws_dense_f32_smem_bytes(D);
+    if (dsmem > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)kws_dense_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dsmem);
+        if (e != hipSuccess) return (int)e;
+    }
+    auto dense_grid = [&](int n) { const int g = (n + 63) / 64; return g > n_cu * 8 ? n_cu * 8 : g; };
+    if (N.n_blocks == 0) {
+        hipLaunchKernelGGL(kws_dense_f32_kernel, dim3(dense_grid(n_clips)), dim3(KWS_WAVE * KWS_DENSEF_WAVES), dsmem, stream, D, features, 1, 0, n_clips, n_clips,
+                           scores, tap_logits, sel);
+        return (int)hipGetLastError();
+    }
+    float *ho = (float *)kws_handoff_for(N.handoff, (void *)stream);
+    if (!ho) return (int)hipErrorOutOfMemory;
+    const int n_waves = kws_nn_f32_waves(N);
+    const size_t smem = kws_nn_f32_smem_bytes(N, n_waves);
+    const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / smem);
+    const void *fn = n_waves <= 8 ? (const void *)kws_nn_f32_trunk_kernel<512> : (const void *)kws_nn_f32_trunk_kernel<1024>;
+    if (smem > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return (int)e;
+    }
+    const int chunk = (int)(N.handoff->bytes / (sizeof(float) * (size_t)N.fc_in));            // >= 1024 clips at KWS_HANDOFF_BYTES
+    for (int c0 = 0; c0 < n_clips; c0 += chunk) {
+        const int c1 = n_clips - c0 > chunk ? c0 + chunk : n_clips, n = c1 - c0;
+        int grid = (n + n_waves - 1) / n_waves;
+        if (grid > n_cu * per_cu) grid = n_cu * per_cu;
+        if (n_waves <= 8)
+            hipLaunchKernelGGL(kws_nn_f32_trunk_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
+                               kws_dev_f32_prof, sel);
+        else
+            hipLaunchKernelGGL(kws_nn_f32_trunk_kernel<1024>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
+                               kws_dev_f32_prof, sel);
+        hipLaunchKernelGGL(kws_dense_f32_kernel, dim3(dense_grid(n)), dim3(KWS_WAVE * KWS_DENSEF_WAVES), dsmem, stream, D, (const float *)ho, 0, c0, c1, n_clips,
+                           scores, tap_logits, sel);
+        const int rc = (int)hipGetLastError();
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 int kws_launch_nn_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, const float *features, int n_clips, float *scores,
                       float *tap_logits, int n_cu, hipStream_t stream, const int *sel)
 {
     (void)hipGetLastError();      // the status returned below is this launch's, not a stale error of an earlier call
     if (n_clips <= 0) return 0;
+    if (kws_nnf_dense(N)) return launch_dense_f32(N, d_plan, features, n_clips, scores, tap_logits, n_cu, stream, sel);
     const int n_waves = kws_nn_f32_waves(N), grid_mult = 1;
     const size_t smem = kws_nn_f32_smem_bytes(N, n_waves);
     const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / smem);

@@ -128,6 +128,35 @@ __device__ __forceinline__ T wave_reduce(T v, Op op)
 __device__ __forceinline__ int wave_reduce_max(int v) { return wave_reduce<int>(v, [](int a, int b) { return max(a, b); }); }
 __device__ __forceinline__ unsigned wave_reduce_add(unsigned v) { return wave_reduce<unsigned>(v, [](unsigned a, unsigned b) { return a + b; }); }
 
+// SOFTMAX int8 -> int8 of one clip: lane = class (on: lane < n_out, logit: its FULLY_CONNECTED output).  The softmax half of nn_head below, for
+// kws_dense_i8_kernel (a copy, not a call from nn_head: the kernels that inline nn_head keep their code objects, profiles/dense_codeobj.md)
+__device__ __forceinline__ void nn_softmax(int n_out, int out_zp, float out_scale, const NnHeadTab &H, bool on, int logit, int lane, int clip,
+                                           float *__restrict__ scores, const NnTaps &taps)
+{
+    // ---- SOFTMAX int8 -> int8 (reference/softmax.h:66-144): lane = class; the maximum and the sum of exponentials are wave
+    //      reductions (the reference's unsigned wrap-around additions commute) ----------------------------------------------
+    const int mx = wave_reduce_max(on ? logit : -128);
+    const int d = on ? mx - logit : 0;
+    const bool valid = on && H.sm_valid[d] != 0;
+    const int ex = H.sm_exp[d];
+    const int sum = (int)wave_reduce_add(valid ? (unsigned)rdivpot(ex, 12) : 0u);
+    if (on) {
+        const int hp1 = sum ? __clz(sum) : 32;                                  // GetReciprocal, common.h:530-546
+        const int nbits = 12 - hp1;
+        const int ssm1 = (int)(((unsigned)sum << hp1) - (1u << 31));
+        const int scale = one_over_one_plus_x(ssm1);
+        int o = -128;
+        if (valid) {
+            const int unsat = rdivpot(srdhm(scale, ex), nbits + 31 - 8);
+            o = min(max(unsat - 128, -128), 127);
+        }
+        if (taps.out_q) taps.out_q[(size_t)clip * n_out + lane] = (int8_t)o;
+        scores[(size_t)clip * n_out + lane] = (float)(o - out_zp) * out_scale;   // ei_run_classifier.h:470
+    }
+    WAVE_SYNC();
+}
+
+
 __device__ __forceinline__ void nn_head(const KwsNnPlan &N, const NnHeadTab &H, const int8_t *xin, int *lg, int lane, int clip,
                                         float *__restrict__ scores, const NnTaps &taps)
 {
@@ -398,7 +427,7 @@ __device__ __forceinline__ void nn_mfma_clip(const Ctx &c, const KwsNnPlan &N, c
 // the matrix-core kernel covers this graph shape; anything else runs on kws_nn_kernel
 static bool nn_fits_mfma(const KwsNnPlan &N)
 {
-    if (N.n_blocks != 2) return false;
+    if (N.n_blocks != 2 || kws_nn_dense(N)) return false;        // (a dense stack behind the blocks: the trunk form of kws_nn_kernel + kws_dense_i8_kernel)
     const KwsConvBlock &a = N.blk[0], &b = N.blk[1];
     if (a.depthwise || b.depthwise) return false;
     return (a.in_cpad == 16 || a.in_cpad <= 64) && a.taps <= 8 && a.out_c <= 32 && a.in_w <= 64 && a.pool == KWS_MFMA_POOL && a.pool_stride == KWS_MFMA_POOL &&

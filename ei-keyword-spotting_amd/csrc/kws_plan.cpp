@@ -192,6 +192,172 @@ static bool h_left_shift_overflows(int64_t wabs, int32_t in_off, int32_t bias, i
     return shift > 30 || bound > (0x7fffffffll >> shift);
 }
 
+// SOFTMAX int8 -> int8 (softmax.cc:187-226): everything but the final reciprocal/rescale depends only on (max - x)
+static EI_IMPULSE_ERROR build_softmax_tables(kws_handle *h, size_t i, int cur, const int32_t **sm_exp, const uint8_t **sm_valid)
+{
+    const Model &m = h->model;
+    const Tensor &tout = m.t[m.t_out];
+    if (i >= m.n.size() || m.n[i].op != OP_SOFTMAX || m.n[i].in[0] != cur || m.n[i].out[0] != (int)m.t_out || i + 1 != m.n.size())
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected a final SOFTMAX");
+    const Node &sn = m.n[i];
+    const Tensor &x = m.t[cur];
+    if (tout.scale[0] != 1.f / 256 || tout.zero[0] != -128) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "softmax output quantisation");
+    double rm = (double)sn.beta * (double)x.scale[0] * (double)(1 << (31 - 5));
+    rm = std::min(rm, (double)((1ll << 31) - 1.0));
+    int32_t mult; int left_shift;
+    h_quantize_multiplier(rm, &mult, &left_shift);
+    const double max_in = 1.0 * ((1 << 5) - 1) * (double)(1ll << (31 - 5)) / (double)(1ll << left_shift);
+    const int diff_min = (int)(-1.0 * (double)(int)floor(max_in));
+    std::vector<int32_t> ex(256);
+    std::vector<uint8_t> valid(256);
+    for (int d = 0; d < 256; d++) {
+        const int32_t diff = -d;
+        valid[d] = diff >= diff_min;
+        const int32_t resc = h_srdhm((int32_t)((uint32_t)diff * (1u << left_shift)), mult);
+        ex[d] = valid[d] ? h_exp_neg_q5_26(resc) : 0;
+    }
+    EI_IMPULSE_ERROR e;
+    if ((e = h->upload(ex, sm_exp))) return e;
+    if ((e = h->upload(valid, sm_valid))) return e;
+    return EI_IMPULSE_OK;
+}
+
+static std::mutex g_handoff_mu;
+static void handoff_init(kws_handle *h, size_t row_bytes)
+{
+    h->handoff.bytes = KWS_HANDOFF_BYTES;
+    if (const char *ev = KWS_DEV_ENV("KWS_DEV_HANDOFF_BYTES")) { const long v = atol(ev); if (v > 0 && (size_t)v < KWS_HANDOFF_BYTES) h->handoff.bytes = (size_t)v; }
+    if (h->handoff.bytes < row_bytes) h->handoff.bytes = row_bytes;          // at least one clip per chunk
+}
+void *kws_handoff_for(KwsHandoff *H, void *stream)
+{
+    std::lock_guard<std::mutex> lk(g_handoff_mu);
+    for (auto &s_ : H->set) if (s_.used && s_.stream == stream) return s_.buf;
+    for (auto &s_ : H->set)
+        if (!s_.used) {
+            if (hipMalloc(&s_.buf, H->bytes) != hipSuccess) { s_.buf = nullptr; return nullptr; }
+            s_.used = 1; s_.stream = stream;
+            return s_.buf;
+        }
+    // more streams than sets: a set changes hands once everything enqueued has finished with it
+    if (hipDeviceSynchronize() != hipSuccess) return nullptr;
+    auto &s_ = H->set[H->next];
+    H->next = (H->next + 1) % KWS_HANDOFF_SETS;
+    s_.stream = stream;
+    return s_.buf;
+}
+
+// Is what starts at node i a dense stack?  A FULLY_CONNECTED that follows no conv block, or that is followed by another one.  Every graph
+// served before keeps its kernels, and a single FULLY_CONNECTED behind conv blocks keeps the limits of those kernels' own head (KWS_FC_IN_MAX /
+// KWS_FC_W_MAX): beyond them it is refused as it always was.
+static bool h_dense_stack(const Model &m, size_t i, int n_blocks)
+{
+    if (i >= m.n.size() || m.n[i].op != OP_FULLY_CONNECTED) return false;
+    if (n_blocks == 0) return true;
+    size_t j = i + 1;
+    while (j < m.n.size() && m.n[j].op == OP_RESHAPE) j++;
+    return j < m.n.size() && m.n[j].op == OP_FULLY_CONNECTED;
+}
+
+// The dense stack of an int8 graph: 1 .. 4 FULLY_CONNECTED (fully_connected.cc:322-396, per-tensor quantisation) from node i on, whose
+// first layer reads `inputs` values of the flowing tensor cur; then SOFTMAX.
+static EI_IMPULSE_ERROR build_dense_i8(kws_handle *h, size_t i, int cur, int inputs)
+{
+    const Model &m = h->model;
+    KwsNnPlan &N = h->nn;
+    KwsDensePlan &D = h->dense;
+    memset(&D, 0, sizeof(D));
+    D.tap_off = h->pooled_tap_bytes;
+    D.n_labels = N.n_labels;
+    D.out_scale = N.out_scale; D.out_zp = N.out_zp;
+    auto same_quant = [&](int a, int b) {
+        return !m.t[a].scale.empty() && !m.t[b].scale.empty() && m.t[a].scale[0] == m.t[b].scale[0] && m.t[a].zero[0] == m.t[b].zero[0];
+    };
+    int k_in = inputs, lds_used = 0;
+    D.act_stride = 64 + 16;
+    while (i < m.n.size() && m.n[i].op == OP_FULLY_CONNECTED) {
+        const int li = D.n_layers;
+        if (li >= KWS_DENSE_MAX) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "more than %d FULLY_CONNECTED layers", KWS_DENSE_MAX);
+        const Node &fc = m.n[i];
+        if (fc.in[0] != cur) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: input is not the flowing tensor", li);
+        const Tensor &x = m.t[cur], &w = m.t[fc.in[1]], &y = m.t[fc.out[0]];
+        const Tensor *bias = (fc.in.size() > 2 && fc.in[2] >= 0) ? &m.t[fc.in[2]] : nullptr;
+        const long units = w.dims[0], k = w.dims[1];
+        if (x.type != TYPE_I8 || w.type != TYPE_I8 || y.type != TYPE_I8 || x.scale.empty() || w.scale.empty() || y.scale.empty() || x.zero.empty() ||
+            w.zero.empty() || y.zero.empty() || w.scale.size() != 1)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: tensor types (int8, per-tensor quantisation)", li);
+        if (k != k_in || k > KWS_DENSE_IN_MAX || units < 1 || units > KWS_DENSE_UNITS_MAX || units * k > KWS_DENSE_W_MAX || !w.is_const ||
+            (long)w.nbytes != units * k || (long)w.data.size() < units * k || y.dims.back() != units || (long)y.nbytes != units)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: weights [%ld][%ld] for %d inputs are outside the kernel's limits (%d units, %d inputs, %d bytes)",
+                        li, units, k, k_in, KWS_DENSE_UNITS_MAX, KWS_DENSE_IN_MAX, KWS_DENSE_W_MAX);
+        if (bias && (!bias->is_const || bias->type != TYPE_I32 || (long)bias->nbytes != units * 4 || (long)bias->data.size() < units * 4))
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: bias", li);
+        if (fc.p[0] < 0 || fc.p[0] > 3) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: fused activation %d", li, fc.p[0]);
+        KwsDenseLayer &L = D.l[li];
+        L.k = (int)k; L.kpad = ((int)k + 63) & ~63; L.units = (int)units; L.upad = ((int)units + 15) & ~15;
+        const int32_t in_off = -x.zero[0];
+        L.w_off = -w.zero[0]; L.out_zp = y.zero[0];
+        const double in_prod = (double)(x.scale[0] * w.scale[0]);     // kernel_util_lite.cc:160-172 (float product)
+        int32_t mult; int exponent;
+        h_quantize_multiplier(in_prod / (double)y.scale[0], &mult, &exponent);
+        if (mult < 0 || exponent < -31) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: requantisation multiplier", li);
+        L.mult = mult; L.shift = exponent;
+        int32_t amin, amax;
+        h_act_range(fc.p[0], y.scale[0], y.zero[0], &amin, &amax);
+        L.act_min = amin; L.act_max = amax;
+        const int8_t *wd = (const int8_t *)w.data.data();
+        const int32_t *bd = bias ? (const int32_t *)bias->data.data() : nullptr;
+        std::vector<int32_t> beff((size_t)L.upad, 0);
+        for (int o = 0; o < L.units; o++) {
+            int64_t wsum = 0, wabs = 0;
+            for (int d = 0; d < L.k; d++) { const int v = wd[(size_t)o * L.k + d]; wsum += v; wabs += std::abs(v + L.w_off); }
+            const int32_t b = bd ? bd[o] : 0;
+            // the same left-shift bound as the conv blocks
+            if (exponent > 0 && h_left_shift_overflows(wabs, in_off, b, exponent))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d unit %d: requantisation shifts left by %d and (sum|w| * max|x| + |bias|) << %d "
+                            "can pass 2^31 - 1", li, o, exponent, exponent);
+            beff[(size_t)o] = (int32_t)(uint32_t)((int64_t)b + (int64_t)in_off * wsum + (int64_t)L.k * in_off * L.w_off);
+        }
+        const int ks = L.kpad / 64;
+        std::vector<int8_t> frag((size_t)L.upad * L.kpad, 0);
+        for (int o = 0; o < L.units; o++)
+            for (int d = 0; d < L.k; d++) {
+                const int t = o >> 4, s_ = d >> 6, lane = (o & 15) + 16 * ((d & 63) >> 4);
+                frag[(((size_t)t * ks + s_) * 64 + lane) * 16 + (d & 15)] = wd[(size_t)o * L.k + d];
+            }
+        L.lds_off = -1;
+        if (lds_used + (int)frag.size() <= KWS_DENSE_LDS_W) { L.lds_off = lds_used; lds_used += (int)frag.size(); }
+        EI_IMPULSE_ERROR e;
+        if ((e = h->upload(frag, &L.wfrag))) return e;
+        if ((e = h->upload(beff, &L.bias_eff))) return e;
+        D.act_stride = std::max(D.act_stride, ((L.units + 63) & ~63) + 16);
+        D.n_layers++;
+        cur = fc.out[0];
+        k_in = L.units;
+        i++;
+        while (i < m.n.size() && m.n[i].op == OP_RESHAPE && m.n[i].in[0] == cur) {
+            if (!same_quant(cur, m.n[i].out[0])) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "reshape changes quantisation");
+            cur = m.n[i].out[0];
+            i++;
+        }
+    }
+    if (D.n_layers == 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected FULLY_CONNECTED after the conv blocks");
+    const KwsDenseLayer &last = D.l[D.n_layers - 1];
+    if (last.units != N.n_labels || last.units > 48)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "the last FULLY_CONNECTED has %d outputs for %d labels (at most 48)", last.units, N.n_labels);
+    for (int li = 0; li + 1 < D.n_layers; li++) h->pooled_tap_bytes += D.l[li].units;
+    D.lds_w_bytes = lds_used;
+    if (EI_IMPULSE_ERROR e = build_softmax_tables(h, i, cur, &N.sm_exp, &N.sm_valid)) return e;
+    D.sm_exp = N.sm_exp; D.sm_valid = N.sm_valid;
+    N.fc_in = inputs; N.fc_out = 0;                      // the trunk form of kws_nn_kernel sizes its output vector by fc_in; it has no head
+    N.dense = &D; N.handoff = &h->handoff;
+    handoff_init(h, (size_t)inputs);
+    h->n_dense = D.n_layers;
+    if (N.n_blocks > 0 && kws_nn_smem_bytes(N, 4) > 158 * 1024)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "int8 model needs %zu B of LDS in the generic network kernel (at most %d)", kws_nn_smem_bytes(N, 4), 158 * 1024);
+    return EI_IMPULSE_OK;
+}
+
 // Recognise the Edge Impulse 1-D CNN family and fold its per-model constants.
 EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
 {
@@ -376,11 +542,14 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         h->pooled_tap_bytes += k.pool_w * k.out_c;
         N.n_blocks++;
     }
-    if (N.n_blocks == 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "graph does not start with a convolution block");
-    if (N.blk[0].in_w * N.blk[0].in_c != N.n_features) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "first conv does not consume the feature vector");
+    if (N.n_blocks > 0 && N.blk[0].in_w * N.blk[0].in_c != N.n_features) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "first conv does not consume the feature vector");
     for (int b = 0; b + 1 < N.n_blocks; b++)
         if (N.blk[b].pool_w != N.blk[b + 1].in_w || N.blk[b].out_c != N.blk[b + 1].in_c)
             return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv blocks do not chain");
+    // no block, or more than one FULLY_CONNECTED: a dense stack
+    if (h_dense_stack(m, i, N.n_blocks))
+        return build_dense_i8(h, i, cur, N.n_blocks ? N.blk[N.n_blocks - 1].pool_w * N.blk[N.n_blocks - 1].out_c : N.n_features);
+    if (N.n_blocks == 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "graph does not start with a convolution block");
     // FULLY_CONNECTED (fully_connected.cc:322-396)
     if (i < m.n.size() && m.n[i].op == OP_FULLY_CONNECTED && (m.t[m.n[i].in[1]].type != TYPE_I8 || m.t[m.n[i].out[0]].type != TYPE_I8))
         return fail(KWS_ERROR_UNSUPPORTED_MODEL, "FULLY_CONNECTED tensor types");
@@ -418,31 +587,7 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         cur = fc.out[0];
         i++;
     }
-    // SOFTMAX (softmax.cc:187-226): everything but the final reciprocal/rescale depends only on (max - x)
-    if (i >= m.n.size() || m.n[i].op != OP_SOFTMAX || m.n[i].in[0] != cur || m.n[i].out[0] != (int)m.t_out || i + 1 != m.n.size())
-        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected a final SOFTMAX");
-    {
-        const Node &sn = m.n[i];
-        const Tensor &x = m.t[cur];
-        if (tout.scale[0] != 1.f / 256 || tout.zero[0] != -128) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "softmax output quantisation");
-        double rm = (double)sn.beta * (double)x.scale[0] * (double)(1 << (31 - 5));
-        rm = std::min(rm, (double)((1ll << 31) - 1.0));
-        int32_t mult; int left_shift;
-        h_quantize_multiplier(rm, &mult, &left_shift);
-        const double max_in = 1.0 * ((1 << 5) - 1) * (double)(1ll << (31 - 5)) / (double)(1ll << left_shift);
-        const int diff_min = (int)(-1.0 * (double)(int)floor(max_in));
-        std::vector<int32_t> ex(256);
-        std::vector<uint8_t> valid(256);
-        for (int d = 0; d < 256; d++) {
-            const int32_t diff = -d;
-            valid[d] = diff >= diff_min;
-            const int32_t resc = h_srdhm((int32_t)((uint32_t)diff * (1u << left_shift)), mult);
-            ex[d] = valid[d] ? h_exp_neg_q5_26(resc) : 0;
-        }
-        EI_IMPULSE_ERROR e;
-        if ((e = h->upload(ex, &N.sm_exp))) return e;
-        if ((e = h->upload(valid, &N.sm_valid))) return e;
-    }
+    if (EI_IMPULSE_ERROR e = build_softmax_tables(h, i, cur, &N.sm_exp, &N.sm_valid)) return e;
     // the generic kernel keeps every block's weights and ADD tables in LDS: a model that does not fit fails here, at load time,
     // not at its first inference
     if (!kws_nn_uses_mfma(N) && kws_nn_smem_bytes(N, 4) > 158 * 1024)
@@ -556,11 +701,68 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
         kws_nn_f32_pick_blocking(&k);
         N.n_blocks++;
     }
-    if (N.n_blocks == 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "graph does not start with a convolution block");
-    if (N.blk[0].in_w * N.blk[0].in_c != N.n_features) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "first conv does not consume the feature vector");
+    if (N.n_blocks > 0 && N.blk[0].in_w * N.blk[0].in_c != N.n_features) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "first conv does not consume the feature vector");
     for (int b = 0; b + 1 < N.n_blocks; b++)
         if (N.blk[b].pool_w != N.blk[b + 1].in_w || N.blk[b].out_c != N.blk[b + 1].in_c)
             return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv blocks do not chain");
+    if (h_dense_stack(m, i, N.n_blocks)) {
+        // dense stack: fully_connected.h:26-60 per layer, in the reference's order
+        KwsDensePlanF32 &D = h->densef;
+        memset(&D, 0, sizeof(D));
+        D.n_labels = N.n_labels;
+        const int inputs = N.n_blocks ? N.blk[N.n_blocks - 1].pool_w * N.blk[N.n_blocks - 1].out_c : N.n_features;
+        int k_in = inputs;
+        while (i < m.n.size() && m.n[i].op == OP_FULLY_CONNECTED) {
+            const int li = D.n_layers;
+            if (li >= KWS_DENSE_MAX) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "more than %d FULLY_CONNECTED layers", KWS_DENSE_MAX);
+            const Node &fc = m.n[i];
+            if (fc.in[0] != cur) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: input is not the flowing tensor", li);
+            const Tensor &w = m.t[fc.in[1]], &y = m.t[fc.out[0]];
+            const Tensor *bias = (fc.in.size() > 2 && fc.in[2] >= 0) ? &m.t[fc.in[2]] : nullptr;
+            const long units = w.dims[0], k = w.dims[1];
+            if (w.type != TYPE_F32 || y.type != TYPE_F32 || m.t[cur].type != TYPE_F32)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: tensor types", li);
+            if (k != k_in || k > KWS_DENSE_IN_MAX || units < 1 || units > KWS_DENSE_UNITS_MAX || units * k * 4 > KWS_DENSE_W_MAX * 4l || !w.is_const ||
+                (long)w.nbytes != units * k * 4 || (long)w.data.size() < units * k * 4 || y.dims.back() != units || (long)y.nbytes != units * 4)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: weights [%ld][%ld] for %d inputs are outside the kernel's limits (%d units, %d inputs, %d weights)",
+                            li, units, k, k_in, KWS_DENSE_UNITS_MAX, KWS_DENSE_IN_MAX, KWS_DENSE_W_MAX);
+            if (bias && (!bias->is_const || bias->type != TYPE_F32 || (long)bias->nbytes != units * 4 || (long)bias->data.size() < units * 4))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: bias", li);
+            if (fc.p[0] < 0 || fc.p[0] > 3) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: fused activation %d", li, fc.p[0]);
+            KwsDenseLayerF32 &L = D.l[li];
+            L.k = (int)k; L.units = (int)units;
+            h_act_range_f32(fc.p[0], &L.lo, &L.hi);
+            std::vector<float> wv = floats(w), bv((size_t)units, 0.0f);
+            if (bias) bv = floats(*bias);
+            EI_IMPULSE_ERROR e;
+            if ((e = h->upload(wv, &L.w))) return e;
+            if ((e = h->upload(bv, &L.bias))) return e;
+            D.buf_floats[li & 1] = std::max(D.buf_floats[li & 1], L.units);
+            D.n_layers++;
+            cur = fc.out[0];
+            k_in = L.units;
+            i++;
+            skip_reshapes();
+        }
+        const KwsDenseLayerF32 &last = D.l[D.n_layers - 1];
+        if (last.units != N.n_labels || last.units > 48)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "the last FULLY_CONNECTED has %d outputs for %d labels (at most 48)", last.units, N.n_labels);
+        if (i >= m.n.size() || m.n[i].op != OP_SOFTMAX || m.n[i].in[0] != cur || m.n[i].out[0] != (int)m.t_out || i + 1 != m.n.size())
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected a final SOFTMAX");
+        N.beta = D.beta = m.n[i].beta;
+        N.fc_in = inputs; N.fc_out = 0;                  // the trunk form of kws_nn_f32_kernel sizes its output vector by fc_in; it has no head
+        N.dense = &D; N.handoff = &h->handoff;
+        handoff_init(h, sizeof(float) * (size_t)inputs);
+        h->n_dense = D.n_layers;
+        if (N.n_blocks > 0 && kws_nn_f32_smem_bytes(N, 4) > 150 * 1024) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "float model too large for the kernel's LDS budget");
+        void *d = nullptr;
+        HIP_TRY(hipMalloc(&d, sizeof(KwsNnPlanF32)));
+        h->dev_allocs.push_back(d);
+        HIP_TRY(hipMemcpy(d, &N, sizeof(KwsNnPlanF32), hipMemcpyHostToDevice));
+        h->d_nnf = (const KwsNnPlanF32 *)d;
+        return EI_IMPULSE_OK;
+    }
+    if (N.n_blocks == 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "graph does not start with a convolution block");
     if (i >= m.n.size() || m.n[i].op != OP_FULLY_CONNECTED || m.n[i].in[0] != cur)
         return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected FULLY_CONNECTED after the conv blocks");
     {

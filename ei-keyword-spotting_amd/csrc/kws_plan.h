@@ -92,14 +92,57 @@ struct KwsConvBlock {
 #define KWS_FC_IN_MAX 1024
 #define KWS_FC_W_MAX 32768
 
+// Dense stacks: graphs that end in 2 .. 4 FULLY_CONNECTED layers, or whose FULLY_CONNECTED layers (1 .. 4) follow no conv block.  kws_dense_i8_kernel / kws_dense_f32_kernel run the whole chain for a tile of clips; conv blocks in front of it run in the trunk form of
+// the generic kernels, which stops at the last block's output ([clips][inputs] in HBM, KwsHandoff).
+#define KWS_DENSE_MAX 4
+#define KWS_DENSE_UNITS_MAX 256            // a hidden layer's units (the last layer: labels <= 48)
+#define KWS_DENSE_IN_MAX 4096              // inputs of the first layer
+#define KWS_DENSE_W_MAX (1 << 20)          // bytes of weights per layer
+#define KWS_DENSE_LDS_W (64 * 1024)        // int8: fragment bytes kept in LDS (layers that do not fit are read from L2)
+struct KwsDenseLayer {
+    int k, kpad;               // inputs, padded to the matrix instruction's 64
+    int units, upad;           // outputs, padded to a 16-column tile
+    int w_off;                 // -weight zero point: w_off * sum(x) is added per clip
+    int out_zp, mult, shift, act_min, act_max;
+    int lds_off;               // byte offset of the fragments in the workgroup's LDS block, or -1: read from L2
+    const int8_t *wfrag;       // [upad / 16][kpad / 64][64 lanes][16]: lane l holds w[16 t + (l & 15)][64 s + 16 (l >> 4) .. + 15], zero padded
+    const int32_t *bias_eff;   // [upad] bias + in_off * sum(w) + k * in_off * w_off
+};
+struct KwsDensePlan {
+    int n_layers, n_labels;
+    int lds_w_bytes;           // fragments staged in LDS
+    int act_stride;            // bytes per clip row of the per-wave activation buffers (a multiple of 16 that is no multiple of 64)
+    int tap_off;               // where the hidden layers' outputs start in a clip's tap_pooled row (= the conv blocks' pooled bytes)
+    KwsDenseLayer l[KWS_DENSE_MAX];
+    const int32_t *sm_exp;     // as KwsNnPlan
+    const uint8_t *sm_valid;
+    float out_scale;
+    int out_zp;
+};
+struct KwsDenseLayerF32 {
+    int k, units;
+    float lo, hi;              // fused activation range
+    const float *w;            // [units][k]
+    const float *bias;         // [units] (zeros where the node has none: the reference adds 0.0f)
+};
+struct KwsDensePlanF32 {
+    int n_layers, n_labels;
+    float beta;
+    int buf_floats[2];         // per clip: the widest output of the even / odd layers
+    KwsDenseLayerF32 l[KWS_DENSE_MAX];
+};
+struct KwsHandoff;             // kws_plan.cpp: the trunk's output buffers, one per stream
+
 struct KwsNnPlan {
     int n_blocks;
     KwsConvBlock blk[KWS_MAX_BLOCKS];
     int n_features;            // 637
     int fc_in, fc_out;
     int fc_in_off, fc_w_off, fc_out_zp, fc_mult, fc_shift, fc_act_min, fc_act_max;
-    const int8_t *fc_w;        // [fc_out][fc_in]
-    const int32_t *fc_bias;    // [fc_out]
+    // fc_out == 0: the graph ends in a dense stack, not in the head above; the head's two pointers then name the stack's plan and the trunk's hand-off
+    // buffers (host pointers, owned by the handle) -- kws_nn_dense().  A union, so that the struct the existing kernels take by value keeps its layout.
+    union { const int8_t *fc_w; const KwsDensePlan *dense; };          // fc_w: [fc_out][fc_in]
+    union { const int32_t *fc_bias; KwsHandoff *handoff; };            // fc_bias: [fc_out]
     // softmax (int8 -> int8): exp LUT indexed by (max - x) in [0,255]; 0 where diff < diff_min
     const int32_t *sm_exp;     // [256] exp_on_negative_values(rescaled diff), Q0.31
     const uint8_t *sm_valid;   // [256] diff >= diff_min
@@ -109,6 +152,7 @@ struct KwsNnPlan {
     int out_zp;
     int n_labels;
 };
+static inline const KwsDensePlan *kws_nn_dense(const KwsNnPlan &N) { return N.fc_out == 0 ? N.dense : nullptr; }
 
 // ---- float32 models (the reference's float TFLite-Micro kernels: reference/conv.h:28-99, add.h:179-215,
 //      pooling.h:189-237, fully_connected.h:26-60, softmax.h:31-63) -------------------------------------------
@@ -135,6 +179,17 @@ struct KwsNnPlanF32 {
     KwsConvBlockF32 blk[KWS_MAX_BLOCKS];
     int n_features, fc_in, fc_out, n_labels;
     float fc_min, fc_max, beta;
-    const float *fc_w;             // [fc_out][fc_in]
-    const float *fc_bias;          // [fc_out]
+    union { const float *fc_w; const KwsDensePlanF32 *dense; };       // [fc_out][fc_in]; fc_out == 0: as KwsNnPlan (kws_nnf_dense())
+    union { const float *fc_bias; KwsHandoff *handoff; };             // [fc_out]
 };
+static inline const KwsDensePlanF32 *kws_nnf_dense(const KwsNnPlanF32 &N) { return N.fc_out == 0 ? N.dense : nullptr; }
+// the trunk's output [clips][inputs] for one chunk of clips, per stream (launches on different streams may overlap); allocated on first use, freed with
+// the handle
+#define KWS_HANDOFF_SETS 8
+#define KWS_HANDOFF_BYTES (16u << 20)
+struct KwsHandoff {
+    struct { void *stream; void *buf; int used; } set[KWS_HANDOFF_SETS];
+    int next;
+    size_t bytes;              // of every buffer: KWS_HANDOFF_BYTES (the development build reads KWS_DEV_HANDOFF_BYTES at kws_create: tests that walk several chunks)
+};
+void *kws_handoff_for(KwsHandoff *H, void *stream);      // kws_plan.cpp; NULL when the allocation fails

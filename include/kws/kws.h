@@ -43,7 +43,20 @@ int kws_feature_count(const kws_handle *h);              /* EI_CLASSIFIER_NN_INP
 int kws_clip_samples(const kws_handle *h);               /* EI_CLASSIFIER_RAW_SAMPLE_COUNT */
 int kws_frame_count(const kws_handle *h);                /* MFCC rows (49) */
 int kws_filter_count(const kws_handle *h);               /* mel filters of the DSP block (32) */
-int kws_pooled_tap_bytes(const kws_handle *h);           /* bytes/clip of the pooled-activation tap */
+int kws_pooled_tap_bytes(const kws_handle *h);           /* bytes/clip of the pooled-activation tap (hidden dense layers' outputs included) */
+int kws_dense_layer_count(const kws_handle *h);          /* FULLY_CONNECTED layers of the graph: 1 for the conv family with its single head, 1 .. 4 for a dense
+                                                            stack ([RESHAPE]* . 0 .. 8 conv blocks . 1 .. 4 FULLY_CONNECTED . SOFTMAX; hidden layers of 1 .. 256
+                                                            units with any fused activation, with or without bias; at most 4096 inputs and 1 MiB of weights per
+                                                            layer; the last layer's outputs are the labels, at most 48; behind conv blocks a stack has at
+                                                            least two layers -- a single FULLY_CONNECTED there keeps the conv kernels' head limits).  Such graphs run on kws_dense_i8_kernel /
+                                                            kws_dense_f32_kernel; a float32 one has no KWS_MODE_FAST (kws_set_mode: KWS_ERROR_UNSUPPORTED_MODEL).
+                                                            Conv blocks in front of a stack hand their output over through a 16 MiB device buffer PER STREAM
+                                                            (allocated at a stream's first such call, kept until kws_destroy, at most 8: 128 MiB per handle); a
+                                                            larger batch is walked in chunks of that size.  Limits that follow: concurrent calls on one handle
+                                                            must use different streams (two threads on ONE stream would share its buffer), and a handle serves
+                                                            at most 8 streams without waiting -- a ninth takes over the oldest buffer after a device
+                                                            synchronise, which is only safe when no other thread is inside a call on that handle.  Graphs
+                                                            without a dense stack, and dense-only graphs, use no such buffer */
 const char *kws_nn_kernel_name(const kws_handle *h);    /* which network kernel serves this model (diagnostics) */
 const char *kws_mfcc_kernel_name(const kws_handle *h);  /* the spectral kernel of int16 batches, MFCC and MFE blocks alike: "kws_mfcc8_kernel" / "kws_mfcc_kernel" (tuned shapes), "kws_mfcc8_kernel (chunked)" (general plans whose spectral stage fits the tuned kernel: chunks of at most 49 frames), "kws_spectral_lds_kernel" (general shapes), "kws_spectral_generic_kernel" (those whose arrays exceed the LDS) */
 int kws_model_is_float(const kws_handle *h);             /* 1: float32 graph (EI_CLASSIFIER_TFLITE_INPUT_QUANTIZED == 0) */
@@ -199,8 +212,9 @@ EI_IMPULSE_ERROR kws_extract_mfcc_batch_device(kws_handle *h, const int16_t *pcm
 EI_IMPULSE_ERROR kws_run_inference_batch_device(kws_handle *h, const float *features, size_t B, float *scores,
                                                 void *stream);
 /* network only, from int8 input tensors; optional int8 taps (device, may be NULL):
- *   tap_pooled [B][kws_pooled_tap_bytes]  every MAX_POOL_2D output, in graph order
- *   tap_fc     [B][label_count]           FULLY_CONNECTED output
+ *   tap_pooled [B][kws_pooled_tap_bytes]  every MAX_POOL_2D output, in graph order; behind them the int8 output of every hidden
+ *                                         FULLY_CONNECTED layer of a dense stack, in graph order
+ *   tap_fc     [B][label_count]           output of the (last) FULLY_CONNECTED
  *   tap_out    [B][label_count]           SOFTMAX output                                         */
 EI_IMPULSE_ERROR kws_nn_batch_device(kws_handle *h, const int8_t *q_in, size_t B, float *scores, int8_t *tap_pooled,
                                      int8_t *tap_fc, int8_t *tap_out, void *stream);

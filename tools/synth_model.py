@@ -42,8 +42,8 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
     RESHAPE only renames axes in this graph family.  Returns {tensor id: value}; stops before the first node whose op is stop_before_op."""
     act = {t_in: np.asarray(x, np.float64)}
 
-    def fused(v, a):                                    # TfLiteFusedActivation: 0 none, 1 relu, 3 relu6
-        return v if a == 0 else np.maximum(v, 0.0) if a == 1 else np.clip(v, 0.0, 6.0)
+    def fused(v, a):                                    # TfLiteFusedActivation: 0 none, 1 relu, 2 relu_n1_to_1, 3 relu6
+        return v if a == 0 else np.maximum(v, 0.0) if a == 1 else np.clip(v, -1.0, 1.0) if a == 2 else np.clip(v, 0.0, 6.0)
 
     def windows(v, size, out_w, stride, pad_left):      # [n][out_w][size][c], rows outside the image = NaN (callers mask them)
         n, w, c = v.shape
@@ -87,7 +87,8 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
             g, ok = windows(a, size, out_w, stride, pad_left)
             act[o] = fused(np.where(ok[None, :, :, None], g, -np.inf).max(axis=2), p[5])
         elif nd["op"] == 4:                             # FULLY_CONNECTED
-            act[o] = fused(a @ const[nd["in"][1]].T + const[nd["in"][2]], p[0])
+            bias = const[nd["in"][2]] if len(nd["in"]) > 2 and nd["in"][2] >= 0 else 0.0          # FULLY_CONNECTED's bias is optional
+            act[o] = fused(a @ const[nd["in"][1]].T + bias, p[0])
         elif nd["op"] == 5:                             # SOFTMAX
             e = np.exp((a - a.max(axis=1, keepdims=True)) * nd["beta"])
             act[o] = e / e.sum(axis=1, keepdims=True)
@@ -117,7 +118,7 @@ def calibrate_ranges(tensors, nodes, t_in, x):
         tensors[o]["scale"], tensors[o]["zero"] = [sc], [int(np.clip(round(-128 - lo / sc), -128, 127))]
 
     def before(nd):                                     # the bias of a node whose input scale has just been settled
-        if nd["op"] not in (1, 4, 6):
+        if nd["op"] not in (1, 4, 6) or len(nd["in"]) < 3 or nd["in"][2] < 0:
             return
         tb, tw, i0 = nd["in"][2], nd["in"][1], nd["in"][0]
         old = np.frombuffer(tensors[tb]["data"], np.int32).astype(np.float64) * np.float64(tensors[tb]["scale"])
@@ -134,7 +135,26 @@ def calibrate_ranges(tensors, nodes, t_in, x):
         act[nd["out"][0]] = sub[nd["out"][0]]
 
 
-def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=256):
+def calibrate_hidden(tensors, nodes, t_in, hidden, x, lift=0.7):
+    """Hidden FULLY_CONNECTED layers of a synthetic dense stack (synth_model_blob's dense=): as drawn, a layer's pre-activations have zero mean over
+    the inputs, so a ReLU parks half of its outputs on the clamp bound, and the drawn output scale saturates the rest -- every clip then produces the
+    same tensor and a test on such a graph proves nothing.  Layer by layer, on the calibration set x: the activation ranges in front of the layer are
+    settled (calibrate_ranges), then every unit's int32 bias is set so that its float twin's pre-activation has mean lift x its own deviation (about a
+    quarter of the outputs below zero).  The layer's own output range is settled by the calibrate_ranges pass that follows (calibrate_head)."""
+    for fc in hidden:
+        idx = nodes.index(fc)
+        calibrate_ranges(tensors, nodes[:idx], t_in, x)
+        a = float_forward(tensors, nodes[:idx], t_in, x)[fc["in"][0]]
+        tw, tb = fc["in"][1], fc["in"][2]
+        z = a.reshape(a.shape[0], -1) @ dequantised_constants(tensors)[tw].T
+        b_scale = float(np.float32(tensors[fc["in"][0]]["scale"][0]) * np.float32(tensors[tw]["scale"][0]))
+        bias = np.round((lift * z.std(axis=0) - z.mean(axis=0)) / b_scale).astype(np.int64)
+        assert np.abs(bias).max() < 2 ** 31
+        tensors[tb]["scale"] = [b_scale]
+        tensors[tb]["data"] = bias.astype(np.int32).tobytes()
+
+
+def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=256, x=None):
     """Give a synthetic graph a head with a sane logit scale (synth_model_blob's logit_std).  The network's input is cmvnw's output:
     every column standardised over its window -- so the calibration set is n_cal matrices of independent N(0, 1) values (measured: the
     logit statistics on those equal the ones on the bench's synthetic clips to a few percent).  With z = W x the float twin's
@@ -142,10 +162,11 @@ def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=2
     int32 biases become round(-class mean / bias scale) + the drawn ones, and the output tensor's scale spans +-8 logit_std."""
     rng = np.random.default_rng(100000 + seed)
     F = tensors[t_in]["dims"][1]
-    x = rng.standard_normal((n_cal, F))
-    fc = [nd for nd in nodes if nd["op"] == 4][0]
+    if x is None:
+        x = rng.standard_normal((n_cal, F))
+    fc = [nd for nd in nodes if nd["op"] == 4][-1]          # the head: the last FULLY_CONNECTED (the only one without dense=)
     calibrate_ranges(tensors, nodes, t_in, x)
-    feat = float_forward(tensors, nodes, t_in, x, stop_before_op=4)[fc["in"][0]]
+    feat = float_forward(tensors, nodes[:nodes.index(fc)], t_in, x)[fc["in"][0]]
     w = dequantised_constants(tensors)[tfw]
     z = feat @ w.T
     mean = z.mean(axis=0)
@@ -163,7 +184,8 @@ def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=2
 
 def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((30, 7, 7), (10, 7, 7)), n_labels=4,
                      conv_bias=False, add_bias=True, num_filters=32, raw_samples=16000, fft_length=256, frame_length=0.02,
-                     frame_stride=0.02, pre_cof=0.98, dsp_block="mfcc", logit_std=None, quantize_filterbank=False, edit=None):
+                     frame_stride=0.02, pre_cof=0.98, dsp_block="mfcc", logit_std=None, quantize_filterbank=False, edit=None, dense=None,
+                     calib=None):
     """blocks: sequence of
          (out_channels, taps, pool)              CONV_2D 1xK (+ optional int32 bias) -> ADD(int8 per-channel)+ReLU -> MAX_POOL
          ("dw", depth_mult, taps, pool, act)     DEPTHWISE_CONV_2D 1xK with int32 bias and fused activation -> MAX_POOL
@@ -176,6 +198,10 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
        impulse's is 1.5).  No random draw is added or removed: every other tensor is the one the same seed gave before.
        Frame geometry defaults to the shipped one (1 s at 16 kHz, 20 ms frames and stride: 49 frames); raw_samples / frame_length /
        frame_stride / fft_length / pre_cof change the DSP block (the frame count follows speechpy's rule, processing.hpp:260-284).
+       blocks=() is a dense-only classifier on the feature matrix.  dense: None, or a sequence of (units, act) -- hidden FULLY_CONNECTED layers (int32
+       bias, fused activation act) between the flattened output of the last block and the head.  A graph with hidden layers is always calibrated
+       (calibrate_hidden, then calibrate_head with logit_std or 1.5) on standardised random feature matrices, or on calib ([n][features]) where the
+       DSP block's output is not of that kind (the MFE block's).  With dense=None every blob is the one the same arguments gave before.
        edit: a callable edit(tensors, nodes) run on the finished graph just before it is serialised -- the way to any quantisation
        parameter, constant or node option outside the drawn bands (tests/kws_testlib.py QUANT_EDGES).  It draws nothing from the
        model's generator: with edit=None every blob is the one the same arguments gave before."""
@@ -290,6 +316,17 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
     fc_in = w * c
     tf = T(9, [1, fc_in], scale=[cur_scale], zero=[cur_zp])
     node(0, [cur, shape_const([1, fc_in])], [tf])
+    hidden = []
+    for units, act in (dense or ()):
+        hw = rng.integers(-127, 128, (units, fc_in)).astype(np.int8)
+        hw_scale = rscale(0.002, 0.01)
+        thw = T(9, [units, fc_in], True, [hw_scale], [0], hw.tobytes())
+        thb = T(2, [units], True, [cur_scale * hw_scale], [0], rng.integers(-400, 400, units).astype(np.int32).tobytes())
+        cur_scale, cur_zp = rscale(0.03, 0.12), (-128 if act in (1, 3) else int(rng.integers(-30, 40)))
+        tho = T(9, [1, units], scale=[cur_scale], zero=[cur_zp])
+        node(4, [tf, thw, thb], [tho], [act])
+        hidden.append(nodes[-1])
+        tf, fc_in = tho, units
     fw = rng.integers(-127, 128, (n_labels, fc_in)).astype(np.int8)
     fw_scale = rscale(0.005, 0.02)
     tfw = T(9, [n_labels, fc_in], True, [fw_scale], [0], fw.tobytes())
@@ -298,8 +335,12 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
     node(4, [tf, tfw, tfb], [tfo], [0])
     tso = T(9, [1, n_labels], scale=[0.00390625], zero=[-128])
     node(5, [tfo], [tso], beta=1.0)
-    if logit_std is not None:
-        calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, float(logit_std), seed)
+    if hidden:
+        xc = np.random.default_rng(200000 + seed).standard_normal((256, F)) if calib is None else np.asarray(calib, np.float64)
+        calibrate_hidden(tensors, nodes, t_in, hidden, xc)
+        calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, 1.5 if logit_std is None else float(logit_std), seed, x=xc)
+    elif logit_std is not None:
+        calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, float(logit_std), seed, x=calib)
     if edit is not None:
         edit(tensors, nodes)
     meta = {"labels": ["label%d" % i for i in range(n_labels)],
@@ -322,11 +363,13 @@ def main():
     ap.add_argument("--high", type=int, default=4000)
     ap.add_argument("--labels", type=int, default=4)
     ap.add_argument("--blocks", default="30,7,7;10,7,7", help="per block: out_channels,taps,pool | dw,depth_mult,taps,pool,act | pw,out_channels,act")
+    ap.add_argument("--dense", default="", help="hidden FULLY_CONNECTED layers in front of the head: units,act;units,act (act: 0 none, 1 relu, 2 relu_n1_to_1, 3 relu6)")
     ap.add_argument("--logit-std", type=float, default=None, help="calibrate the head: zero-mean class logits of this pooled deviation on standardised features")
     a = ap.parse_args()
-    blocks = tuple(tuple(v if v in ("dw", "pw") else int(v) for v in b.split(",")) for b in a.blocks.split(";"))
+    blocks = tuple(tuple(v if v in ("dw", "pw") else int(v) for v in b.split(",")) for b in a.blocks.split(";") if b)      # --blocks "": dense only
+    dense = tuple(tuple(int(v) for v in d.split(",")) for d in a.dense.split(";") if d) or None
     blob = synth_model_blob(a.seed, ncep=a.ncep, win_size=a.win_size, low=a.low, high=a.high, blocks=blocks,
-                            n_labels=a.labels, num_filters=a.num_filters, logit_std=a.logit_std)
+                            n_labels=a.labels, num_filters=a.num_filters, logit_std=a.logit_std, dense=dense)
     with open(a.out, "wb") as f:
         f.write(blob)
     print(a.out, len(blob), "bytes")
