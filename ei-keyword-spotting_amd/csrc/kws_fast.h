@@ -20,6 +20,7 @@
 
 #include "kws_plan.h"
 #include "kws_split22.h"
+#include "kws_fast_scale.h"
 
 #define KWS_FAST_MAX_BLOCKS 8        // conv / depthwise / pointwise blocks of a fused float32 graph (= KWS_MAX_BLOCKS)
 #define KWS_FAST_NZ_MAX 12        // longest mel filter (filters 0..31) kept in registers

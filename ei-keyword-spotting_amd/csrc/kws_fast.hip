@@ -21,6 +21,7 @@
 
 #include "kws_device.h"
 #include "kws_fast.h"
+#include "kws_bfly_m2k1.h"
 // The second compilation of this file (kws_fast_w3.o, -DKWS_FAST_WPS=3: three waves per SIMD, <= 168 registers, the float32-network forms only) goes into the
 // same library under names of its own; the launchers of the first one hand a plan laid out for three waves (KwsFastPlan::wps) over to them.
 #if KWS_FAST_WPS >= 3
@@ -1099,8 +1100,9 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
     const float *dct_frag = shared + FP.dct_off;
     const int pstride = FP.pstride;
     const int n_waves = blockDim.x >> 6;
-    // 1 / fft_length, the int16 scale 2^-15 squared and the split's two halvings: powers of two (the plan checks fft_length)
-    const float pre_cof = P.pre_cof, pscale = P.inv_fft * (1.0f / 1073741824.0f) * 0.25f;
+    // 1 / fft_length, the int16 scale 2^-15 squared and the split's two halvings: a power of two (the plan checks fft_length).  It is NOT applied per bin: the
+    // power rows are unscaled, the plan uploads the mel tap weights multiplied by it, and a frame's energy takes it once behind its reduction (kws_fast_scale.h)
+    const float pre_cof = P.pre_cof, pscale = kws_fast_pscale(P.inv_fft);
     const int frame_stride = P.frame_stride, n_samples = P.n_samples;
     const float *cnt_tab = shared + FP.cnt_off;
     const int *upd_tab = (const int *)(shared + FP.upd_off);
@@ -1167,7 +1169,9 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         const int fl = lane_c & 7, fg = lane_c >> 3;
         // blocks fl (output positions 8 fl ..) and fl + 8: block j = 4 i1 + i2 reads input points i1 + 4 i2 + 16 i3 + 64 i4
         const int nbA = (fl >> 2) + 4 * (fl & 3);
-        const cf a1 = to_cf(P.tw[16]), a2 = to_cf(P.tw[32]), a3 = to_cf(P.tw[48]);
+        // the m = 2 level's k = 1 twiddles tw[16] = (c, -c), tw[32] = (e, -1), tw[48] = (-c, -c): their butterfly needs c and e only (kws_bfly_m2k1.h; the plan
+        // has checked the table's bit patterns)
+        const float a_c = P.tw[16].x, a_e = P.tw[32].x;
         const cf b1 = to_cf(P.tw[4 * fl]), b2 = to_cf(P.tw[8 * fl]), b3 = to_cf(P.tw[12 * fl]);
 #if KWS_FAST_WPS >= 3
         // (three waves per SIMD: the last level's twiddles and the split's are read from the workgroup's LDS table in every pass, KwsFastPlan::twl_off)
@@ -1345,7 +1349,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { sm[i] = cadd(z[blk][2 * i], z[blk][2 * i + 1]); df[i] = csub(z[blk][2 * i], z[blk][2 * i + 1]); }
                     bfly4_unit(sm[0], sm[1], sm[2], sm[3]);
-                    bfly4(df[0], df[1], df[2], df[3], a1, a2, a3);
+                    bfly4_m2k1(df[0], df[1], df[2], df[3], a_c, a_e);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { z[blk][2 * i] = sm[i]; z[blk][2 * i + 1] = df[i]; }
                 }
@@ -1414,13 +1418,13 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                     cf fpnk; fpnk.r = other.r; fpnk.i = -other.i;
                     const cf f1k = cadd(fpk, fpnk), f2k = csub(fpk, fpnk);
                     const cf twv = cmul(f2k, stw[qq]);
-                    cf lo, hi;                                       // twice the reference's: the halving is part of pscale
+                    cf lo, hi;                                       // twice the reference's: the halving is part of pscale (which the mel weights carry)
                     lo.r = f1k.r + twv.r;
                     lo.i = f1k.i + twv.i;
                     hi.r = f1k.r - twv.r;
                     hi.i = twv.i - f1k.i;
-                    const float plo = __fmaf_rn(lo.r, lo.r, lo.i * lo.i) * pscale;
-                    const float phi = __fmaf_rn(hi.r, hi.r, hi.i * hi.i) * pscale;
+                    const float plo = __fmaf_rn(lo.r, lo.r, lo.i * lo.i);
+                    const float phi = __fmaf_rn(hi.r, hi.r, hi.i * hi.i);
                     // bin 64 is written twice by the reference and the second store wins: same order here; its first value is not
                     // part of the frame energy
                     prow[k] = plo;
@@ -1430,17 +1434,12 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                 }
                 if (fl == 0) {                                       // tmp[0]: DC and Nyquist bins (kiss_fftr.cpp:84-96)
                     const float dc = u[0][0].r + u[0][0].i, ny = u[0][0].r - u[0][0].i;
-#if KWS_FAST_WPS >= 3
-                    // (4 pscale would live in a vector register through the pass loop and come back from scratch here; both factors are powers of two: the same bits)
-                    const float pdc = ((dc * dc) * pscale) * 4.0f, pny = ((ny * ny) * pscale) * 4.0f;
-#else
-                    const float pdc = (dc * dc) * (4.0f * pscale), pny = (ny * ny) * (4.0f * pscale);
-#endif
+                    const float pdc = (dc * dc) * 4.0f, pny = (ny * ny) * 4.0f;      // (unscaled like every bin)
                     esum += pdc + pny;
                     prow[0] = pdc;
                 }
                 // frame energy (feature.hpp:289-298): its log is parked until the DCT has run
-                esum = oct_sum(esum);
+                esum = oct_sum(esum) * pscale;                       // the power rows are unscaled: the energy takes the scale once
                 if (fl == 0 && live) elog[f] = fast_log(esum == 0.0f ? FLT_EPSILON : esum);
             }
             FPH(2);
@@ -1534,13 +1533,13 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                     cf fpnk; fpnk.r = fq[rep].r; fpnk.i = -fq[rep].i;
                     const cf f1k = cadd(fpk[rep], fpnk), f2k = csub(fpk[rep], fpnk);
                     const cf twv = cmul(f2k, stw_);
-                    cf lo, hi;                                       // twice the reference's: the halving is part of pscale
+                    cf lo, hi;                                       // twice the reference's: the halving is part of pscale (which the mel weights carry)
                     lo.r = f1k.r + twv.r;
                     lo.i = f1k.i + twv.i;
                     hi.r = f1k.r - twv.r;
                     hi.i = twv.i - f1k.i;
-                    const float plo = __fmaf_rn(lo.r, lo.r, lo.i * lo.i) * pscale;
-                    const float phi = __fmaf_rn(hi.r, hi.r, hi.i * hi.i) * pscale;
+                    const float plo = __fmaf_rn(lo.r, lo.r, lo.i * lo.i);
+                    const float phi = __fmaf_rn(hi.r, hi.r, hi.i * hi.i);
                     if (k != KWS_NC / 2) {                           // bin 64 is written twice by the reference: the second store wins
                         esum += plo;
                         prow[k] = plo;
@@ -1550,11 +1549,11 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                 }
                 if (t == 0) {
                     const float dc = d0.x + d0.y, ny = d0.x - d0.y;
-                    const float pdc = (dc * dc) * (4.0f * pscale), pny = (ny * ny) * (4.0f * pscale);
+                    const float pdc = (dc * dc) * 4.0f, pny = (ny * ny) * 4.0f;
                     esum += pdc + pny;
                     prow[0] = pdc;
                 }
-                esum = half_wave_sum(esum);
+                esum = half_wave_sum(esum) * pscale;
                 if (t == 0 && live_t) *((pair_tail && half == 1) ? stash + 47 : elog + ft) = fast_log(esum == 0.0f ? FLT_EPSILON : esum);
             }
             // frame slot 1 of a paired pass belongs to the next clip: its row goes to the stash instead of image row n_frames

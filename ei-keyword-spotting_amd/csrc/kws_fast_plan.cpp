@@ -1,6 +1,7 @@
 // kws_fast_plan.cpp -- tables and LDS layout of KWS_MODE_FAST (kws_fast.h).  Like kws_plan.cpp: everything that does not depend on
 // the audio is computed once per model on the host and uploaded.
 #include "kws_internal.h"
+#include "kws_bfly_m2k1.h"
 #include <atomic>
 #include <cstdlib>
 
@@ -268,6 +269,14 @@ static EI_IMPULSE_ERROR build_fast_dsp(kws_handle *h, KwsFastPlan &F, std::vecto
     if (P.generic) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode serves the configurations of the tuned MFCC kernel (fft 256, 32 / 40 filters, "
                                                             "up to 52 aligned frames); this model runs on the general kernels");
     if (c.fft_length != 256) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: fft_length %d (kernel is built for 256)", c.fft_length);
+    {
+        // the pass loop's m = 2, k = 1 butterflies are written for the bit patterns of KissFFT's table (kws_bfly_m2k1.h): a table without them must not reach it
+        std::vector<float2> tw;
+        h_twiddles(c.fft_length / 2, tw);
+        if (!kws_bfly_m2k1_table_ok(tw[16].x, tw[16].y, tw[32].x, tw[32].y, tw[48].x, tw[48].y))
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: the FFT's twiddle table does not hold (c, -c), (e, -1), (-c, -c) at 16, 32, 48 (bit patterns %a %a, %a %a, %a %a)",
+                        (double)tw[16].x, (double)tw[16].y, (double)tw[32].x, (double)tw[32].y, (double)tw[48].x, (double)tw[48].y);
+    }
     if (NF != 32 && NF != 40) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: %d mel filters (the kernel is instantiated for 32 and 40)", NF);
     // cmvnw row/column split: 16 columns x 4 groups of 13 rows, or 20 columns x 3 groups of 17 rows
     // (the three-waves-per-SIMD build holds 13 rows per lane whatever the column count: 40 columns take three passes of 16)
@@ -326,6 +335,13 @@ static EI_IMPULSE_ERROR build_fast_dsp(kws_handle *h, KwsFastPlan &F, std::vecto
     std::vector<float> tw1, tw2;
     tap_table([&](int lane) { return lane & 31; }, KWS_FAST_NZ_MAX, s1, tw1);
     tap_table([&](int lane) { return F.nf2p ? 32 + (lane & (F.nf2p - 1)) : -1; }, KWS_FAST_NZ2, s2, tw2);
+    // The kernel's power rows are unscaled: the weights carry the power spectrum's scale, a power of two -- the same bits as scaling every bin
+    // (kws_fast_scale.h).  Only these two uploads are scaled: `taps` and everything else the host derives from the filterbank keep the reference's weights.
+    {
+        const float pscale = kws_fast_pscale(P.inv_fft);
+        if (kws_fast_scale_taps(tw1.data(), tw1.size(), pscale) + kws_fast_scale_taps(tw2.data(), tw2.size(), pscale) != 0)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a mel weight times the power scale %g is subnormal", (double)pscale);
+    }
 
     // ---- DCT-II operand fragments (numpy.hpp:378-401: X[n] = 2 sum_k x[k] cos(pi n (2k+1) / 2N), ortho scale) -----------
     F.dct_groups = NF / 8;

@@ -61,7 +61,7 @@ def main():
                     _, name, ms = ln.split()
                     res.setdefault((name, v), []).append(float(ms))
     for name in models.split(","):
-        print(name, "  ".join("%s %.4f ms (%s)" % (v, sorted(res.get((name, v), [0]))[len(res.get((name, v), [0])) // 2], " ".join("%.3f" % x for x in res.get((name, v), []))) for v in variants))
+        print(name, "  ".join("%s %.4f ms (%s)" % (v, sorted(res.get((name, v), [0]))[len(res.get((name, v), [0])) // 2], " ".join("%.4f" % x for x in res.get((name, v), []))) for v in variants))
 
 
 if __name__ == "__main__":
