@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = [
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_slide_live_create", "kws_slide_live_destroy", "kws_slide_live_path", "kws_slide_live_reset", "kws_slide_live_window_count",
     "kws_slide_live_push_device",
-    "kws_extract_mfe_batch_device", "kws_set_mode", "kws_get_mode", "kws_fast_is_fused", "kws_fast_fallback_count", "kws_fast_exact_count", "kws_fast_guard",
+    "kws_extract_mfe_batch_device", "kws_set_mode", "kws_get_mode", "kws_fast_is_fused", "kws_fast_lds_fragments", "kws_fast_fallback_count", "kws_fast_exact_count", "kws_fast_guard",
     "kws_set_logits_tap", "kws_fast_gain", "kws_fast_tolerance_info",
     "kws_comm_unique_id", "kws_comm_create", "kws_comm_world_size", "kws_comm_rank", "kws_comm_ranks_seen", "kws_comm_rccl_version", "kws_comm_wait", "kws_allgather_scores", "kws_comm_destroy",
     "kws_wav_info_from_memory", "kws_wav_decode_mono", "kws_resample_length", "kws_resample_device", "kws_resample_device_ex",
@@ -130,6 +130,8 @@ def lib():
         L.kws_set_mode.argtypes = [vp, i32]
         L.kws_get_mode.argtypes = [vp]
         L.kws_fast_is_fused.argtypes = [vp]
+        if hasattr(L, "kws_fast_lds_fragments"):         # absent from older builds compared in tools/ab_rate.py
+            L.kws_fast_lds_fragments.argtypes = [vp]
         L.kws_fast_fallback_count.argtypes = [vp, C.POINTER(sz)]
         if hasattr(L, "kws_fast_guard"):                 # absent from older builds compared in tools/ab_rate.py
             L.kws_fast_guard.argtypes = [vp, i32, vp]
@@ -292,6 +294,10 @@ class Model:
     @property
     def fast_is_fused(self):
         return bool(self.L.kws_fast_is_fused(self.h))
+
+    def fast_lds_fragments(self):
+        """bit b set: the fused float32 plan reads block b's weight fragments from LDS (clear: from device memory, or no split-operand block)"""
+        return int(self.L.kws_fast_lds_fragments(self.h))
 
     def fast_fallback_count(self):
         n = C.c_size_t()

@@ -130,6 +130,14 @@ int kws_get_mode(const kws_handle *h)
     return h->mode;
 }
 int kws_fast_is_fused(const kws_handle *h) { return (h->fast_fused_ok || h->fast_q_ok) ? 1 : 0; }
+int kws_fast_lds_fragments(const kws_handle *h)
+{
+    int mask = 0;
+    if (h->fast_fused_ok)
+        for (int b = 0; b < h->fast_fused.n_blocks; b++)
+            if (h->fast_fused.blk[b].hconv && h->fast_fused.blk[b].h_b_off >= 0) mask |= 1 << b;
+    return mask;
+}
 EI_IMPULSE_ERROR kws_fast_fallback_count(kws_handle *h, size_t *count)
 {
     if (!h || !count) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");

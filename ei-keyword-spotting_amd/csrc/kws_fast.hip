@@ -22,6 +22,7 @@
 #include "kws_device.h"
 #include "kws_fast.h"
 #include "kws_bfly_m2k1.h"
+#include "kws_fast_maxmin.h"
 // The second compilation of this file (kws_fast_w3.o, -DKWS_FAST_WPS=3: three waves per SIMD, <= 168 registers, the float32-network forms only) goes into the
 // same library under names of its own; the launchers of the first one hand a plan laid out for three waves (KwsFastPlan::wps) over to them.
 #if KWS_FAST_WPS >= 3
@@ -63,15 +64,17 @@ __device__ __forceinline__ float half_wave_sum(float v)
     return v;
 }
 // whole-wave reductions, every lane receives the result: four DPP steps inside a row of 16 (no LDS round trip), then lane ^ 16
-// and lane ^ 32 through the LDS crossbar
+// and lane ^ 32 through the LDS crossbar.  (fast_max: what arrives from another lane is no value the compiler knows, and fmaxf canonicalised both operands
+// of every step.  That holds for every caller in every form of the kernel, the guard's two reductions -- column 0's largest |value|, the largest p (1 - p) --
+// included: their operands are results of this kernel's arithmetic, a NaN among them quiet, and is dropped here as fmaxf dropped it.)
 __device__ __forceinline__ float wave_max(float v)
 {
-    v = fmaxf(v, dpp_mov<0xB1>(v));
-    v = fmaxf(v, dpp_mov<0x4E>(v));
-    v = fmaxf(v, dpp_mov<0x141>(v));
-    v = fmaxf(v, dpp_mov<0x140>(v));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401F)));
-    return fmaxf(v, __shfl_xor(v, 32, KWS_WAVE));
+    v = fast_max(v, dpp_mov<0xB1>(v));
+    v = fast_max(v, dpp_mov<0x4E>(v));
+    v = fast_max(v, dpp_mov<0x141>(v));
+    v = fast_max(v, dpp_mov<0x140>(v));
+    v = fast_max(v, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401F)));
+    return fast_max(v, __shfl_xor(v, 32, KWS_WAVE));
 }
 __device__ __forceinline__ float wave_sum(float v)
 {
@@ -154,8 +157,9 @@ __device__ __forceinline__ void fast_conv_finish(const KwsFastBlock &k, v4f (&ac
 #pragma unroll
                 for (int i = 1; i < 4; ++i) {
                     const bool row_ok = r0 + i < out_w;
-                    mlo = (row_ok && pw[i] == pw[0]) ? fmaxf(mlo, acc[mt][nt][i]) : mlo;
-                    if (i < 3) mhi = (row_ok && pw[i] == pw[3]) ? fmaxf(mhi, acc[mt][nt][i]) : mhi;
+                    const float tlo = fast_max(mlo, acc[mt][nt][i]);        // (taken whether or not it is kept: fast_max)
+                    mlo = (row_ok && pw[i] == pw[0]) ? tlo : mlo;
+                    if (i < 3) { const float thi = fast_max(mhi, acc[mt][nt][i]); mhi = (row_ok && pw[i] == pw[3]) ? thi : mhi; }
                 }
                 merge(pw[0], n, mlo, r0 < out_w);
                 merge(pw[3], n, mhi, r0 + 3 < out_w && pw[3] != pw[0]);
@@ -182,8 +186,8 @@ __device__ __forceinline__ void fast_conv_finish(const KwsFastBlock &k, v4f (&ac
             for (int i = 0; i < 4; ++i) {
                 const int row = 16 * mt + 4 * lq + i;
                 float v = acc[mt][nt][i] * scale + bias;
-                v = fminf(fmaxf(v, cmin), cmax);
-                if (has_add) { v = v + addc; v = fminf(fmaxf(v, amin), amax); }
+                v = fast_clamp_u(v, cmin, cmax);
+                if (has_add) v = fast_clamp_u(v + addc, amin, amax);
                 *((row < out_w && n < out_c) ? sp + __mul24(row, sstride) : sink) = v;
             }
         }
@@ -191,8 +195,8 @@ __device__ __forceinline__ void fast_conv_finish(const KwsFastBlock &k, v4f (&ac
     for (int vr = 0; vr < k.vrows; ++vr) {
         const int n = lane & 31, nc = min(n, out_c - 1);
         float v = vout[vr] * scale + shared[k.bias_off + nc];
-        v = fminf(fmaxf(v, cmin), cmax);
-        if (has_add) { v = v + shared[k.addc_off + nc]; v = fminf(fmaxf(v, amin), amax); }
+        v = fast_clamp_u(v, cmin, cmax);
+        if (has_add) v = fast_clamp_u(v + shared[k.addc_off + nc], amin, amax);
         if (lane < 32 && n < out_c) stage[(16 * MT + vr) * sstride + n] = v;
     }
 }
@@ -392,7 +396,7 @@ __device__ __forceinline__ float fast_split_trips(float *__restrict__ img, int i
         // the k-padding channels (in_c .. in_cp - 1) meet zero weights, but what sits there need not survive the scaling: zeros
         v[u].x = pc[u] < in_c ? v[u].x : 0.0f;
         v[u].y = pc[u] + 1 < in_c ? v[u].y : 0.0f;
-        mx = fmaxf(mx, fmaxf(fabsf(v[u].x), fabsf(v[u].y)));
+        mx = fast_max(mx, fast_max_abs(v[u].x, v[u].y));
     }
     mx = wave_max(mx);
     // max|x| < 2^e; e kept where both s and 1 / s are normal numbers whatever the image holds
@@ -556,15 +560,22 @@ __device__ __forceinline__ float fast_conv_tiles_h(const KwsFastBlock &k, float 
                 else { h_[nt] = *(const v8h *)(bl + off); l_[nt] = *(const v8h *)(bl + off + NT * (KWS_WAVE * 16)); }
             }
         };
-        auto fetch_a = [&](const int2 &d, v8h (&dst)[MT], int plus) {
+        // The MT operand addresses of a k-step -- image-row test, zero-block select and address sum -- are formed ONCE, behind the first group of products, and
+        // serve both refills: the lo halves at once, the hi halves after the other two groups.  MT registers live across those two groups, where the table entry
+        // and the zero block's address are no longer needed -- not the 2 MT registers hoisted out of the whole loop that were spilled (profiles/net_lean.md).
+        const char *pa[MT];
+        auto form_a = [&](const int2 &d) {
             int r0v = row0, abv = row0 * rowb;
             KWS_OPAQUE3(r0v); KWS_OPAQUE3(abv);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const bool in_img = (unsigned)(r0v + d.y + 16 * mt) < (unsigned)in_w;
-                const char *p = in_img ? (const char *)in + (abv + d.x + mt * (16 * rowb)) : zb;
-                dst[mt] = *(const v8h *)(p + plus);
+                pa[mt] = in_img ? (const char *)in + (abv + d.x + mt * (16 * rowb)) : zb;
             }
+        };
+        auto read_a = [&](v8h (&dst)[MT], int plus) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) dst[mt] = *(const v8h *)(pa[mt] + plus);
         };
         auto step = [&](int ks, const v8h (&bh_)[NT], const v8h (&bl_)[NT], v8h (&nh_)[NT], v8h (&nl_)[NT]) {
             fetch_b(ks + 2, nh_, nl_);
@@ -575,7 +586,8 @@ __device__ __forceinline__ float fast_conv_tiles_h(const KwsFastBlock &k, float 
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[mt], bh_[nt], acc[mt][nt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            fetch_a(dn, al, lo_off);
+            form_a(dn);
+            read_a(al, lo_off);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
@@ -586,12 +598,12 @@ __device__ __forceinline__ float fast_conv_tiles_h(const KwsFastBlock &k, float 
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bh_[nt], acc[mt][nt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            fetch_a(dn, ah, 0);
+            read_a(ah, 0);
             __builtin_amdgcn_sched_barrier(0);
         };
         fetch_b(0, bh[0], blo[0]);
         fetch_b(1, bh[1], blo[1]);
-        { const int2 d = tab[0]; fetch_a(d, al, lo_off); fetch_a(d, ah, 0); }
+        { const int2 d = tab[0]; form_a(d); read_a(al, lo_off); read_a(ah, 0); }
         __builtin_amdgcn_s_setprio(1);
         // (whole trips of three: a k-step past the last one multiplies the zero block by the last fragments)
         for (int ks = 0; ks < n_ks; ks += 3) {
@@ -645,9 +657,9 @@ __device__ __forceinline__ void fast_pool_finish(const KwsFastBlock &k, const fl
     for (int i = lane; i < items; i += KWS_WAVE) {
         const int p = (int)(((unsigned)i * inv) >> 20), c = i - p * out_cp, cc = min(c, out_c - 1);
         float v = pm[p * 32 + cc] * scale + shared[k.bias_off + cc];
-        v = fminf(fmaxf(v, cmin), cmax);
-        if (has_add) { v = v + shared[k.addc_off + cc]; v = fminf(fmaxf(v, amin), amax); }
-        v = fminf(fmaxf(v, pmin), pmax);
+        v = fast_clamp_u(v, cmin, cmax);
+        if (has_add) v = fast_clamp_u(v + shared[k.addc_off + cc], amin, amax);
+        v = fast_clamp_u(v, pmin, pmax);
         img[p * out_stride + c] = c < out_c ? v : 0.0f;
     }
 }
@@ -693,8 +705,8 @@ __device__ __forceinline__ void fast_pool(const KwsFastBlock &k, const float *__
         for (int u = 0; u < 2; ++u) {
             float m = v[u][0];
 #pragma unroll
-            for (int j = 1; j < 8; ++j) m = fmaxf(m, v[u][j]);
-            m = fminf(fmaxf(m, pmin), pmax);
+            for (int j = 1; j < 8; ++j) m = fast_max(m, v[u][j]);
+            m = fast_clamp_u(m, pmin, pmax);
             if (i0 + u * KWS_WAVE + lane < items) img[p[u] * out_stride + c[u]] = c[u] < out_c ? m : 0.0f;
         }
     }
@@ -1899,7 +1911,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
             for (; i + S < fc_in; i += 2 * S) { tot = __fmaf_rn(cur[i], wfc[i], tot); tot1 = __fmaf_rn(cur[i + S], wfc[i + S], tot1); }
             if (i < fc_in) tot = __fmaf_rn(cur[i], wfc[i], tot);
             tot = group_sum(tot + tot1, S) + shared[FP.fc_b_off + uc];
-            tot = fminf(fmaxf(tot, FP.fc_min), FP.fc_max);
+            tot = fast_clamp_u(tot, FP.fc_min, FP.fc_max);
             const bool on = unit < fc_out;
             if (tap_logits && on && sl == 0) tap_logits[(size_t)clip * n_labels + unit] = tot;       // kws_set_logits_tap
             const float mx = wave_max(on ? tot : -FLT_MAX);

@@ -88,6 +88,9 @@ EI_IMPULSE_ERROR kws_set_mode(kws_handle *h, int mode);   /* KWS_ERROR_UNSUPPORT
 int kws_get_mode(const kws_handle *h);
 /* 1: KWS_MODE_FAST runs this model's network fused behind the MFCC block (float32 CONV_2D graphs); 0: features go through HBM */
 int kws_fast_is_fused(const kws_handle *h);
+/* Where the fused float32 plan keeps the weight fragments of its split-operand convolution blocks: bit b set = block b's fragments have a copy in the
+ * workgroup's LDS block, clear = they are read from device memory (through L2) -- or block b is no such block.  0 for a model without a fused float32 plan. */
+int kws_fast_lds_fragments(const kws_handle *h);
 /* What the last KWS_MODE_FAST batch call on this handle did with its clips (both synchronise the device):
  *   kws_fast_fallback_count  clips the fast kernel (first tier) handed back.  They went to the SECOND tier: cepstra from the exact kernels
  *                            (bit-identical to the reference's), then the fast cmvnw + network from those -- about 0.4 x the exact path;
