@@ -1,6 +1,6 @@
 // kws_generic.hip -- the exact MFCC block for every configuration the tuned kernel (kws_mfcc.hip) is not instantiated for: any even
 // fft_length whose half factors into 2, 3, 4, 5 (numpy::rfft zero-pads or truncates the frame to it, SDK/dsp/numpy.hpp:1091-1156;
-// kf_factor kiss_fft.cpp:303-324), any such mel filter count up to 64, any frame count / stride / clip length (no alignment
+// kf_factor kiss_fft.cpp:303-324), any such mel filter count from 2 to 128, any frame count / stride / clip length (no alignment
 // rules), mel filters of any width.  Same bit-exactness contract as kws_device.h: every floating-point operation in the
 // reference's order and precision.
 //
@@ -116,6 +116,7 @@ __device__ void g_rfft(const float *in, float *tmp, float *spec, int nfft, const
         const int p = fac[2 * l], m = fac[2 * l + 1];
         int fstride = 1;
         for (int q = 0; q < l; q++) fstride *= fac[2 * q];
+        if (p == 1) continue;                              // a transform of one point (the DCT of two filters): kf_bfly_generic with p = 1 leaves it as it is
         for (int base = 0; base < ncfft; base += p * m) g_bfly<S>(tmp, base, fstride, m, p, tw);
     }
     const cf t0 = g_ld<S>(tmp, 0);
@@ -748,6 +749,7 @@ __global__ __launch_bounds__(WPS >= 4 ? 512 : 256, WPS) void kws_spectral_lds_ke
             WAVE_SYNC();
             for (int l = P.dct_levels - 1; l >= 0; l--) {
                 const int p = P.dct_fac[2 * l], m = P.dct_fac[2 * l + 1];
+                if (p == 1) continue;                              // two filters: one point, kf_factor's (1, 1) -- nothing to do (wave-uniform)
                 int fstride = 1;
                 for (int q = 0; q < l; q++) fstride *= P.dct_fac[2 * q];
                 const int nb = nc / p;

@@ -386,6 +386,7 @@ static int fft_work(cpx *Fout, const cpx *f, size_t fstride, const int *factors,
         }
     }
     switch (p) {
+    case 1: break;   /* a transform of ONE point (the DCT of two mel filters): kf_factor yields (1, 1) and kf_bfly_generic with p = 1 copies the point onto itself */
     case 2: bfly2(Fout, fstride, pl, m); break;
     case 3: bfly3(Fout, fstride, pl, m); break;
     case 4: bfly4(Fout, fstride, pl, m); break;

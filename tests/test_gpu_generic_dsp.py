@@ -179,16 +179,20 @@ def test_quantized_filterbank_models_on_gpu(name, pkg, oracle, tmp_path):
     assert (bits(f) == bits(fo)).all() and (q == qo).all() and (bits(s) == bits(so)).all(), name
     gm.close()
 
-@pytest.mark.parametrize("name", ["fft1024_filters36", "stride10ms_win31", "fft128_win51"])
+@pytest.mark.parametrize("name", ["fft1024_filters36", "stride10ms_win31", "fft128_win51", "envelope_fft96", "envelope_fft320", "envelope_fft600"])
 def test_chunk_length_is_measured_per_handle_and_never_changes_a_bit(name, dev_pkg, oracle, tmp_path, monkeypatch):
     """kws_spectral_lds_kernel runs with eight or four frames per chunk (csrc/kws_generic.hip); which is faster depends on the shape, so a handle
-    measures it on its own first large calls (kws_api.cpp generic_chunk_begin).  Both pinned values and the measured path give the oracle's bits."""
+    measures it on its own first large calls (kws_api.cpp generic_chunk_begin).  Both pinned values and the measured path give the oracle's bits.
+    envelope_*: mixed-radix shapes of tests/general_dsp_shapes.py (radix 3 and radix 5 butterflies; fft600: with twiddles other than 1) through the same combinations."""
     pkg = dev_pkg            # KWS_DEV_GENERIC_LCH is a development switch: the development build of the library (conftest.py)
     monkeypatch.setenv("KWS_DEV_GENERIC_NO_TUNED_SPECTRAL", "1")     # (this test is about the cooperative kernel: a shape whose spectral stage the tuned kernel could take stays on it)
     import ctypes
     import torch
-    kw = dict(BLOCKS, **CASES[name])
-    blob = synth_model_blob(seed=3, **kw)
+    if name.startswith("envelope_"):
+        import general_dsp_shapes
+        blob = general_dsp_shapes.blob(name[len("envelope_"):])
+    else:
+        blob = synth_model_blob(seed=3, **dict(BLOCKS, **CASES[name]))
     path = str(tmp_path / "m.kwsm")
     open(path, "wb").write(blob)
     om = OracleModel(oracle, path)

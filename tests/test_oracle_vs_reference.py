@@ -389,3 +389,27 @@ def test_quant_edge_models_through_reference_op_registrations(group, oracle, ref
             assert all((a == t).all() for a, t in zip(taps, ot) if a.dtype == np.int8), key
         r = quant_edge_run(lambda q: om.nn_invoke(q, taps=True), blob, QUANT_EDGES[key]["where"], qs)
         assert quant_edge_not_vacuous(key, r["edited"], r["fc"]) is None, (key, quant_edge_not_vacuous(key, r["edited"], r["fc"]))
+
+
+@pytest.mark.parametrize("name", __import__("general_dsp_shapes").NAMES)
+def test_general_envelope_shapes_pinned(name, oracle, reference, tmp_path):
+    """Every served shape of tests/general_dsp_shapes.py -- the ends of what build_dsp_plan hands the general kernels: mixed-radix and degenerate
+    fft lengths, fft 2048 / 4096, 2 .. 128 filters, cmvnw windows of 1 / 3 / 301 rows, odd geometry -- the reference's extract_mfcc_features ==
+    the restatement, bit for bit, on two synthetic clips (the first two of the GPU tests' batch), the impulses, the ramp, the zero clip and the
+    full-scale alternation.  This is what lets tests/test_gpu_general_envelope.py compare the kernels with the restatement alone.  The table's
+    conditions against a vacuous comparison are asserted here: finite features on every clip, at least MIN_DISTINCT distinct values per
+    synthetic clip (win1: one value by construction, and said so)."""
+    import general_dsp_shapes as G
+    from kws_testlib import OracleModel
+    om = OracleModel(oracle, G.write_model(name, tmp_path))
+    cfg, n = om.cfg, om.raw_sample_count
+    assert oracle.num_frames(n, cfg) == reference.num_frames(n, cfg)
+    assert (bits(oracle.filterbanks(cfg)) == bits(reference.filterbanks(cfg))).all()
+    for i, c in enumerate(G.clips(oracle, n, 2)):
+        a, b = oracle.extract_mfcc(c, cfg), reference.extract_mfcc(c, cfg)
+        assert a.shape == b.shape == (om.n_features,) and (bits(a) == bits(b)).all(), (name, i)
+        assert (bits(oracle.mfcc_nocmvn(c, cfg)) == bits(reference.mfcc_nocmvn(c, cfg))).all(), (name, i)
+        assert np.isfinite(a).all(), (name, i)
+        if i < 2:
+            distinct = np.unique(bits(a)).size
+            assert distinct == 1 if name in G.ONE_VALUE else distinct >= G.MIN_DISTINCT, (name, i, distinct)
