@@ -697,6 +697,21 @@ EI_IMPULSE_ERROR kws_extract_mfcc_batch_device(kws_handle *h, const int16_t *pcm
 // development / test aid (not in the public headers): kws_spectral_lds_kernel's chunk length on this handle: 0 while it is being measured
 int kws_dev_generic_chunk(const kws_handle *h) { return h ? h->gen_tune.choice : 0; }
 
+// development / test aid (not in the public headers): what kws_nn_f32_pick_blocking chose for conv block `block` of a float32 handle, and how the
+// handle's kernel is launched: out = { tb, ob, fused_pool, ntb, rows, depthwise, waves per workgroup, dynamic LDS bytes }.  Read only.  Returns 0, or a
+// negative value for no handle, a handle that is not float32, or a block index outside 0 .. n_blocks - 1.
+int kws_dev_f32_blocking(const kws_handle *h, int block, int out[8])
+{
+    if (!h || !out || !h->is_float) return -1;
+    const KwsNnPlanF32 &N = h->nnf;
+    if (block < 0 || block >= N.n_blocks) return -2;
+    const KwsConvBlockF32 &k = N.blk[block];
+    const int waves = kws_nn_f32_waves(N);
+    out[0] = k.tb; out[1] = k.ob; out[2] = k.fused_pool; out[3] = k.ntb; out[4] = k.rows; out[5] = k.depthwise;
+    out[6] = waves; out[7] = (int)kws_nn_f32_smem_bytes(N, waves);
+    return 0;
+}
+
 // development aid (not in the public headers): per-phase shader-clock totals of wave 0 of the float network kernel
 extern long long *kws_dev_f32_prof;
 void kws_dev_set_f32_prof(long long *dev_buf) { kws_dev_f32_prof = dev_buf; }

@@ -7,8 +7,10 @@
 //  Kernel 2f: float32 models.  One wave per clip.  Every accumulation replays the reference's sequential
 //  `total += input * filter` order (tap outer, channel inner; product and sum rounded separately -- the build has
 //  -ffp-contract=off), so everything up to the logits is bit-identical to the float TFLite-Micro kernels; only softmax's
-//  expf is the device's.  Zero-padded activation rows stand in for the reference's skipped out-of-image taps: they add
-//  an exact 0 (x*0 = +-0, and total + (+-0) == total for every total the chain can hold, +0 included).
+//  expf is the device's.  Zero-padded activation rows stand in for the reference's skipped out-of-image taps: for a FINITE
+//  weight they add an exact 0 (0*w = +-0, and total + (+-0) == total for every total the chain can hold, +0 included: a
+//  chain starts at +0 and +0 + -0 = +0).  PRECONDITION: every conv / depthwise weight is finite -- 0 * inf = NaN where the
+//  reference never touches the tap; build_nn_plan_f32 refuses a model with a non-finite weight (kws_plan.cpp).
 //
 //  The multiply-adds of a clip are order-constrained only WITHIN one output's chain, so a lane runs TB x OB chains (TB
 //  consecutive time steps x OB consecutive output channels) side by side: per chain step it reads TB activations and one

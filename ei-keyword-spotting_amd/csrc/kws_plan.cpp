@@ -606,6 +606,17 @@ static void h_act_range_f32(int act, float *lo, float *hi)
     else if (act == 3) { *lo = 0.f; *hi = 6.f; }         // kTfLiteActRelu6
 }
 
+// A multiplied constant (conv / depthwise / FULLY_CONNECTED weight) must be finite.  The kernels' zero-padded image rows multiply every weight of an
+// out-of-image tap by 0 where the reference skips the tap (conv.h:71-75, depthwiseconv_float.h:71-75): 0 * w is an exact 0 only for a finite w
+// (0 * inf = NaN).  FULLY_CONNECTED weights are held to the same condition so that one rule covers every multiplied constant.  Biases and ADD
+// constants are added, never multiplied by padding: no condition.  Returns the index of the first non-finite value, or -1.
+static long h_first_non_finite(const std::vector<float> &v)
+{
+    for (size_t i = 0; i < v.size(); ++i)
+        if (!std::isfinite(v[i])) return (long)i;
+    return -1;
+}
+
 static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
 {
     const Model &m = h->model;
@@ -653,6 +664,9 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
         h_act_range_f32(act, &k.conv_min, &k.conv_max);           // the float depthwise op honours its activation
         std::vector<float> wv = floats(w), bv(out_c, 0.0f), av(out_c, 0.0f);
         if ((int)wv.size() != out_c * f_w * (dw ? 1 : in_c)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu filter size", i);
+        if (const long bad = h_first_non_finite(wv); bad >= 0)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: weight tensor %d holds a non-finite value (element %ld): the float kernels need finite weights", i,
+                        cv.in[1], bad);
         if (bias) { if ((int)bias->nbytes != out_c * 4) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu bias size", i); bv = floats(*bias); }
         cur = cv.out[0]; cur_w = out_w; cur_c = out_c;
         i++;
@@ -733,6 +747,9 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
             L.k = (int)k; L.units = (int)units;
             h_act_range_f32(fc.p[0], &L.lo, &L.hi);
             std::vector<float> wv = floats(w), bv((size_t)units, 0.0f);
+            if (const long bad = h_first_non_finite(wv); bad >= 0)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "dense layer %d: weight tensor %d holds a non-finite value (element %ld): the float kernels need finite weights",
+                            li, fc.in[1], bad);
             if (bias) bv = floats(*bias);
             EI_IMPULSE_ERROR e;
             if ((e = h->upload(wv, &L.w))) return e;
@@ -776,6 +793,9 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
             return fail(KWS_ERROR_UNSUPPORTED_MODEL, "FULLY_CONNECTED shape %dx%d outside the kernel's limits", N.fc_out, N.fc_in);
         h_act_range_f32(fc.p[0], &N.fc_min, &N.fc_max);
         std::vector<float> wv = floats(w), bv(N.fc_out, 0.0f);
+        if (const long bad = h_first_non_finite(wv); bad >= 0)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "FULLY_CONNECTED: weight tensor %d holds a non-finite value (element %ld): the float kernels need finite weights",
+                        fc.in[1], bad);
         if (bias) { if ((int)bias->nbytes != N.fc_out * 4) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "FULLY_CONNECTED bias size"); bv = floats(*bias); }
         EI_IMPULSE_ERROR e;
         if ((e = h->upload(wv, &N.fc_w))) return e;

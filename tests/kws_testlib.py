@@ -1115,3 +1115,585 @@ def quant_edge_golden():
     offs = np.cumsum([0] + [int(n) * n_rows for n in g["n_labels"]])
     return {str(k): dict(out=g["out"][offs[i]:offs[i + 1]].reshape(n_rows, -1), fc=g["fc"][offs[i]:offs[i + 1]].reshape(n_rows, -1),
                          pooled_sha=g["pooled_sha"][i]) for i, k in enumerate(g["keys"])}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  the float32 network kernels over every blocking and at float edges (tests/test_gpu_f32_edges.py, the CPU pins in
+#  tests/test_oracle_vs_reference.py, tests/golden/f32_edges_l476.npz)
+# ---------------------------------------------------------------------------------------------------------------
+F32_FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def f32_act_range(act):
+    """CalculateActivationRange<float> (kernel_util_lite.h:79-97): TfLiteFusedActivation -> (lo, hi)"""
+    return {0: (-F32_FLT_MAX, F32_FLT_MAX), 1: (0.0, F32_FLT_MAX), 2: (-1.0, 1.0), 3: (0.0, 6.0)}[act]
+
+
+def f32_pick_blocking(depthwise, out_w, out_c, pool, pool_stride, pool_w):
+    """kws_nn_f32_pick_blocking restated: (tb, ob, mode), mode "direct" (no pooling node) | "fused" (pooled in registers) | "staged".
+    A restatement for choosing and describing test shapes only: the GPU test asserts the library's own pick through kws_dev_f32_blocking."""
+    can_fuse = pool > 1 and pool == pool_stride and pool in (2, 4, 7, 8)
+    best, pick = [1e30, 1e30], [(1, 1), (1, 1)]
+    for fused in (0, 1):
+        for tb in (1, 2, 4, 7, 8):
+            for ob in (1, 2, 4):
+                if depthwise and ob != 1:
+                    continue
+                if fused and (not can_fuse or tb != pool):
+                    continue
+                n_tb = pool_w if fused else (out_w + tb - 1) // tb
+                items = n_tb * ((out_c + ob - 1) // ob)
+                cost = ((items + 63) // 64) * (2 * tb * ob + tb + 1)
+                if cost < best[fused]:
+                    best[fused], pick[fused] = cost, (tb, ob)
+    fused = 1 if can_fuse and best[1] <= best[0] else 0
+    tb, ob = pick[fused]
+    return tb, ob, "fused" if fused else "direct" if pool == 1 else "staged"
+
+
+def f32_graph_blocks(blob):
+    """The conv blocks of a float .kwsm as build_nn_plan_f32 reads them: per block a dict of the shape, the blocking (f32_pick_blocking),
+    the nodes (conv_nd, add_nd, pool_nd: node dicts or None) and the head: (blocks, dict(fc_in, fc_out, dense, n_features))."""
+    import eon_import
+    tensors, nodes, t_in, _, _ = eon_import.parse_blob(blob)
+    blocks = []
+    for nd in nodes:
+        if nd["op"] in (1, 6):
+            blocks.append(dict(conv_nd=nd, add_nd=None, pool_nd=None))
+        elif nd["op"] == 2:
+            blocks[-1]["add_nd"] = nd
+        elif nd["op"] == 3:
+            blocks[-1]["pool_nd"] = nd
+    for b in blocks:
+        cv = b["conv_nd"]
+        x, w = tensors[cv["in"][0]]["dims"], tensors[cv["in"][1]]["dims"]
+        dw = cv["op"] == 6
+        in_w, in_c, taps = x[2], x[3], w[2]
+        out_c = w[3] if dw else w[0]
+        out_w = in_w if cv["p"][0] == 1 else in_w - taps + 1
+        pad_left = max(0, (out_w - 1) + taps - in_w) // 2
+        pool = stride = 1
+        pool_w = out_w
+        if b["pool_nd"] is not None:
+            p = b["pool_nd"]["p"]
+            pool, stride = p[4], p[2]
+            pool_w = (out_w + stride - 1) // stride if p[0] == 1 else (out_w - pool) // stride + 1
+        tb, ob, mode = f32_pick_blocking(dw, out_w, out_c, pool, stride, pool_w)
+        ntb = pool_w if mode == "fused" else (out_w + tb - 1) // tb
+        b.update(depthwise=dw, in_w=in_w, in_c=in_c, taps=taps, out_c=out_c, out_w=out_w, pad_left=pad_left, pool=pool, pool_stride=stride,
+                 pool_w=pool_w, pool_valid=b["pool_nd"] is not None and b["pool_nd"]["p"][0] == 2, conv_valid=cv["p"][0] == 2,
+                 tb=tb, ob=ob, mode=mode, ntb=ntb, rows=max(pad_left + in_w, ntb * tb + taps - 1))
+    fcs = [nd for nd in nodes if nd["op"] == 4]
+    dense = len(fcs) > 1 or not blocks
+    w = tensors[fcs[0]["in"][1]]["dims"]
+    head = dict(fc_in=w[1], fc_out=0 if dense else w[0], dense=dense, n_features=tensors[t_in]["dims"][-1], n_dense=len(fcs) if dense else 0)
+    return blocks, head
+
+
+def f32_launch_shape(blob):
+    """(waves per workgroup, dynamic LDS bytes) of kws_nn_f32_kernel for a float blob: kws_nn_f32_waves / kws_nn_f32_smem_bytes / nnf_layout
+    restated (test shapes only; the GPU test asserts both against kws_dev_f32_blocking)"""
+    blocks, head = f32_graph_blocks(blob)
+    r4 = lambda v: (v + 3) & ~3
+    w_fl = a_fl = b_fl = y_fl = 0
+    for i, b in enumerate(blocks):
+        w_fl += (b["taps"] if b["depthwise"] else b["taps"] * b["in_c"]) * r4(b["out_c"])
+        img = b["rows"] * b["in_c"]
+        if i & 1:
+            b_fl = max(b_fl, img)
+        else:
+            a_fl = max(a_fl, img)
+        if b["mode"] == "staged":
+            y_fl = max(y_fl, b["out_w"] * b["out_c"])
+    fc_fl = r4(head["fc_out"] * head["fc_in"] + head["fc_out"])
+    vec_fl = r4(max(head["fc_in"], 64)) + 64
+    smem = lambda waves: (w_fl + fc_fl + waves * (r4(a_fl) + r4(b_fl) + r4(y_fl) + vec_fl)) * 4
+    vec4 = any(not b["depthwise"] and b["tb"] > 1 and b["in_c"] % 4 == 0 for b in blocks)
+    waves = next((w for w in range(8 if vec4 else 16, 4, -1) if smem(w) <= 158 * 1024), 4)
+    return waves, smem(waves)
+
+
+def f32_edit_blob(blob, edit):
+    """a float blob with edit(tensors, nodes) applied (edit=None: the blob itself)"""
+    if edit is None:
+        return blob
+    import eon_import
+    tensors, nodes, t_in, t_out, meta = eon_import.parse_blob(blob)
+    edit(tensors, nodes)
+    return eon_import.serialise(tensors, nodes, t_in, t_out, meta)
+
+
+def f32_blob(entry):
+    """entry: dict(kw = synth_model_blob keyword arguments, edit = None or edit(tensors, nodes) of the de-quantised graph) -> float .kwsm"""
+    from dequantize_model import dequantize
+    return f32_edit_blob(dequantize(synth_model_blob(**entry["kw"])), entry.get("edit"))
+
+
+def _fget(t):
+    return np.frombuffer(t["data"], np.float32).copy()
+
+
+def _fset(t, v):
+    v = np.ascontiguousarray(v, np.float32)
+    assert v.nbytes == t["nbytes"], (v.nbytes, t["nbytes"])
+    t["data"] = v.tobytes()
+
+
+def _frames(n, ncep, **kw):
+    """DSP geometry for n frames of ncep columns (20 ms frames and stride at 16 kHz: 320 (n + 1) samples)"""
+    nf = 32 if ncep <= 32 else 40 if ncep <= 40 else 64
+    return dict(dict(raw_samples=320 * (n + 1), ncep=ncep, num_filters=nf, high=0, n_labels=3, add_bias=False, conv_bias=True), **kw)
+
+
+def _f32_blockings():
+    """key "conv|dw/tb<T>/ob<O>/<mode>[#note]" -> dict(kw, block, edit, rows = input rows of f32_inputs).  The block under test is block `block` (block 0 wherever nothing is said).
+    Shapes: the smallest that an enumeration of kws_nn_f32_pick_blocking over every out_w <= 198, out_c <= 64, pool window 1 .. 8 with SAME or
+    VALID padding (and window 3 / stride 2) finds per blocking, or a neighbour that adds a coverage point; taps and input channels are spread so
+    that the points a-i of test_f32_blocking_table_covers_the_kernel occur.  The enumeration finds 56 reachable (depthwise, tb, ob, mode)
+    combinations -- all 15 conv (tb, ob) and all 5 depthwise tb in every mode, except that tb 1 cannot fuse (a fused lane owns one window of
+    tb = pool >= 2 rows); conv (7, 1) direct and staged are reachable from 129 x 3 on.  All 56 have an entry: none had to be left out.
+    A SAME pool is loadable only where its left padding is 0 (build_nn_plan_f32): window * windows - rows <= 1.
+    Pools: p SAME, -p VALID, (window, stride, VALID?) as synth_model_blob takes them."""
+    T = {}
+    in_cs, tapss = (3, 4, 5, 8, 2, 6, 7, 12), (3, 1, 2, 7, 9, 4, 16, 5)
+    TAIL = (4, 1, -8)                 # a pooled one-tap block that brings a long output under KWS_FC_IN_MAX
+
+    def put(key, frames, ncep, blocks, block=0, rows=64, **kw):
+        assert key not in T, key
+        T[key] = dict(kw=_frames(frames, ncep, seed=7000 + len(T), blocks=tuple(blocks), **kw), block=block, edit=None, rows=rows)
+
+    def conv(key, w, c, pool=1, tail=False, valid_conv=False, **kw):
+        n = len(T)
+        in_c, taps = in_cs[n % 8], tapss[(n // 2 + n) % 8]
+        put(key, w + (taps - 1 if valid_conv else 0), in_c, [(c, taps, pool)] + ([TAIL] if tail else []),
+            conv_valid=(0,) if valid_conv else (), **kw)
+
+    # ---- CONV_2D, one time step per lane (weights streamed as [oc block][step][ob]; 8 steps per batch, J % 8 one by one)
+    put("conv/tb1/ob1/direct", 1, 2, [(1, 1, 1)])                                       # J = 2: no full batch
+    put("conv/tb1/ob1/staged", 1, 3, [(1, 7, 2)])                                       # J = 21; a SAME window of one row
+    put("conv/tb1/ob2/direct", 5, 4, [(13, 2, 1)])                                      # in_c % 4 == 0, even taps, J = 8
+    put("conv/tb1/ob2/staged", 5, 3, [(13, 9, 2)], add_bias=True)                       # 9 taps on 5 rows, ragged SAME window, ADD + ReLU
+    put("conv/tb1/ob2/staged#valid_pool", 5, 5, [(13, 3, -2)])                          # the VALID pool drops row 4
+    put("conv/tb1/ob2/staged#overlap", 5, 2, [(13, 3, (3, 2, True))])                   # window 3, stride 2
+    put("conv/tb1/ob2/direct#valid_conv", 7, 3, [(13, 3, 1)], conv_valid=(0,))          # VALID convolution 7 -> 5 rows
+    put("conv/tb1/ob4/direct", 3, 13, [(43, 1, 1)])                                     # J = 13
+    put("conv/tb1/ob4/staged", 3, 6, [(43, 4, 2)])
+    put("conv/tb1/ob2/direct#behind_vec4", 80, 4, [(1, 3, 2), (13, 1, -8), (13, 3, 1)], block=2)   # block 0 has 16-byte rows: the 256-register build
+    # ---- CONV_2D, register blocked
+    conv("conv/tb2/ob1/direct", 65, 1)
+    conv("conv/tb2/ob1/fused", 65, 1, 2)                                                # SAME, ragged last window
+    conv("conv/tb2/ob1/staged", 65, 1, (3, 2, True))                                    # window 3, stride 2
+    conv("conv/tb2/ob2/direct", 65, 2)
+    conv("conv/tb2/ob2/fused", 67, 2, -2)                                               # VALID drops row 66
+    conv("conv/tb2/ob2/staged", 65, 2, 3, add_bias=True)                                # SAME, ragged last window; ADD + ReLU
+    conv("conv/tb2/ob4/direct", 97, 3)
+    conv("conv/tb2/ob4/fused", 97, 3, 2)
+    conv("conv/tb2/ob4/staged", 97, 3, -3)
+    conv("conv/tb2/ob1/direct#valid_conv", 65, 1, valid_conv=True)
+    conv("conv/tb4/ob1/direct", 65, 3)
+    conv("conv/tb4/ob1/fused", 65, 3, -4)
+    conv("conv/tb4/ob1/staged", 65, 3, 2)
+    conv("conv/tb4/ob2/direct", 77, 5)
+    conv("conv/tb4/ob2/fused", 67, 5, 4, add_bias=True)                                 # SAME, ragged last window; ADD + ReLU
+    conv("conv/tb4/ob2/staged", 77, 5, 2)
+    conv("conv/tb4/ob4/direct", 30, 25)
+    conv("conv/tb4/ob4/fused", 30, 25, -4)
+    conv("conv/tb4/ob4/staged", 30, 25, (3, 2, False))                                  # overlapping SAME windows
+    conv("conv/tb7/ob1/direct", 129, 3)
+    conv("conv/tb7/ob1/fused", 85, 5, -7)
+    conv("conv/tb7/ob1/staged", 129, 3, 2)
+    conv("conv/tb7/ob2/direct", 97, 7)
+    conv("conv/tb7/ob2/fused", 97, 7, 7)                                                # SAME, ragged last window
+    conv("conv/tb7/ob2/staged", 97, 7, 2)
+    conv("conv/tb7/ob4/direct", 198, 7, tail=True)
+    conv("conv/tb7/ob4/fused", 198, 7, -7)
+    conv("conv/tb7/ob4/staged", 198, 7, 2)
+    conv("conv/tb8/ob1/direct", 86, 5)
+    conv("conv/tb8/ob1/fused", 86, 5, -8)
+    conv("conv/tb8/ob1/staged", 86, 5, 2)
+    conv("conv/tb8/ob2/direct", 86, 9)
+    conv("conv/tb8/ob2/fused", 87, 9, 8)                                                # SAME, ragged last window
+    conv("conv/tb8/ob2/staged", 86, 9, 2)
+    conv("conv/tb8/ob4/direct", 65, 25, tail=True)
+    conv("conv/tb8/ob4/fused", 65, 25, -8)
+    conv("conv/tb8/ob4/staged", 65, 25, 2, add_bias=True)
+    # ---- DEPTHWISE_CONV_2D ("dw", depth multiplier, taps, pool, activation)
+    put("dw/tb1/ob1/direct", 1, 1, [("dw", 1, 3, 1, 0)])
+    put("dw/tb1/ob1/staged", 1, 1, [("dw", 1, 1, 2, 0)])
+    put("dw/tb2/ob1/direct", 5, 13, [("dw", 1, 3, 1, 0)])
+    put("dw/tb2/ob1/fused", 5, 13, [("dw", 1, 5, 2, 0)])                                # SAME, ragged last window
+    put("dw/tb2/ob1/staged", 5, 13, [("dw", 1, 7, 3, 0)])                               # SAME, ragged last window
+    put("dw/tb2/ob1/staged#overlap", 5, 13, [("dw", 1, 2, (3, 2, True), 0)])
+    put("dw/tb2/ob1/direct#valid_conv", 7, 13, [("dw", 1, 3, 1, 0)], conv_valid=(0,))
+    put("dw/tb2/ob1/direct#behind_vec4", 80, 4, [(1, 3, 2), (13, 1, -8), ("dw", 1, 3, 1, 0)], block=2)
+    put("dw/tb4/ob1/direct", 97, 2, [("dw", 1, 3, 1, 0)])
+    put("dw/tb4/ob1/fused", 97, 1, [("dw", 2, 4, -4, 0)])                               # depth multiplier 2; VALID drops row 96
+    put("dw/tb4/ob1/staged", 97, 2, [("dw", 1, 16, 2, 0)])
+    put("dw/tb7/ob1/direct", 7, 7, [("dw", 7, 3, 1, 0)])
+    put("dw/tb7/ob1/fused", 7, 7, [("dw", 7, 5, 7, 1)])                                 # fused ReLU
+    put("dw/tb7/ob1/staged", 7, 7, [("dw", 7, 9, 2, 0)])
+    put("dw/tb8/ob1/direct", 15, 13, [("dw", 2, 3, 1, 0)])
+    # (a window of 8 rows: a row wins one input in 8, and the edge row with two taps fewer -- 160 rows of input bring every position to a win)
+    put("dw/tb8/ob1/fused", 11, 5, [("dw", 7, 3, -8, 0)], rows=160)                     # VALID drops rows 8 .. 10
+    put("dw/tb8/ob1/fused#ragged", 15, 13, [("dw", 2, 3, 8, 0)])
+    put("dw/tb8/ob1/staged", 15, 13, [("dw", 2, 7, 2, 3)])                              # fused ReLU6
+    return T
+
+
+F32_BLOCKINGS = _f32_blockings()
+
+
+def f32_blocking_name(b):
+    """a block of f32_graph_blocks (or the accessor's values in the same keys) -> "conv|dw/tb<T>/ob<O>/<mode>" """
+    return "%s/tb%d/ob%d/%s" % ("dw" if b["depthwise"] else "conv", b["tb"], b["ob"], b["mode"])
+
+
+def f32_inputs(n_features, n=64, seed=476):
+    """the feature rows of the blocking tests: n rows of independent N(0, 2^2) values (the network-only entry point takes any vector)"""
+    return (np.random.default_rng(seed).standard_normal((n, n_features)) * np.float32(2.0)).astype(np.float32)
+
+
+F32_GOLDEN_ROWS = 4            # tests/golden/f32_edges_l476.npz holds the reference's logits and scores of the first 4 rows per graph
+
+
+def f32_reach_shares(blob, invoke, xs):
+    """Against a vacuous comparison: per conv block of a float blob, the share of conv output positions (t, oc) that, for at least one row of
+    xs, lie strictly inside every clamp range behind them in the block (the convolution's, the ADD's, the pool's fused activation) AND win
+    their pooling window -- so that a wrong value there changes the block's output.  Positions no pooling window covers (the tail a VALID pool
+    drops) cannot reach any output by the op's definition and are left out of the count.  invoke(x) -> (scores, every tensor)."""
+    blocks, _ = f32_graph_blocks(blob)
+    reached = [np.zeros((b["out_w"], b["out_c"]), bool) for b in blocks]
+    covered = []
+    for b in blocks:
+        cov = np.zeros(b["out_w"], bool)
+        for pw in range(b["pool_w"]):
+            cov[pw * b["pool_stride"]:pw * b["pool_stride"] + b["pool"]] = True
+        covered.append(cov)
+    for x in xs:
+        _, taps = invoke(x)
+        for b, r in zip(blocks, reached):
+            shape = (b["out_w"], b["out_c"])
+            v = np.asarray(taps[b["conv_nd"]["out"][0]]).reshape(shape)
+            lo, hi = f32_act_range(b["conv_nd"]["p"][3])
+            ok = (v > lo) & (v < hi)
+            if b["add_nd"] is not None:
+                v = np.asarray(taps[b["add_nd"]["out"][0]]).reshape(shape)
+                lo, hi = f32_act_range(b["add_nd"]["p"][0])
+                ok &= (v > lo) & (v < hi)
+            if b["pool_nd"] is not None:
+                lo, hi = f32_act_range(b["pool_nd"]["p"][5])
+                win = np.zeros(shape, bool)
+                for pw in range(b["pool_w"]):
+                    rows = slice(pw * b["pool_stride"], min(pw * b["pool_stride"] + b["pool"], b["out_w"]))
+                    m = v[rows].max(axis=0)
+                    win[rows] |= (v[rows] == m) & (m > lo) & (m < hi)
+                ok &= win
+            r |= ok
+    return [float(r[c].mean()) for r, c in zip(reached, covered)]
+
+
+def f32_blocking_coverage(blobs):
+    """the coverage points a-i of the issue counted from the table: class ("conv_tb>1" | "conv_tb1" | "dw") -> set of point names that occur
+    at the block under test of some entry.  blobs: key -> float blob."""
+    out = {"conv_tb>1": set(), "conv_tb1": set(), "dw": set()}
+    for key, blob in blobs.items():
+        b = f32_graph_blocks(blob)[0][F32_BLOCKINGS[key]["block"]]
+        pts = out["dw" if b["depthwise"] else "conv_tb1" if b["tb"] == 1 else "conv_tb>1"]
+        pts.add("in_c%4==0" if b["in_c"] % 4 == 0 else "in_c%4!=0")
+        if b["out_c"] % b["ob"]:
+            pts.add("out_c%ob!=0")
+        if b["out_c"] % 4:
+            pts.add("out_c%4!=0")
+        if b["out_w"] % b["tb"]:
+            pts.add("out_w%tb!=0")
+        t = b["taps"]
+        pts.add("taps1" if t == 1 else "taps7" if t == 7 else "taps9..16" if t >= 9 else "taps_even" if t % 2 == 0 else "taps_other")
+        if t >= 9 and t % 2 == 0:
+            pts.add("taps_even")
+        J = t * b["in_c"]
+        pts.add("J<8" if J < 8 else "J>8,J%8!=0" if J % 8 else "J%8==0")
+        if b["pool"] > 1:
+            last = (b["pool_w"] - 1) * b["pool_stride"] + b["pool"]
+            if not b["pool_valid"] and last > b["out_w"]:
+                pts.add("same_ragged_" + b["mode"])
+            if b["pool_valid"] and last < b["out_w"]:
+                pts.add("valid_pool_drops_tail")
+            if (b["pool"], b["pool_stride"]) == (3, 2):
+                pts.add("overlapping_pool")
+        if b["conv_valid"]:
+            pts.add("valid_conv")
+        pts.add("waves<=8" if f32_launch_shape(blob)[0] <= 8 else "waves>8")
+    return out
+
+
+# ---- float edges: activations on every op, subnormals, signed zeros, overflow, softmax, refusals ----
+F32_EDGE_GRAPHS = {
+    "ca13": dict(seed=8101, ncep=13, blocks=((12, 3, 7), (12, 3, 7)), n_labels=12),                      # conv -> ADD -> pool, twice
+    "ca16": dict(seed=8102, ncep=16, blocks=((12, 3, 7), (12, 3, 7)), n_labels=12),                      # ... with 16-byte rows
+    "dwpw": dict(seed=8103, ncep=13, blocks=(("dw", 1, 3, 7, 0), ("pw", 12, 0)), n_labels=12),           # depthwise + pointwise pair
+    "cd": dict(seed=8104, ncep=13, blocks=((12, 3, 7),), dense=((12, 1),), n_labels=12, add_bias=False),  # trunk kernel + kws_dense_f32_kernel
+    "cp13": dict(seed=8105, ncep=13, blocks=((12, 3, 7), (12, 3, 7)), n_labels=4, add_bias=False),       # conv -> pool twice, no additive constant but the head's
+    "c1": dict(seed=8106, ncep=13, blocks=((4, 3, 1),), n_labels=4, add_bias=False),                     # one un-pooled conv: a NaN is not dropped by a max
+}
+# op under test -> (op code, index among the nodes of that code); "head" / "hidden": FULLY_CONNECTED
+F32_EDGE_OPS = {
+    "ca13": dict(conv0=(1, 0), add0=(2, 0), pool0=(3, 0), conv1=(1, 1), add1=(2, 1), pool1=(3, 1), head=(4, 0)),
+    "ca16": dict(conv0=(1, 0), add0=(2, 0), pool0=(3, 0)),
+    "dwpw": dict(dw0=(6, 0), pool0=(3, 0), pw1=(1, 0), head=(4, 0)),
+    "cd": dict(conv0=(1, 0), pool0=(3, 0), hidden=(4, 0), head=(4, 1)),
+}
+F32_ACT_NAMES = {0: "none", 1: "relu", 2: "relu_n1_to_1", 3: "relu6"}
+_ACT_SLOT = {1: 3, 6: 3, 2: 0, 3: 5, 4: 0}                   # where a node's options hold its TfLiteFusedActivation
+
+
+def f32_bound_values():
+    """-1, 0, 1 and 6 and the float32 values one ulp either side of each: what an additive constant is set to so that a zero input lands a
+    pre-activation exactly there"""
+    out = []
+    for b in (-1.0, 0.0, 1.0, 6.0):
+        b = np.float32(b)
+        out += [b, np.nextafter(b, np.float32(-np.inf)), np.nextafter(b, np.float32(np.inf))]
+    return np.array(out, np.float32)
+
+
+def _nodes_of(nodes, code):
+    return [nd for nd in nodes if nd["op"] == code]
+
+
+def _additive(tensors, nodes, nd):
+    """the tensor of node nd's additive constant (conv / depthwise / FULLY_CONNECTED bias, ADD constant), or None"""
+    if nd["op"] == 2:
+        return tensors[[i for i in nd["in"] if tensors[i]["const"]][0]]
+    if nd["op"] in (1, 4, 6) and len(nd["in"]) > 2 and nd["in"][2] >= 0:
+        return tensors[nd["in"][2]]
+    return None
+
+
+def _act_edit(graph, op, act):
+    """Small-integer weights (-2 .. 2), every additive constant 0, every activation none -- then the op under test gets activation act and the
+    additive constant that feeds it (its own bias / ADD constant; for a pool the constant of the op in front) cycles through
+    f32_bound_values(): on an all-zero input every pre-activation of the op IS that constant, exactly."""
+    code, idx = F32_EDGE_OPS[graph][op]
+
+    def edit(tensors, nodes):
+        rng = np.random.default_rng(F32_EDGE_SEED)
+        for nd in nodes:
+            if nd["op"] in _ACT_SLOT:
+                nd["p"][_ACT_SLOT[nd["op"]]] = 0
+            if nd["op"] in (1, 4, 6):
+                tw = tensors[nd["in"][1]]
+                _fset(tw, rng.integers(-2, 3, tw["nbytes"] // 4))
+            ta = _additive(tensors, nodes, nd)
+            if ta is not None:
+                _fset(ta, np.zeros(ta["nbytes"] // 4))
+        target = _nodes_of(nodes, code)[idx]
+        target["p"][_ACT_SLOT[code]] = act
+        src = target
+        if code == 3:                                          # the op in front of the pool that adds a constant
+            k = nodes.index(target)
+            src = [nd for nd in nodes[:k] if _additive(tensors, nodes, nd) is not None][-1]
+        ta = _additive(tensors, nodes, src)
+        _fset(ta, np.resize(f32_bound_values(), ta["nbytes"] // 4))
+    return edit
+
+
+F32_EDGE_SEED = 20241019
+
+
+def _scale(tensors, nd, which, k):
+    """multiply a node's weights ("w") or additive constant ("b") by 2^k (exact)"""
+    t = tensors[nd["in"][1]] if which == "w" else _additive(tensors, None, nd)
+    if t is not None:
+        _fset(t, _fget(t) * np.float32(2.0) ** k)
+
+
+def _subnormal_edit(flushed):
+    """block 0's weights x 2^-120 (its additive constant x 2^-132), the next multiplying op's weights x 2^+100, every later additive constant
+    x 2^-32 (so that it does not swamp what block 0 hands on).  With inputs of 2^-12 N(0, 2^2) every block-0 activation is subnormal (or zero)
+    and the logits are normal.  flushed: the twin whose block 0 produces zeros -- what a flush of its outputs would leave."""
+    def edit(tensors, nodes):
+        mult = [nd for nd in nodes if nd["op"] in (1, 4, 6)]
+        _scale(tensors, mult[0], "w", -120)
+        _scale(tensors, mult[0], "b", -132)
+        _scale(tensors, mult[1], "w", 100)
+        first = nodes.index(mult[0])
+        for nd in nodes[first + 1:]:
+            if nd["op"] in (1, 2, 4, 6):
+                if nd["op"] == 2 and nodes.index(nd) < nodes.index(mult[1]):
+                    _scale(tensors, nd, "b", -132)              # block 0's own ADD
+                else:
+                    _scale(tensors, nd, "b", -32)
+        if flushed:
+            for nd in nodes[first:nodes.index(mult[1])]:
+                for t in ((tensors[nd["in"][1]] if nd["op"] in (1, 6) else None), _additive(tensors, nodes, nd) if nd["op"] in (1, 2, 6) else None):
+                    if t is not None:
+                        _fset(t, np.zeros(t["nbytes"] // 4))
+    return edit
+
+
+def _zeros_edit(value):
+    """every additive constant of the graph := value (+0.0 or -0.0)"""
+    def edit(tensors, nodes):
+        for nd in nodes:
+            ta = _additive(tensors, nodes, nd) if nd["op"] in (1, 2, 4, 6) else None
+            if ta is not None:
+                _fset(ta, np.full(ta["nbytes"] // 4, value, np.float32))
+    return edit
+
+
+def _overflow_edit(act):
+    """block 0's weights become |w| 2^100 and its activation act: with the rows of f32_case_inputs(("signed", 40)) -- finite values of 2^40 N(0, 2^2),
+    all positive in rows 0 .. 31, all negative in rows 32 .. 47, mixed behind -- every product overflows: the sums are +inf, -inf, and NaN (inf - inf)"""
+    def edit(tensors, nodes):
+        cv = [nd for nd in nodes if nd["op"] in (1, 6)][0]
+        tw = tensors[cv["in"][1]]
+        _fset(tw, np.abs(_fget(tw)))
+        _scale(tensors, cv, "w", 100)
+        cv["p"][3] = act
+    return edit
+
+
+def _softmax_edit(beta=None, apart=None, equal=False):
+    def edit(tensors, nodes):
+        if beta is not None:
+            _nodes_of(nodes, 5)[0]["beta"] = beta
+        fc = _nodes_of(nodes, 4)[-1]
+        tb = _additive(tensors, nodes, fc)
+        if apart is not None:
+            _fset(tb, np.arange(tb["nbytes"] // 4) * np.float32(apart))
+        if equal:
+            _fset(tensors[fc["in"][1]], np.zeros(tensors[fc["in"][1]]["nbytes"] // 4))
+            _fset(tb, np.full(tb["nbytes"] // 4, 1.5, np.float32))
+    return edit
+
+
+def _f32_edges():
+    """key "<family>/<graph>/<case>" -> dict(kw, edit, inputs): inputs "edge" (f32_edge_inputs), an exponent k (f32_inputs x 2^k) or ("signed", k)
+    (f32_case_inputs)"""
+    E = {}
+
+    def put(key, graph, edit, inputs="edge", **kw):
+        assert key not in E, key
+        E[key] = dict(kw=dict(F32_EDGE_GRAPHS[graph], **kw), edit=edit, inputs=inputs, graph=graph)
+
+    for graph, ops in F32_EDGE_OPS.items():
+        for op in ops:
+            for act, an in F32_ACT_NAMES.items():
+                put("act_%s_%s/%s" % (graph, op, an), graph, _act_edit(graph, op, act))
+    for graph in ("cp13", "dwpw"):
+        put("subnormal/%s" % graph, graph, _subnormal_edit(False), inputs=-12)
+    put("zeros/cp13_bias_free", "cp13", _zeros_edit(0.0))
+    put("zeros/cp13_neg_zero_bias", "cp13", _zeros_edit(-0.0))
+    put("zeros/ca13_neg_zero_constants", "ca13", _zeros_edit(-0.0))
+    put("zeros/dwpw_neg_zero_bias", "dwpw", _zeros_edit(-0.0))
+    put("overflow/cp13_relu6", "cp13", _overflow_edit(3), inputs=("signed", 40))
+    put("overflow/cp13_none", "cp13", _overflow_edit(0), inputs=("signed", 40))
+    put("overflow/c1_none", "c1", _overflow_edit(0), inputs=("signed", 40))              # NaN logits and scores in the mixed rows
+    put("softmax/beta_0.25", "cp13", _softmax_edit(beta=0.25))
+    put("softmax/beta_4", "cp13", _softmax_edit(beta=4.0))
+    put("softmax/logits_200_apart", "cp13", _softmax_edit(apart=200.0))
+    put("softmax/logits_equal", "cp13", _softmax_edit(equal=True))
+    for n in (2, 47, 48):
+        put("softmax/labels_%d" % n, "cp13", None, n_labels=n)
+    return E
+
+
+F32_EDGES = _f32_edges()
+
+
+def f32_edge_groups():
+    return sorted({k.split("/")[0] for k in F32_EDGES})
+
+
+def f32_edge_inputs(n_features, n=64):
+    """row 0 all +0.0, row 1 all -0.0, row 2 alternating +-0.0, rows 3 .. n - 17 small integers (-3 .. 3: with integer weights every sum is
+    exact), the last 16 rows N(0, 2^2)"""
+    rng = np.random.default_rng(F32_EDGE_SEED + 1)
+    x = rng.integers(-3, 4, (n, n_features)).astype(np.float32)
+    x[0] = 0.0
+    x[1] = -0.0
+    x[2] = np.where(np.arange(n_features) % 2, np.float32(-0.0), np.float32(0.0))
+    x[n - 16:] = (rng.standard_normal((16, n_features)) * np.float32(2.0)).astype(np.float32)
+    return x
+
+
+def f32_case_inputs(entry, n_features):
+    """the input rows of an F32_BLOCKINGS / F32_EDGES entry"""
+    if "inputs" not in entry:
+        return f32_inputs(n_features, entry["rows"])
+    if entry["inputs"] == "edge":
+        return f32_edge_inputs(n_features)
+    if isinstance(entry["inputs"], tuple):                    # ("signed", k)
+        x = (f32_inputs(n_features) * np.float32(2.0) ** entry["inputs"][1]).astype(np.float32)
+        x[:32] = np.abs(x[:32])
+        x[32:48] = -np.abs(x[32:48])
+        return x
+    return (f32_inputs(n_features) * np.float32(2.0) ** entry["inputs"]).astype(np.float32)
+
+
+def f32_all_cases():
+    """every table graph, blockings then edges: key -> entry (tools/make_golden.py, the golden and reference pins)"""
+    return dict([("blocking/" + k, e) for k, e in F32_BLOCKINGS.items()] + [("edge/" + k, e) for k, e in F32_EDGES.items()])
+
+
+def _set_weight(code, idx, value, element=5):
+    def edit(tensors, nodes):
+        tw = tensors[_nodes_of(nodes, code)[idx]["in"][1]]
+        w = _fget(tw)
+        w[element % w.size] = value
+        _fset(tw, w)
+    return edit
+
+
+def _f32_refusals():
+    """float graphs kws_create must refuse with KWS_ERROR_UNSUPPORTED_MODEL: key -> dict(kw, edit, says = a piece of kws_last_error's text)"""
+    g = F32_EDGE_GRAPHS
+    R = {
+        "labels_49": dict(kw=dict(g["cp13"], n_labels=49), edit=None, says="FULLY_CONNECTED"),
+        "taps_17": dict(kw=dict(g["cp13"], blocks=((12, 17, 7), (12, 3, 7))), edit=None, says="conv"),
+        "out_channels_65": dict(kw=dict(g["cp13"], blocks=((65, 3, 7), (12, 3, 7))), edit=None, says="conv"),
+        "pool_window_9": dict(kw=dict(g["cp13"], blocks=((12, 3, (9, 9, True)), (12, 3, 1))), edit=None, says="pool"),
+        "nine_conv_blocks": dict(kw=dict(g["cp13"], blocks=((8, 3, 1),) + (("pw", 8, 0),) * 8), edit=None, says="conv blocks"),
+        "weights_past_lds": dict(kw=dict(g["cp13"], blocks=((64, 16, 1), (64, 16, 7)), n_labels=2), edit=None, says="LDS"),
+    }
+    inf, nan = np.float32(np.inf), np.float32(np.nan)
+    for key, graph, code, idx, v in (("conv0_inf", "cp13", 1, 0, inf), ("conv1_neg_inf", "cp13", 1, 1, -inf), ("conv0_nan", "ca16", 1, 0, nan),
+                                     ("depthwise_nan", "dwpw", 6, 0, nan), ("pointwise_inf", "dwpw", 1, 0, inf), ("head_inf", "cp13", 4, 0, inf),
+                                     ("head_nan", "ca13", 4, 0, nan), ("hidden_nan", "cd", 4, 0, nan), ("dense_head_neg_inf", "cd", 4, 1, -inf)):
+        R["non_finite/" + key] = dict(kw=dict(g[graph]), edit=_set_weight(code, idx, v), says="non-finite")
+    return R
+
+
+F32_REFUSALS = _f32_refusals()
+
+# graphs whose waves serve a second and later clip in a batch of 2 x resident + 37 (tests/test_gpu_f32_edges.py): key -> (kw, what the plan must show)
+F32_MULTIPASS = {
+    "b512_prefetch": (dict(seed=8201, ncep=16, blocks=((30, 7, 7), (10, 7, 7))), dict(waves_max=8, prefetch=True)),
+    "b512_no_prefetch": (dict(seed=8202, ncep=13, blocks=((8, 3, 1), (9, 3, 7))), dict(waves_max=8, prefetch=False)),
+    "b1024": (dict(seed=8203, ncep=13, blocks=((30, 7, 7), (10, 7, 7))), dict(waves_min=9, prefetch=False)),
+    "dense": (dict(seed=8204, ncep=16, blocks=((30, 7, 7),), dense=((16, 1),), n_labels=4), dict(waves_max=8, prefetch=False)),
+}
+
+
+def f32_prefetch_eligible(blob):
+    """pf_ok of kws_nn_f32_generic.h: the first block's padded image and the feature vector are 16-byte aligned, and there is a second block"""
+    blocks, head = f32_graph_blocks(blob)
+    k = blocks[0]
+    lo = k["pad_left"] * k["in_c"]
+    hi = lo + k["in_w"] * k["in_c"]
+    return (lo | hi | head["n_features"]) & 3 == 0 and (k["rows"] * k["in_c"] + 3) // 4 <= 64 * 9 and len(blocks) > 1
+
+
+def f32_golden():
+    """tests/golden/f32_edges_l476.npz (tools/make_golden.py --only-f32-edges): f32_all_cases key -> dict(logits, scores [F32_GOLDEN_ROWS][labels]),
+    the reference's own float op registrations on the first F32_GOLDEN_ROWS input rows of the case"""
+    g = np.load(os.path.join(GOLDEN, "f32_edges_l476.npz"))
+    offs = np.cumsum([0] + [int(n) * F32_GOLDEN_ROWS for n in g["n_labels"]])
+    return {str(k): dict(logits=g["logits"][offs[i]:offs[i + 1]].reshape(F32_GOLDEN_ROWS, -1),
+                         scores=g["scores"][offs[i]:offs[i + 1]].reshape(F32_GOLDEN_ROWS, -1)) for i, k in enumerate(g["keys"])}
+
+
+def same_bits_or_both_nan(a, b):
+    a = np.asarray(a, np.float32)
+    b = np.asarray(b, np.float32)
+    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())

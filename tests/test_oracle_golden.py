@@ -348,3 +348,25 @@ def test_quant_edge_models_against_recorded_reference(group, oracle, tmp_path):
         assert (r["out"][rows] == g[key]["out"]).all() and (r["fc"][rows] == g[key]["fc"]).all(), key
         assert (quant_edge_digest(r["pooled"][rows]) == g[key]["pooled_sha"]).all(), key
         assert quant_edge_not_vacuous(key, r["edited"], r["fc"]) is None, (key, quant_edge_not_vacuous(key, r["edited"], r["fc"]))
+
+
+@pytest.mark.parametrize("group", sorted({k.split("/")[0] + "/" + k.split("/")[1] for k in __import__("kws_testlib").f32_all_cases()}))
+def test_f32_edge_graphs_against_recorded_reference(group, oracle, tmp_path):
+    """tests/golden/f32_edges_l476.npz: what the reference's float op registrations gave for every graph of kws_testlib.F32_BLOCKINGS and
+    F32_EDGES on the first 4 rows of its input set -- the restatement held to it where the reference is not built: logits bit for bit (NaN
+    for NaN), scores within 1e-7 with the same NaN mask (libm expf on both sides, as tests/test_oracle_vs_reference.py asks)."""
+    from kws_testlib import F32_GOLDEN_ROWS, OracleModel, f32_all_cases, f32_blob, f32_case_inputs, f32_golden, same_bits_or_both_nan
+    g = f32_golden()
+    cases = f32_all_cases()
+    assert sorted(g) == sorted(cases)
+    keys = [k for k in cases if k.startswith(group + "/")]
+    assert keys
+    for key in keys:
+        p = tmp_path / "m.kwsm"
+        p.write_bytes(f32_blob(cases[key]))
+        om = OracleModel(oracle, str(p))
+        n_t = len(om.tensor_bytes)
+        for i, x in enumerate(f32_case_inputs(cases[key], om.n_features)[:F32_GOLDEN_ROWS]):
+            s, taps = om.nn_invoke_f32(x, taps=True)
+            assert same_bits_or_both_nan(taps[n_t - 2], g[key]["logits"][i]), (key, i)
+            assert (np.isnan(s) == np.isnan(g[key]["scores"][i])).all() and np.abs(np.nan_to_num(s - g[key]["scores"][i])).max() <= 1e-7, (key, i)

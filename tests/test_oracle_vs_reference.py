@@ -413,3 +413,150 @@ def test_general_envelope_shapes_pinned(name, oracle, reference, tmp_path):
         if i < 2:
             distinct = np.unique(bits(a)).size
             assert distinct == 1 if name in G.ONE_VALUE else distinct >= G.MIN_DISTINCT, (name, i, distinct)
+
+
+# ---- the float32 network over every blocking and at float edges (kws_testlib.F32_BLOCKINGS / F32_EDGES; tests/test_gpu_f32_edges.py) ----
+def _f32_model(oracle, tmp_path, entry):
+    from kws_testlib import OracleModel, f32_blob, f32_case_inputs
+    blob = f32_blob(entry)
+    p = tmp_path / "m.kwsm"
+    p.write_bytes(blob)
+    om = OracleModel(oracle, str(p))
+    return blob, om, f32_case_inputs(entry, om.n_features)
+
+
+def _f32_pin(reference, om, blob, xs, key):
+    """the restatement against the reference's own float op registrations: every tensor up to the logits bit for bit (NaN for NaN), scores
+    within 1e-7 with the same NaN mask -- what test_random_graphs_through_reference_op_registrations asserts.  Returns the restatement's runs."""
+    runs = []
+    for i, x in enumerate(xs):
+        out, taps = reference.graph_run(blob, x)
+        oo, ot = om.nn_invoke_f32(x, taps=True)
+        assert all(_same_bits_or_both_nan(a, t) for a, t in zip(taps[:-1], ot[:-1]) if a.dtype == np.float32), (key, i)
+        assert (np.isnan(out) == np.isnan(oo)).all() and np.abs(np.nan_to_num(out - oo)).max() <= 1e-7, (key, i)
+        runs.append((oo, ot))
+    return runs
+
+
+def test_f32_blocking_table_covers_the_kernel():
+    """kws_testlib.F32_BLOCKINGS by the restated kws_nn_f32_pick_blocking (the GPU test asserts the library's own pick): every reachable
+    (depthwise, tb, ob, mode) has an entry whose block under test takes it -- all 15 conv (tb, ob) and all 5 depthwise tb, direct / fused /
+    staged, minus the fused forms of tb 1, which do not exist: 56 -- and, for register-blocked conv, one-step conv and depthwise blocks each,
+    the table holds: input channels that are and are not multiples of 4 (the 16-byte path of the 256-register build), output channels that are
+    no multiple of ob and of 4, a ragged last time block, 1 / even / 7 / 9..16 taps, a one-step block with fewer than 8 chain steps and one
+    with J % 8 != 0, a ragged SAME window fused and staged, a VALID pool that drops a tail, an overlapping pool (3 / 2), a VALID convolution,
+    and handles on both kernel builds (<= 8 and > 8 waves per workgroup).  Points that do not exist for a class are not asked of it: depthwise
+    has no ob / input-channel / tap-batching paths, tb 1 has no time blocks and cannot fuse."""
+    from kws_testlib import F32_BLOCKINGS, f32_blob, f32_blocking_coverage, f32_blocking_name, f32_graph_blocks
+    blobs = {k: f32_blob(e) for k, e in F32_BLOCKINGS.items()}
+    want = {"%s/tb%d/ob%d/%s" % (kind, tb, ob, mode) for kind, obs in (("conv", (1, 2, 4)), ("dw", (1,))) for tb in (1, 2, 4, 7, 8) for ob in obs
+            for mode in ("direct", "fused", "staged") if not (tb == 1 and mode == "fused")}
+    assert len(want) == 56
+    got = set()
+    for k, blob in blobs.items():
+        name = f32_blocking_name(f32_graph_blocks(blob)[0][F32_BLOCKINGS[k]["block"]])
+        assert name == k.split("#")[0], (k, name)
+        got.add(name)
+    assert got == want, sorted(want - got)
+    cov = f32_blocking_coverage(blobs)
+    common = {"out_c%4!=0", "same_ragged_staged", "valid_pool_drops_tail", "overlapping_pool", "valid_conv", "waves<=8", "waves>8"}
+    conv = {"in_c%4==0", "in_c%4!=0", "out_c%ob!=0", "taps1", "taps_even", "taps7", "taps9..16"}
+    assert cov["conv_tb>1"] >= common | conv | {"out_w%tb!=0", "same_ragged_fused"}, sorted((common | conv) - cov["conv_tb>1"])
+    assert cov["conv_tb1"] >= common | conv | {"J<8", "J>8,J%8!=0"}, sorted((common | conv) - cov["conv_tb1"])
+    assert cov["dw"] >= common | {"same_ragged_fused", "out_w%tb!=0"}, sorted(common - cov["dw"])
+
+
+@pytest.mark.parametrize("group", sorted({k.rsplit("/", 2)[0] for k in __import__("kws_testlib").F32_BLOCKINGS}))
+def test_f32_blocking_graphs_through_reference_op_registrations(group, oracle, reference, tmp_path):
+    """Every graph of F32_BLOCKINGS (grouped by kind and tb) on its input rows: the restatement == the reference's float op registrations,
+    tensor for tensor; and the comparison is not vacuous: in every block at least 99 % of the conv output positions are, for some input row,
+    strictly inside every clamp range behind them and the winner of their pooling window (kws_testlib.f32_reach_shares), so a wrong value
+    at any of them reaches a logit."""
+    from kws_testlib import F32_BLOCKINGS, f32_reach_shares
+    keys = [k for k in F32_BLOCKINGS if k.rsplit("/", 2)[0] == group]
+    assert keys
+    for key in keys:
+        blob, om, xs = _f32_model(oracle, tmp_path, F32_BLOCKINGS[key])
+        runs = _f32_pin(reference, om, blob, xs, key)
+        it = iter(runs)
+        shares = f32_reach_shares(blob, lambda x: next(it), xs)
+        assert min(shares) >= 0.99, (key, shares)
+        assert all(np.isfinite(oo).all() for oo, _ in runs), key
+
+
+@pytest.mark.parametrize("group", __import__("kws_testlib").f32_edge_groups())
+def test_f32_edge_graphs_through_reference_op_registrations(group, oracle, reference, tmp_path):
+    """Every graph of F32_EDGES on its input rows: the restatement == the reference's float op registrations, tensor for tensor (NaN for NaN).
+    And each case is what it says: an activation case lands, on the all-zero row, every pre-activation of its op on -1 / 0 / 1 / 6 or one
+    ulp beside, so the output there is those values clamped -- both bounds and an exact-bound value included; a subnormal case has every
+    block-0 activation subnormal or zero (most not zero), normal logits, and other logits than its twin with block 0 flushed to zero; the
+    zero-input rows of a bias-free graph give all-zero logits; an overflow case has block-0 outputs at the clamp of an infinity (6, or
+    +-FLT_MAX: ActivationFunctionWithMinMax clamps an infinity even with no activation) or NaN in every row; the softmax cases have the logit
+    gaps they name."""
+    import eon_import
+    from kws_testlib import (F32_EDGES, F32_EDGE_OPS, F32_FLT_MAX, OracleModel, _subnormal_edit, f32_act_range, f32_blob, f32_bound_values,
+                             f32_graph_blocks)
+    keys = [k for k in F32_EDGES if k.split("/")[0] == group]
+    assert keys
+    for key in keys:
+        e = F32_EDGES[key]
+        blob, om, xs = _f32_model(oracle, tmp_path, e)
+        runs = _f32_pin(reference, om, blob, xs, key)
+        tensors, nodes, _, _, _ = eon_import.parse_blob(blob)
+        n_t = len(tensors)
+        logits = np.stack([t[n_t - 2] for _, t in runs])
+        blocks, _ = f32_graph_blocks(blob)
+        conv0 = np.stack([t[blocks[0]["conv_nd"]["out"][0]] for _, t in runs])
+        if group.startswith("act_"):
+            op = group.split("_", 2)[2]
+            code, idx = F32_EDGE_OPS[e["graph"]][op]
+            nd = [n_ for n_ in nodes if n_["op"] == code][idx]
+            act = nd["p"][{1: 3, 6: 3, 2: 0, 3: 5, 4: 0}[code]]
+            lo, hi = f32_act_range(act)
+            out0 = np.asarray(runs[0][1][nd["out"][0]])                       # row 0: the all-zero input
+            n_ch = tensors[nd["out"][0]]["dims"][-1]
+            consts = np.resize(f32_bound_values(), n_ch)
+            want = np.minimum(np.maximum(consts, np.float32(lo)), np.float32(hi))
+            assert (bits(out0.reshape(-1, n_ch)) == bits(want)[None, :]).all(), key
+            if act:
+                assert (consts == np.float32(lo)).any() and (consts < lo).any() and (consts > lo).any(), key
+                assert (want == np.float32(lo)).any(), key
+            if act in (2, 3):
+                assert (consts == np.float32(hi)).any() and (consts > hi).any() and (want == np.float32(hi)).any(), key
+            allv = np.concatenate([np.asarray(t[nd["out"][0]]).reshape(-1) for _, t in runs])
+            assert len(np.unique(allv)) >= 5, key                             # and the integer rows move it
+        elif group == "subnormal":
+            tiny = float(np.finfo(np.float32).tiny)
+            last0 = blocks[0]["pool_nd"]["out"][0]
+            for tid in (blocks[0]["conv_nd"]["out"][0], last0):
+                v = np.stack([t[tid] for _, t in runs])
+                assert (np.abs(v) < tiny).all() and (v != 0).mean() > 0.3, (key, tid)
+            assert (np.abs(logits) >= tiny).all() and np.isfinite(logits).all(), key
+            pf = tmp_path / "flushed.kwsm"
+            pf.write_bytes(f32_blob(dict(kw=e["kw"], edit=_subnormal_edit(True))))
+            of = OracleModel(oracle, str(pf))
+            for x, lg in zip(xs, logits):
+                _, tf = of.nn_invoke_f32(x, taps=True)
+                assert (np.asarray(tf[last0]) == 0).all() and (bits(tf[n_t - 2]) != bits(lg)).any(), key
+        elif group == "zeros":
+            assert all((x == 0).all() for x in xs[:3]) and np.signbit(xs[1]).all() and np.signbit(xs[2]).any() and not np.signbit(xs[2]).all()
+            if key.endswith("bias_free"):
+                assert (logits[:3] == 0).all(), key
+            assert len(np.unique(logits[3:])) > 8, key
+        elif group == "overflow":
+            top = 6.0 if key.endswith("relu6") else F32_FLT_MAX
+            assert (conv0[:32] == np.float32(top)).all() and np.isnan(conv0[48:]).any(), key          # +inf clamped; inf - inf
+            assert (conv0[32:48] == np.float32(0.0 if key.endswith("relu6") else -top)).all(), key    # -inf clamped
+            # what reaches the logits: MAX_POOL_2D's std::max drops a NaN, FULLY_CONNECTED clamps an infinity to +-FLT_MAX
+            assert (np.isnan(logits) | (np.abs(logits) == np.float32(F32_FLT_MAX))).any(), key
+            if key == "overflow/c1_none":
+                assert np.isnan(logits[48:]).any() and np.isnan(np.stack([o for o, _ in runs])).any() and not np.isnan(logits).all(), key
+            if key.endswith("relu6"):
+                assert np.isfinite(logits[:48]).all() and (np.abs(logits[:48]) < 1e6).all(), key           # clamped back to 6 (and to 0)
+            assert np.isfinite(xs).all(), key
+        elif key == "softmax/logits_200_apart":
+            assert (np.diff(np.sort(logits, axis=1), axis=1) > 150).all() and (np.stack([o for o, _ in runs]) == 0).any(), key
+        elif key == "softmax/logits_equal":
+            assert (logits == logits[:, :1]).all(), key
+        elif group == "softmax":
+            assert logits.shape[1] == e["kw"]["n_labels"] and len(np.unique(logits)) > 8, key

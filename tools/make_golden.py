@@ -19,6 +19,7 @@ Without arguments: leaves_l476, e2e_l476, deep_l476, continuous_l476, f32_twin_l
   --only-other-length      other_length_l476.npz    run_classifier on windows of another length (1 .. 49 frames)
   --only-mfe-other-length  mfe_other_length_l432.npz  the same for the MFE-block model, composed from the L432 copy's leaves
   --only-quant-edges       quant_edges_l476.npz     the int8 graphs at the edges of their quantisation (kws_testlib.QUANT_EDGES)
+  --only-f32-edges         f32_edges_l476.npz       the float32 graphs over every blocking and at float edges (kws_testlib.F32_BLOCKINGS / F32_EDGES)
 """
 import os
 import sys
@@ -190,6 +191,28 @@ def quant_edges(ref):
     out["out"], out["fc"], out["pooled_sha"] = np.concatenate(out["out"]), np.concatenate(out["fc"]), np.stack(out["pooled_sha"])
     np.savez_compressed(os.path.join(GOLDEN, "quant_edges_l476.npz"), **out)
     print("quant_edges_l476.npz", os.path.getsize(os.path.join(GOLDEN, "quant_edges_l476.npz")), "bytes;", len(keys), "models")
+
+
+def f32_edges(ref):
+    """Every graph of kws_testlib.F32_BLOCKINGS and F32_EDGES through the reference's own float op registrations on the first
+    F32_GOLDEN_ROWS rows of its input set: the logits (the FULLY_CONNECTED output) and the scores.  Recorded results only: models and
+    inputs are regenerated in the tests."""
+    import eon_import
+    from kws_testlib import F32_GOLDEN_ROWS, f32_all_cases, f32_blob, f32_case_inputs
+    cases = f32_all_cases()
+    keys = sorted(cases)
+    out = {"keys": np.array(keys), "n_labels": [], "logits": [], "scores": []}
+    for key in keys:
+        blob = f32_blob(cases[key])
+        tens, _, t_in, _, _ = eon_import.parse_blob(blob)
+        for x in f32_case_inputs(cases[key], tens[t_in]["nbytes"] // 4)[:F32_GOLDEN_ROWS]:
+            s, taps = ref.graph_run(blob, x)
+            out["scores"].append(np.float32(s)); out["logits"].append(np.float32(taps[len(tens) - 2]))
+        out["n_labels"].append(len(s))
+    out["n_labels"] = np.int32(out["n_labels"])
+    out["logits"], out["scores"] = np.concatenate(out["logits"]), np.concatenate(out["scores"])
+    np.savez_compressed(os.path.join(GOLDEN, "f32_edges_l476.npz"), **out)
+    print("f32_edges_l476.npz", os.path.getsize(os.path.join(GOLDEN, "f32_edges_l476.npz")), "bytes;", len(keys), "graphs")
 
 
 def qfb(synth, cfg):
@@ -378,6 +401,8 @@ def main():
         return graphs(ref)
     if "--only-quant-edges" in sys.argv:
         return quant_edges(ref)
+    if "--only-f32-edges" in sys.argv:
+        return f32_edges(ref)
     synth = Oracle()          # only used for kwso_synth_fill (shared integer generator)
     cfg = L476_CONFIG()
     os.makedirs(GOLDEN, exist_ok=True)

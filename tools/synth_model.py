@@ -185,12 +185,15 @@ def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=2
 def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((30, 7, 7), (10, 7, 7)), n_labels=4,
                      conv_bias=False, add_bias=True, num_filters=32, raw_samples=16000, fft_length=256, frame_length=0.02,
                      frame_stride=0.02, pre_cof=0.98, dsp_block="mfcc", logit_std=None, quantize_filterbank=False, edit=None, dense=None,
-                     calib=None):
+                     calib=None, conv_valid=()):
     """blocks: sequence of
          (out_channels, taps, pool)              CONV_2D 1xK (+ optional int32 bias) -> ADD(int8 per-channel)+ReLU -> MAX_POOL
          ("dw", depth_mult, taps, pool, act)     DEPTHWISE_CONV_2D 1xK with int32 bias and fused activation -> MAX_POOL
          ("pw", out_channels, act)               CONV_2D 1x1 with int32 bias and fused activation (pointwise)
        (pool 1 = no pooling node, a negative pool = VALID padding: the ragged tail of the time axis is dropped; act: TfLiteFusedActivation 0 none, 1 relu, 3 relu6).
+       A pool may also be a tuple (window, stride, valid): a MAX_POOL_2D whose stride differs from its window (overlapping or skipping windows), with
+       VALID (valid true) or SAME padding.  conv_valid: indices into blocks of the convolutions with VALID padding (output rows = rows - taps + 1)
+       instead of SAME.  Neither draws anything: with integer pools and conv_valid=() every blob is the one the same arguments gave before.
        logit_std: None = the FULLY_CONNECTED layer as drawn (random weights and biases: one class usually wins every clip by tens
        of logit units, the softmax is saturated and a score says nothing about the logits behind it); a number = the head is
        calibrated (calibrate_head): scale and biases are set so that, over standardised random feature matrices -- which is what
@@ -244,20 +247,31 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
         nonlocal cur, w
         if pool in (0, 1):
             return
-        valid = pool < 0                                                # negative: VALID padding (floor, a ragged tail is dropped)
-        pool = abs(pool)
+        if isinstance(pool, tuple):                                     # (window, stride, valid)
+            pool, stride, valid = pool
+        else:
+            valid = pool < 0                                            # negative: VALID padding (floor, a ragged tail is dropped)
+            pool = stride = abs(pool)
         t4 = T(9, [1, w, 1, c_out], scale=[cur_scale], zero=[cur_zp])
         node(0, [cur, shape_const([1, w, 1, c_out])], [t4])
-        pw = w // pool if valid else (w + pool - 1) // pool
-        assert pw >= 1 and (pw - 1) * pool < w           # SAME: the last window may be ragged (clipped to the tensor)
+        pw = (w - pool) // stride + 1 if valid else (w + stride - 1) // stride      # ComputeOutSize (kernels/padding.h)
+        assert pw >= 1 and (pw - 1) * stride < w         # SAME: the last window may be ragged (clipped to the tensor)
         tp = T(9, [1, pw, 1, c_out], scale=[cur_scale], zero=[cur_zp])
-        node(3, [t4], [tp], [2 if valid else 1, 1, pool, 1, pool, 0])   # VALID / SAME, stride (w1,hP), filter (w1,hP)
+        node(3, [t4], [tp], [2 if valid else 1, 1, stride, 1, pool, 0])   # VALID / SAME, stride (w1,hP), filter (w1,hP)
         w = pw
         t5 = T(9, [1, 1, w, c_out], scale=[cur_scale], zero=[cur_zp])
         node(0, [tp, shape_const([1, 1, w, c_out])], [t5])
         cur = t5
 
-    for blk in blocks:
+    def conv_rows(bi, taps):                                                # (TfLitePadding, output rows) of block bi's convolution
+        nonlocal w
+        if bi in conv_valid:
+            assert w - taps + 1 >= 1
+            w = w - taps + 1
+            return 2
+        return 1
+
+    for bi, blk in enumerate(blocks):
         if blk[0] == "dw":
             _, mult, taps, pool, act = blk
             c_out = c * mult
@@ -267,8 +281,9 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
             bias = rng.integers(-300, 300, c_out).astype(np.int32)
             tb = T(2, [c_out], True, [cur_scale * s_ for s_ in wscales], [0] * c_out, bias.tobytes())
             out_scale, out_zp = rscale(0.03, 0.12), int(rng.integers(-128, -90)) if act else int(rng.integers(-30, 40))
+            padding = conv_rows(bi, taps)
             tc = T(9, [1, 1, w, c_out], scale=[out_scale], zero=[out_zp])
-            node(6, [cur, tw, tb], [tc], [1, 1, 1, act, 1, 1, mult])          # SAME, stride 1
+            node(6, [cur, tw, tb], [tc], [padding, 1, 1, act, 1, 1, mult])    # SAME (or VALID), stride 1
             cur, cur_scale, cur_zp = tc, out_scale, out_zp
             add_pool(pool)
             c = c_out
@@ -294,8 +309,9 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
         bias = rng.integers(-200, 200, oc).astype(np.int32) if conv_bias else np.zeros(oc, np.int32)
         tb = T(2, [oc], True, [cur_scale * s for s in wscales], [0] * oc, bias.tobytes())
         out_scale, out_zp = rscale(0.03, 0.12), int(rng.integers(-30, 40))
+        padding = conv_rows(bi, taps)
         tc = T(9, [1, 1, w, oc], scale=[out_scale], zero=[out_zp])
-        node(1, [cur, tw, tb], [tc], [1, 1, 1, 0, 1, 1])                    # SAME, stride 1, no activation
+        node(1, [cur, tw, tb], [tc], [padding, 1, 1, 0, 1, 1])              # SAME (or VALID), stride 1, no activation
         cur, cur_scale, cur_zp = tc, out_scale, out_zp
         if add_bias:
             t3 = T(9, [1, w, oc], scale=[cur_scale], zero=[cur_zp])
