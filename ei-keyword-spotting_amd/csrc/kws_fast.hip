@@ -848,15 +848,25 @@ __device__ __forceinline__ void fast_dwconv(const KwsFastBlock &k, const float *
 //  update entry upd[n_frames - 1] takes out the row it puts in) and the columns past n_cepstral work on a copy of the last column, so what is not stored is
 //  finite wherever what is stored is -- but for a row group without any live row (fewer than 40 frames), whose lanes are left out.  (The NaN path through the network would NOT do: the activation clamps' fminf /
 //  fmaxf drop a NaN operand and turn an infinity into a finite bound.)
-template <int CR, int CG, bool DEFER, bool SPLIT = false>
+//  SAFE (SPLIT only): the caller has checked (NG - 1) CR + SAFE <= n_frames -- a wave-uniform test, once per clip -- so every row group has a live row and the
+//  row test r0 + i < n_frames of a lane's first SAFE values is true in EVERY lane: those values carry no compare, no select and no clamp of the row index
+//  (each of them selected the same operand before: no bit changes).  SAFE = 0 is the general form, every value under its own test.  What is constant per
+//  lane and column block is formed once per block there, not once per value: the store's base and row stride (the sink and 0 for a lane whose column has
+//  no place in the row), and the guard's on/off -- a lane that is not `act` carries the coefficients 0, 0: its term is 0 x |finite| + 0 times a finite
+//  1 / (deviation + eps), and fma(0, 0, vacc) is vacc bit for bit (vacc is a sum of squares from +0: never -0).
+template <int CR, int CG, bool DEFER, bool SPLIT = false, int SAFE = 0>
 __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float *__restrict__ cnt_tab, const int *__restrict__ upd, int fs,
                                            float inv_win, const float *__restrict__ guard_tab, float level, float abs_scale, bool silent, float sys_t2, int piv_row, const float *__restrict__ mref, bool c0_exact, int lane, int nfr, int ncep,
                                            const float *__restrict__ ext_tab, float *__restrict__ sink, int in_cp = 0)
 {
     static_assert(!SPLIT || (DEFER && CG == 16), "the split store is written for column blocks of 16 and the deferred guard sum");
+    static_assert(SAFE == 0 || (SPLIT && SAFE <= CR), "rows known to be live: the split form only");
     constexpr int NG = KWS_WAVE / CG;
     const int cgrp = min(lane / CG, NG - 1), cl = lane - (lane / CG) * CG;
-    const bool lane_on = lane < NG * CG;
+    const bool lane_on = SPLIT || lane < NG * CG;      // (SPLIT: four groups of 16, every lane of the wave)
+    // row r0 + i of this lane against the frame count, and the row it reads (a row past the last frame reads the last one)
+#define CMVN_ROW_LIVE(r0v, i) ((i) < SAFE || (r0v) + (i) < nfr)
+#define CMVN_ROW(r0v, i) ((i) < SAFE ? (r0v) + (i) : min((r0v) + (i), nfr - 1))
     const int r0 = cgrp * CR;
     const int nfr8 = (nfr + 7) & ~7;
     const float *cnt = cnt_tab + cgrp * nfr8;          // rows padded to a multiple of 8 with zeros
@@ -883,7 +893,7 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
             KWS_OPAQUE3(cg_);
             const int r0_ = cg_ * CR;
 #pragma unroll
-            for (int i = 0; i < CR - 1; ++i) u[i] = upd[min(r0_ + i, nfr - 1)];
+            for (int i = 0; i < CR - 1; ++i) u[i] = upd[CMVN_ROW(r0_, i)];
             if (ext_tab) {
                 const float *ext = ext_tab + cg_ * (1 + 2 * KWS_FAST_CMVN_EXT);
                 m0 = ext[0];
@@ -893,7 +903,7 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
         }
 #endif
         const int c = cb + cl;
-        const bool act = lane_on && c < ncep && r0 < nfr;
+        const bool act = lane_on && c < ncep && (SAFE > 0 || r0 < nfr);
         float *col = img + min(c, ncep - 1);
         // every read of the column block goes out in one batch: the pivot, the lane's own rows, the rows the updates name.
         // The pivot (round 6): row piv_row of the column -- the clip's first digitally silent frame when it has one, else its first row.  With the
@@ -911,16 +921,17 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
         // systematically instead of randomly: the alternative coefficient is the larger one measured on such clips.
         const bool is_c0 = c0_exact && cb + cl == 0;
         // (level arrives multiplied by abs_scale = sqrt(live rows / rows): the rows of digitally silent frames carry the reference's own values)
-        const float g_abs = __fmaf_rn(gcol.y, level, gcol.x * abs_scale);
+        float g_abs = __fmaf_rn(gcol.y, level, gcol.x * abs_scale);
+        if constexpr (SPLIT) g_abs = act ? g_abs : 0.0f;
         // the per-|window mean| coefficient: gcol.w where the reference's sequential window sums round SYSTEMATICALLY (runs of identical or nearly identical
         // values: a clip with silent frames; a near-constant column, below), gcol.z where they round at random.  Column 0: gcol.w = its means replayed.
         float g_rel = (cb + cl == 0 ? c0_exact : silent) ? gcol.w : gcol.z;
         float mr[CR];
 #pragma unroll
-        for (int i = 0; i < CR; ++i) mr[i] = (c0_exact && cb == 0) ? mref[min(r0 + i, nfr - 1)] : 0.0f;
+        for (int i = 0; i < CR; ++i) mr[i] = (c0_exact && cb == 0) ? mref[CMVN_ROW(r0, i)] : 0.0f;
         float own[CR];
 #pragma unroll
-        for (int i = 0; i < CR; ++i) own[i] = col[min(r0 + i, nfr - 1) * fs];
+        for (int i = 0; i < CR; ++i) own[i] = col[CMVN_ROW(r0, i) * fs];
         float dl[CR - 1], da[CR - 1];
 #pragma unroll
         for (int i = 0; i < CR - 1; ++i) { dl[i] = col[u[i] & 0xffff]; da[i] = col[(unsigned)u[i] >> 16]; }
@@ -933,7 +944,7 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
             float T0 = 0.0f, T1 = 0.0f, U0 = 0.0f, U1 = 0.0f;          // this lane's rows
 #pragma unroll
             for (int i = 0; i < CR; ++i) {
-                const float d = (lane_on && r0 + i < nfr) ? own[i] - piv : 0.0f;
+                const float d = (lane_on && CMVN_ROW_LIVE(r0, i)) ? own[i] - piv : 0.0f;
                 if (i & 1) { T1 += d; U1 = __fmaf_rn(d, d, U1); } else { T0 += d; U0 = __fmaf_rn(d, d, U0); }
             }
             float T = T0 + T1, U = U0 + U1;
@@ -976,6 +987,7 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
         if constexpr (DEFER) {
             const float m0 = S * inv_win, v0 = fmaxf(__fmaf_rn(-m0, m0, Q * inv_win), 0.0f), am0 = m0 + piv;
             g_rel = (cb + cl != 0 && v0 < sys_t2 * (am0 * am0)) ? gcol.w : g_rel;
+            if constexpr (SPLIT) g_rel = act ? g_rel : 0.0f;
         }
         float o[CR], gq[DEFER ? CR : 1];
 #pragma unroll
@@ -1002,6 +1014,8 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
             // last column); past in_cp it has no place in the row.
             _Float16 *const hcol = (_Float16 *)((char *)img + 4 * cb) + cl;
             const bool col_on = lane_on && c < in_cp;
+            _Float16 *dst_i = col_on ? hcol + r0 * (2 * fs) : (_Float16 *)sink;      // this lane's row r0 + i, or the sink with a row stride of 0
+            const int dst_step = col_on ? 2 * fs : 0;
             // (the factor doubles as the overflow flag -- it turns into a NaN, and with it whatever the lane stores from then on: one register instead of two)
             float sc = c < ncep ? (float)(1 << KWS_SPLIT22_PRE_EXP) : 0.0f;
             // (the values are pinned behind the sync: converted ahead of it -- nothing but the stores has to wait -- every value is two registers, hi and lo, where
@@ -1010,17 +1024,17 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
             for (int i = 0; i < CR; ++i) asm volatile("" : "+v"(o[i]));
 #pragma unroll
             for (int i = 0; i < CR; ++i) {
-                const int r = r0 + i;
-                const bool live = act && r < nfr;
+                const bool live = CMVN_ROW_LIVE(r0, i);             // (a constant for i < SAFE; the lane's own on/off is in dst_i and in gq[i] already)
                 _Float16 hi, lo;
                 const float d = kws_split22(o[i], sc, &hi, &lo);
-                _Float16 *const dst = (col_on && r < nfr) ? hcol + r * (2 * fs) : (_Float16 *)sink;
+                _Float16 *const dst = live ? dst_i : (_Float16 *)sink;
                 dst[0] = hi;
                 dst[KWS_FAST_PRE_LO / 2] = lo;
+                dst_i += dst_step;
                 sc = __fmaf_rn(d, 0.0f, sc);                        // unchanged, or a NaN where a value left binary16's range (see above)
                 vacc = live ? __fmaf_rn(gq[i], gq[i], vacc) : vacc;
             }
-            vacc = r0 < nfr ? __fmaf_rn(sc, 0.0f, vacc) : vacc;
+            vacc = (SAFE > 0 || r0 < nfr) ? __fmaf_rn(sc, 0.0f, vacc) : vacc;
         } else {
 #pragma unroll
         for (int i = 0; i < CR; ++i) {
@@ -1033,6 +1047,8 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
     }
     WAVE_SYNC();
     return vacc;
+#undef CMVN_ROW_LIVE
+#undef CMVN_ROW
 }
 
 // PROF: development aid -- shader-clock totals per phase of wave 0 of workgroup 0 (tools/gpu_fast_phase_profile.py)
@@ -1626,6 +1642,41 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
             // Stores without a branch per value: rows past the last frame and coefficients that are not this tile's go to a
             // per-lane sink.
             float *const sink = KWS_FAST_SINK + lane_l;
+            // The transform's coefficient 0 -- sum_k log-mel[r][k] / sqrt(NF), replaced by the log frame energy below -- is the frame's mean
+            // log-mel level x sqrt(NF): what the fp32 rounding of the spectral phase scales with (the guard's `level`, kws_fast.h).  The
+            // lanes of column 0 (lm == 0) hold it for sixteen rows each.
+            // It is summed under the row predicate of the stores.
+#if KWS_FAST_WPS >= 3
+            // (three waves per SIMD) What is constant per lane is formed once, not once per store: the address of the lane's first row and its row stride --
+            // the sink and 0 where the coefficient is not this tile's.  The row test is taken per value only where a lane can fail it: with 48 frames or
+            // more (wave-uniform, once per clip; the usual 49) every row of row tiles 0 - 2 is live, and only tile 3 carries the test.
+            float *dbase[2];
+            int dstep[2];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const int n = 16 * nt + lm;
+                const bool col_ok = n <= NF / 2 && n > 0;
+                dbase[nt] = col_ok ? img + 4 * lq * fs + n : sink;
+                dstep[nt] = col_ok ? fs : 0;
+            }
+            auto dct_store = [&](auto full_c) {
+                constexpr int FULL = decltype(full_c)::value;            // row tiles known to hold live rows only
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const bool row_ok = mt < FULL || 16 * mt + 4 * lq + i < nfr;
+#pragma unroll
+                        for (int nt = 0; nt < 2; ++nt) {
+                            float *const dst = dbase[nt] + (16 * mt + i) * dstep[nt];
+                            *(row_ok ? dst : sink) = acc[mt][nt][i];
+                        }
+                        lvl_sum += row_ok ? fabsf(acc[mt][0][i]) : 0.0f;
+                    }
+            };
+            if (nfr >= 48) dct_store(std::integral_constant<int, 3>()); else dct_store(std::integral_constant<int, 0>());
+            if (lane_l < nfr) img[lane_l * fs] = e0;
+#else
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -1639,13 +1690,11 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                     }
                 }
             if (lane_l < nfr) img[lane_l * fs] = e0;
-            // The transform's coefficient 0 -- sum_k log-mel[r][k] / sqrt(NF), replaced by the log frame energy above -- is the frame's mean
-            // log-mel level x sqrt(NF): what the fp32 rounding of the spectral phase scales with (the guard's `level`, kws_fast.h).  The
-            // lanes of column 0 (lm == 0) hold it for sixteen rows each.
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) lvl_sum += (16 * mt + 4 * lq + i < nfr) ? fabsf(acc[mt][0][i]) : 0.0f;      // (the row predicate of the stores above)
+#endif
             lvl_sum = lm == 0 ? lvl_sum : 0.0f;
             WAVE_SYNC();
         }
@@ -1772,7 +1821,13 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
             }
 #if KWS_FAST_WPS >= 3
             // (this build runs plans with KwsFastPlan::presplit only -- the launcher checks --: ONE cmvnw instantiation, whose stores are block 0's operands)
-            vlane = fast_cmvn<13, 16, true, true>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink, FP.blk[0].in_cp);
+            // Two copies of it, picked once per clip by a wave-uniform test on the frame count: with 3 x 13 + 9 frames or more (the usual 49) only the last
+            // four values of a lane can lie past the last frame, and the other nine run without their row predicates (fast_cmvn: SAFE).
+            // (The <8, 5> form -- mel filters of 5 - 8 taps in front of 40 filters, no shipped model -- spills a third register with the second copy
+            // compiled in: it keeps the general one.)
+            constexpr bool TWO_COPIES = !(NZ == 8 && DG == 5);
+            if (TWO_COPIES && nfr >= 3 * 13 + 9) vlane = fast_cmvn<13, 16, true, true, 9>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink, FP.blk[0].in_cp);
+            else vlane = fast_cmvn<13, 16, true, true>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink, FP.blk[0].in_cp);
 #else
             if (cr == 13) vlane = fast_cmvn<13, 16, QCP == 0>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink);
             else vlane = fast_cmvn<17, 20, QCP == 0>(img, cnt_tab, upd_tab, fs, inv_win, guard_tab, level, abs_scale, silent, FP.sys_t2, piv_row, elog, c0_exact, lane_m, nfr, ncep, ext_tab, csink);
