@@ -138,19 +138,22 @@ int kws_fast_lds_fragments(const kws_handle *h)
             if (h->fast_fused.blk[b].hconv && h->fast_fused.blk[b].h_b_off >= 0) mask |= 1 << b;
     return mask;
 }
-EI_IMPULSE_ERROR kws_fast_fallback_count(kws_handle *h, size_t *count)
+// the count of one of the handle's clip lists (kws_internal.h: d_flags, d_flags2) once everything enqueued has finished; 0 before the first fast call
+static EI_IMPULSE_ERROR read_list_count(kws_handle *h, int *kws_handle::*list, size_t *count)
 {
     if (!h || !count) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     *count = 0;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->d_flags) return EI_IMPULSE_OK;
+    if (!(h->*list)) return EI_IMPULSE_OK;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
     int n = 0;
-    HIP_TRY(hipMemcpy(&n, h->d_flags, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n, h->*list, sizeof(int), hipMemcpyDeviceToHost));
     *count = (size_t)n;
     return EI_IMPULSE_OK;
 }
+EI_IMPULSE_ERROR kws_fast_fallback_count(kws_handle *h, size_t *count) { return read_list_count(h, &kws_handle::d_flags, count); }
+EI_IMPULSE_ERROR kws_fast_exact_count(kws_handle *h, size_t *count) { return read_list_count(h, &kws_handle::d_flags2, count); }
 
 EI_IMPULSE_ERROR kws_fast_guard(const kws_handle *h, int tier, float *coef)
 {
@@ -209,20 +212,6 @@ EI_IMPULSE_ERROR kws_set_logits_tap(kws_handle *h, float *logits)
     return EI_IMPULSE_OK;
 }
 
-EI_IMPULSE_ERROR kws_fast_exact_count(kws_handle *h, size_t *count)
-{
-    if (!h || !count) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    *count = 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->d_flags2) return EI_IMPULSE_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    int n = 0;
-    HIP_TRY(hipMemcpy(&n, h->d_flags2, sizeof(int), hipMemcpyDeviceToHost));
-    *count = (size_t)n;
-    return EI_IMPULSE_OK;
-}
-
 static EI_IMPULSE_ERROR ensure_flags(kws_handle *h, size_t B)
 {
     if (B + 1 <= h->flags_cap) return EI_IMPULSE_OK;
@@ -238,9 +227,42 @@ static EI_IMPULSE_ERROR ensure_flags(kws_handle *h, size_t B)
     return EI_IMPULSE_OK;
 }
 
+// s_cep for B clips
+static EI_IMPULSE_ERROR ensure_cep(kws_handle *h, size_t B)
+{
+    if (B <= h->cep_cap) return EI_IMPULSE_OK;
+    if (h->s_cep) (void)hipFree(h->s_cep);
+    h->s_cep = nullptr; h->cep_cap = 0;
+    HIP_TRY(hipMalloc((void **)&h->s_cep, B * h->model.nn_input_frame_size * sizeof(float)));
+    h->cep_cap = B;
+    return EI_IMPULSE_OK;
+}
+
+// the launchers take the clip count as an int; the tuned kernels read the PCM in 16-byte pieces
+static EI_IMPULSE_ERROR check_batch(size_t B) { return B > 0x7fffffff ? fail(KWS_ERROR_BAD_ARGUMENT, "batch too large") : EI_IMPULSE_OK; }
+static EI_IMPULSE_ERROR check_batch_pcm(const void *pcm, size_t B)
+{
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
+    return ((uintptr_t)pcm & 15) != 0 ? fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned") : EI_IMPULSE_OK;
+}
+
+// P for windows that sit in rolling buffers of ring_rows rows with head ring_head (continuous mode, kws_streams_*); ring_rows == 0: plain windows
+static KwsDspPlan ring_plan(const KwsDspPlan &P, int ring_rows, int ring_head)
+{
+    KwsDspPlan PR = P;
+    PR.ring_rows = ring_rows;
+    PR.ring_head = ring_rows > 0 ? ((ring_head % ring_rows) + ring_rows) % ring_rows : 0;      // (the fast kernel's ring() wraps with one subtraction: head < rows)
+    return PR;
+}
+
+// Does kws_mfe_norm_kernel serve P's matrix?  cmvn_columns<17, 20> (more than 16 columns): 3 x 17 rows and a window of at least 17; <13, 16>: 4 x 13 rows, 13
+static bool kws_mfe_norm_tuned_fits(const KwsDspPlan &P)
+{
+    return P.n_frames <= (P.n_filters > 16 ? 51 : 52) && P.win_size >= (P.n_filters > 16 ? 17 : 13);
+}
+
 static EI_IMPULSE_ERROR classify_fast_device(kws_handle *h, const int16_t *pcm, size_t B, float *scores, float *fx, bool want_f, int8_t *q,
                                              hipStream_t s);
-static EI_IMPULSE_ERROR classify_device(kws_handle *h, const int16_t *pcm, size_t B, float *scores, float *f, int8_t *q, hipStream_t s);
 int grid_cap_mfcc(const kws_handle *h) { return h->n_cu * 8; }
 int grid_cap_nn(const kws_handle *h) { return h->n_cu * 4; }
 
@@ -383,7 +405,7 @@ EI_IMPULSE_ERROR generic_for(kws_handle *h, hipStream_t s, size_t B, kws_handle:
 EI_IMPULSE_ERROR spectral_device(kws_handle *h, const KwsDspPlan &P, const void *pcm, int is_float, size_t B, float *mfcc,
                                         const float *wrap, hipStream_t s, int out_stride)
 {
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
     if (h->model.dsp.block == DSP_BLOCK_MFE && !P.mfe_mel) {
         // the MFE block's per-window stage is speechpy::feature::mfe itself (extract_mfe_per_slice_features, L432 ei_run_dsp.h:420-470)
         if (P.generic) {
@@ -393,22 +415,19 @@ EI_IMPULSE_ERROR spectral_device(kws_handle *h, const KwsDspPlan &P, const void 
             PM.mfe_mel = mfcc;
             return spectral_device(h, PM, pcm, is_float, B, nullptr, wrap, s, out_stride);
         }
-        if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
-        int rc = kws_launch_mfe(P, pcm, is_float, (int)B, mfcc, nullptr, wrap, out_stride, grid_cap_mfcc(h), s);
-        if (rc) return fail(KWS_ERROR_HIP, "MFE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (EI_IMPULSE_ERROR e = check_batch_pcm(pcm, B)) return e;
+        KWS_LAUNCH_TRY("MFE kernel", kws_launch_mfe(P, pcm, is_float, (int)B, mfcc, nullptr, wrap, out_stride, grid_cap_mfcc(h), s));
         return EI_IMPULSE_OK;
     }
     if (h->dsp.generic) {
         kws_handle::GenericBuf *g = nullptr;
         EI_IMPULSE_ERROR e = generic_for(h, s, 0, &g);
         if (e) return e;
-        int rc = launch_spectral_generic_for(h, P, pcm, is_float, B, mfcc, wrap, out_stride, g->ws, s);
-        if (rc) return fail(KWS_ERROR_HIP, "MFCC kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("MFCC kernel", launch_spectral_generic_for(h, P, pcm, is_float, B, mfcc, wrap, out_stride, g->ws, s));
         return EI_IMPULSE_OK;
     }
-    if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
-    int rc = kws_launch_spectral(P, pcm, is_float, (int)B, mfcc, wrap, out_stride, grid_cap_mfcc(h), s);
-    if (rc) return fail(KWS_ERROR_HIP, "MFCC kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
+    if (EI_IMPULSE_ERROR e = check_batch_pcm(pcm, B)) return e;
+    KWS_LAUNCH_TRY_OBJ("MFCC kernel", kws_launch_spectral(P, pcm, is_float, (int)B, mfcc, wrap, out_stride, grid_cap_mfcc(h), s));
     return EI_IMPULSE_OK;
 }
 
@@ -418,14 +437,12 @@ EI_IMPULSE_ERROR spectral_device(kws_handle *h, const KwsDspPlan &P, const void 
 // hands over another buffer).
 static EI_IMPULSE_ERROR mfe_norm_device(kws_handle *h, const KwsDspPlan &P, const float *mel, size_t B, float *features, int8_t *q, hipStream_t s)
 {
-    int rc;
     if (P.generic) {
-        rc = kws_launch_mfe_norm_generic(P, mel ? mel : features, (int)B, features, q, h->nn.in_scale, h->nn.in_zp, s);
+        KWS_LAUNCH_TRY("MFE normalisation", kws_launch_mfe_norm_generic(P, mel ? mel : features, (int)B, features, q, h->nn.in_scale, h->nn.in_zp, s));
     } else {
-        rc = kws_launch_mfe_norm(features, (int)B, P.n_frames, P.n_filters, P.win_size, P.pad_map, P.n_frames + 2 * P.pad, grid_cap_nn(h), s);
-        if (!rc && q) rc = kws_launch_quantize(features, q, B * (size_t)P.n_frames * P.n_filters, h->nn.in_scale, h->nn.in_zp, s);
+        KWS_LAUNCH_TRY("MFE normalisation", kws_launch_mfe_norm(features, (int)B, P.n_frames, P.n_filters, P.win_size, P.pad_map, P.n_frames + 2 * P.pad, grid_cap_nn(h), s));
+        if (q) KWS_LAUNCH_TRY("MFE normalisation", kws_launch_quantize(features, q, B * (size_t)P.n_frames * P.n_filters, h->nn.in_scale, h->nn.in_zp, s));
     }
-    if (rc) return fail(KWS_ERROR_HIP, "MFE normalisation launch failed: %s", hipGetErrorString((hipError_t)rc));
     return EI_IMPULSE_OK;
 }
 
@@ -443,9 +460,8 @@ static EI_IMPULSE_ERROR mfe_block_device(kws_handle *h, const KwsDspPlan &P, con
         mel = g->mfcc;
         if ((e = spectral_device(h, P, pcm, is_float, B, g->mfcc, nullptr, s, 0))) return e;
     } else {
-        if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
-        int rc = kws_launch_mfe(P, pcm, is_float, (int)B, features, nullptr, nullptr, 0, grid_cap_mfcc(h), s);
-        if (rc) return fail(KWS_ERROR_HIP, "MFE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (EI_IMPULSE_ERROR e = check_batch_pcm(pcm, B)) return e;
+        KWS_LAUNCH_TRY("MFE kernel", kws_launch_mfe(P, pcm, is_float, (int)B, features, nullptr, nullptr, 0, grid_cap_mfcc(h), s));
     }
     return mfe_norm_device(h, P, mel, B, features, q, s);
 }
@@ -453,7 +469,7 @@ static EI_IMPULSE_ERROR mfe_block_device(kws_handle *h, const KwsDspPlan &P, con
 // extract_mfcc_features + quantisation in one launch (fused kernel)
 EI_IMPULSE_ERROR mfcc_fused_device_plan(kws_handle *h, const KwsDspPlan &P, const void *pcm, int is_float, size_t B, float *features, int8_t *q, hipStream_t s)
 {
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
     if (h->model.dsp.block == DSP_BLOCK_MFE) {
         // extract_mfe_features: the float feature matrix is needed either way
         return mfe_block_device(h, P, pcm, is_float, B, features, q, s);
@@ -463,14 +479,12 @@ EI_IMPULSE_ERROR mfcc_fused_device_plan(kws_handle *h, const KwsDspPlan &P, cons
         kws_handle::GenericBuf *g = nullptr;
         EI_IMPULSE_ERROR e = generic_for(h, s, B, &g);
         if (e) return e;
-        int rc = launch_spectral_generic_for(h, P, pcm, is_float, B, g->mfcc, nullptr, 0, g->ws, s);
-        if (!rc) rc = kws_launch_cmvn_generic(P, g->mfcc, (int)B, features, q, h->nn.in_scale, h->nn.in_zp, s);
-        if (rc) return fail(KWS_ERROR_HIP, "MFCC kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("MFCC kernel", launch_spectral_generic_for(h, P, pcm, is_float, B, g->mfcc, nullptr, 0, g->ws, s));
+        KWS_LAUNCH_TRY("MFCC kernel", kws_launch_cmvn_generic(P, g->mfcc, (int)B, features, q, h->nn.in_scale, h->nn.in_zp, s));
         return EI_IMPULSE_OK;
     }
-    if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
-    int rc = kws_launch_mfcc_fused(P, pcm, is_float, (int)B, features, q, h->nn.in_scale, h->nn.in_zp, h->n_cu * 8, s);
-    if (rc) return fail(KWS_ERROR_HIP, "MFCC kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
+    if (EI_IMPULSE_ERROR e = check_batch_pcm(pcm, B)) return e;
+    KWS_LAUNCH_TRY_OBJ("MFCC kernel", kws_launch_mfcc_fused(P, pcm, is_float, (int)B, features, q, h->nn.in_scale, h->nn.in_zp, h->n_cu * 8, s));
     return EI_IMPULSE_OK;
 }
 EI_IMPULSE_ERROR mfcc_fused_device(kws_handle *h, const void *pcm, int is_float, size_t B, float *features, int8_t *q, hipStream_t s)
@@ -478,13 +492,19 @@ EI_IMPULSE_ERROR mfcc_fused_device(kws_handle *h, const void *pcm, int is_float,
     return mfcc_fused_device_plan(h, h->dsp, pcm, is_float, B, features, q, s);
 }
 
-// float32 models: the network reads the feature matrix itself (ei_run_classifier.h:447-452 copies it into the input tensor)
-EI_IMPULSE_ERROR nn_f32_device(kws_handle *h, const float *features, size_t B, float *scores, float *tap_logits, hipStream_t s)
+// the handle's exact network (kws_internal.h); float32 models: it reads the feature matrix itself (ei_run_classifier.h:447-452 copies it into the input tensor)
+EI_IMPULSE_ERROR network_device(kws_handle *h, const float *features, const int8_t *q, size_t B, float *scores, float *tap_logits, int8_t *tap_pooled, int8_t *tap_fc,
+                                int8_t *tap_out, const int *sel, hipStream_t s)
 {
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
-    int rc = kws_launch_nn_f32(h->nnf, h->d_nnf, features, (int)B, scores, tap_logits, h->n_cu, s);
-    if (rc) return fail(KWS_ERROR_HIP, "float NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
+    if (h->is_float) KWS_LAUNCH_TRY("float NN kernel", kws_launch_nn_f32(h->nnf, h->d_nnf, features, (int)B, scores, tap_logits, h->n_cu, s, sel));
+    else KWS_LAUNCH_TRY("NN kernel", kws_launch_nn(h->nn, q, (int)B, scores, tap_pooled, h->pooled_tap_bytes, tap_fc, tap_out, grid_cap_nn(h), s, sel));
     return EI_IMPULSE_OK;
+}
+// the same as the batch calls run it: a float32 graph's logits to the handle's tap (kws_set_logits_tap), no int8 taps
+static EI_IMPULSE_ERROR batch_network_device(kws_handle *h, const float *features, const int8_t *q, size_t B, float *scores, const int *sel, hipStream_t s)
+{
+    return network_device(h, features, q, B, scores, h->tap_logits, nullptr, nullptr, nullptr, sel, s);
 }
 #define KWS_INT8_ONLY(h) do { if ((h)->is_float) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%s takes an int8 tensor; the loaded model is float32", __func__); } while (0)
 
@@ -494,9 +514,8 @@ EI_IMPULSE_ERROR cmvn_nn_device(kws_handle *h, const float *mfcc, size_t B, floa
                                        int8_t *tap_pooled, int8_t *tap_fc, int8_t *tap_out, hipStream_t s, int ring_rows, int ring_head)
 {
     // ring_rows != 0: mfcc holds ring-indexed rolling buffers (continuous mode, kws_streams_*)
-    KwsDspPlan PR = h->dsp;
-    PR.ring_rows = ring_rows; PR.ring_head = ring_rows > 0 ? ((ring_head % ring_rows) + ring_rows) % ring_rows : 0;      // (the fast kernel's ring() wraps with one subtraction: head < rows)
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    const KwsDspPlan PR = ring_plan(h->dsp, ring_rows, ring_head);
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
     int ran_nn = 0;
     if (h->model.dsp.block == DSP_BLOCK_MFE) {
         // calc_cepstral_mean_and_var_normalization_mfe on a copy of the mel matrices (L432 classifier/ei_run_classifier.h:745-775)
@@ -511,14 +530,9 @@ EI_IMPULSE_ERROR cmvn_nn_device(kws_handle *h, const float *mfcc, size_t B, floa
             if (e) return e;
             copy = g->mfcc;
         }
-        int rc = kws_launch_unring(mfcc, copy, (int)B, P.n_frames, P.n_filters, ring_rows, ring_head, s);
-        if (rc) return fail(KWS_ERROR_HIP, "copy kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("copy kernel", kws_launch_unring(mfcc, copy, (int)B, P.n_frames, P.n_filters, ring_rows, ring_head, s));
         if (EI_IMPULSE_ERROR e = mfe_norm_device(h, P, copy, B, f, qq, s)) return e;
-        if (!scores) return EI_IMPULSE_OK;
-        if (h->is_float) return nn_f32_device(h, f, B, scores, nullptr, s);
-        rc = kws_launch_nn(h->nn, qq, (int)B, scores, tap_pooled, h->pooled_tap_bytes, tap_fc, tap_out, grid_cap_nn(h), s);
-        if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        return EI_IMPULSE_OK;
+        return scores ? network_device(h, f, qq, B, scores, nullptr, tap_pooled, tap_fc, tap_out, nullptr, s) : EI_IMPULSE_OK;
     }
     if (h->dsp.generic) {
         if (h->is_float && (q || tap_pooled || tap_fc || tap_out)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "int8 outputs requested from a float32 model");
@@ -527,88 +541,95 @@ EI_IMPULSE_ERROR cmvn_nn_device(kws_handle *h, const float *mfcc, size_t B, floa
         if (e) return e;
         float *f = features ? features : (h->is_float ? g->feat : nullptr);
         int8_t *qq = h->is_float ? nullptr : (q ? q : h->s_q);
-        int rc = 0;
         if (ring_rows) {
-            rc = kws_launch_unring(mfcc, g->mfcc, (int)B, h->dsp.n_frames, h->dsp.n_cepstral, ring_rows, ring_head, s);
+            KWS_LAUNCH_TRY("CMVN kernel", kws_launch_unring(mfcc, g->mfcc, (int)B, h->dsp.n_frames, h->dsp.n_cepstral, ring_rows, ring_head, s));
             mfcc = g->mfcc;
         }
-        if (!rc) rc = kws_launch_cmvn_generic(h->dsp, mfcc, (int)B, f, qq, h->nn.in_scale, h->nn.in_zp, s);
-        if (rc) return fail(KWS_ERROR_HIP, "CMVN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (!scores) return EI_IMPULSE_OK;
-        if (h->is_float) return nn_f32_device(h, f, B, scores, nullptr, s);
-        rc = kws_launch_nn(h->nn, qq, (int)B, scores, tap_pooled, h->pooled_tap_bytes, tap_fc, tap_out, grid_cap_nn(h), s);
-        if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        return EI_IMPULSE_OK;
+        KWS_LAUNCH_TRY("CMVN kernel", kws_launch_cmvn_generic(h->dsp, mfcc, (int)B, f, qq, h->nn.in_scale, h->nn.in_zp, s));
+        return scores ? network_device(h, f, qq, B, scores, nullptr, tap_pooled, tap_fc, tap_out, nullptr, s) : EI_IMPULSE_OK;
     }
     if (h->is_float) {
         if (q || tap_pooled || tap_fc || tap_out) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "int8 outputs requested from a float32 model");
         float *f = features ? features : h->s_mfcc;
-        int rc = kws_launch_cmvn_nn(PR, h->nn, mfcc, (int)B, f, nullptr, nullptr, nullptr, 0, nullptr, nullptr, grid_cap_nn(h), &ran_nn, s);
-        if (rc) return fail(KWS_ERROR_HIP, "CMVN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        return scores ? nn_f32_device(h, f, B, scores, h->tap_logits, s) : EI_IMPULSE_OK;
+        KWS_LAUNCH_TRY("CMVN kernel", kws_launch_cmvn_nn(PR, h->nn, mfcc, (int)B, f, nullptr, nullptr, nullptr, 0, nullptr, nullptr, grid_cap_nn(h), &ran_nn, s));
+        return scores ? batch_network_device(h, f, nullptr, B, scores, nullptr, s) : EI_IMPULSE_OK;
     }
     int8_t *qq = q;
     if (scores && !qq) qq = h->s_q;           // the generic NN kernel reads the quantised tensor from HBM
-    int rc = kws_launch_cmvn_nn(PR, h->nn, mfcc, (int)B, features, qq, scores, tap_pooled, h->pooled_tap_bytes, tap_fc, tap_out,
-                                grid_cap_nn(h), &ran_nn, s);
-    if (rc) return fail(KWS_ERROR_HIP, "CMVN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (scores && !ran_nn) {
-        rc = kws_launch_nn(h->nn, qq, (int)B, scores, tap_pooled, h->pooled_tap_bytes, tap_fc, tap_out, grid_cap_nn(h), s);
-        if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    return EI_IMPULSE_OK;
+    KWS_LAUNCH_TRY("CMVN kernel", kws_launch_cmvn_nn(PR, h->nn, mfcc, (int)B, features, qq, scores, tap_pooled, h->pooled_tap_bytes, tap_fc, tap_out, grid_cap_nn(h), &ran_nn, s));
+    return scores && !ran_nn ? network_device(h, nullptr, qq, B, scores, nullptr, tap_pooled, tap_fc, tap_out, nullptr, s) : EI_IMPULSE_OK;
 }
 
-// KWS_MODE_FAST for windows that arrive as cepstra (continuous mode): O(1) cmvnw + the network (fused for float graphs), then the
-// exact kernels over the windows the fast kernel listed as ill-conditioned.  Uses the handle's scratch (h->mu held by the caller).
+// ---- KWS_MODE_FAST: tiers ----------------------------------------------------------------------------------------------------------------
+// One fast tier.  launch(plan, d_plan, scores, features, q, list, tap_logits) enqueues the tier's kernel -- from PCM, from cepstra, over every clip or over a
+// list -- with the plan and the outputs chosen here:
+//   * a float32 graph of the fused shapes that is asked for scores runs `fused`: the network in the same launch, the feature matrix stays on chip.  A caller
+//     who wants the matrix as well (want_f) gets it from the feature-emitting plan first.  That launch knows no scores -- its guard assumes the largest
+//     p (1 - p) there is -- and ITS list stands, for features and scores alike: the fused launch's goes to the sink d_flags3 (used nowhere else);
+//   * everything else runs the feature-emitting plan -- features to fx_plain, the int8 tensor to q -- and then, asked for scores, the exact network on them
+//     (over the list `sel`, when the tier runs over one).  scores_plain is that launch's `scores` argument: the kernel computes none, and the callers differ.
+// The clips the tier does not keep are listed in list_out ([0] = count, which the caller has reset).
+extern "C++" template <class Launch>          // (this file is one extern "C" block)
+static EI_IMPULSE_ERROR fast_tier(kws_handle *h, const KwsFastPlan &fused_plan, const KwsFastPlan *d_fused_plan, size_t B, float *scores, float *scores_plain, float *fx_plain,
+                                  bool want_f, int8_t *q, const int *sel, int *list_out, hipStream_t s, Launch launch)
+{
+    const bool fused = scores && h->is_float && h->fast_fused_ok;       // scores == NULL: features / int8 tensor only (extract_mfcc_features)
+    if (fused && want_f) {
+        if (EI_IMPULSE_ERROR e = launch(h->fast_plain, h->d_fast_plain, nullptr, fx_plain, nullptr, list_out, nullptr)) return e;
+        HIP_TRY(hipMemsetAsync(h->d_flags3, 0, sizeof(int), s));
+    }
+    if (fused) return launch(fused_plan, d_fused_plan, scores, nullptr, nullptr, want_f ? h->d_flags3 : list_out, h->tap_logits);
+    if (EI_IMPULSE_ERROR e = launch(h->fast_plain, h->d_fast_plain, scores_plain, fx_plain, q, list_out, h->tap_logits)) return e;
+    return scores ? batch_network_device(h, fx_plain, q, B, scores, sel, s) : EI_IMPULSE_OK;
+}
+
+// The tier from cepstra `cep` (plan P: ring-indexed in continuous mode) over every window or over the list sel_in -- or, feat_in, the fused network alone
+// from the exact kernels' feature matrix in `cep`.  These forms run the two-wave plan (kws_internal.h: fast_fused_cep).
+static EI_IMPULSE_ERROR fast_tier_from_cepstra(kws_handle *h, const KwsDspPlan &P, const float *cep, size_t B, float *scores, float *scores_plain, float *fx_plain, bool want_f,
+                                               int8_t *q, const int *sel_in, int *list_out, int feat_in, hipStream_t s)
+{
+    return fast_tier(h, h->fast_fused_cep, h->d_fast_fused_cep, B, scores, scores_plain, fx_plain, want_f, q, sel_in, list_out, s,
+                     [&](const KwsFastPlan &FP, const KwsFastPlan *d_plan, float *sc, float *f, int8_t *qo, int *list, float *tap) -> EI_IMPULSE_ERROR {
+                         KWS_LAUNCH_TRY("fast kernel", kws_launch_fast_from_cepstra(P, FP, d_plan, cep, (int)B, sc, f, qo, h->nn.in_scale, h->nn.in_zp, list, list + 1, h->n_cu, s,
+                                                                                    sel_in, tap, feat_in));
+                         return EI_IMPULSE_OK;
+                     });
+}
+
+// What a list ends in: the exact cmvnw from the same cepstra (+ the int8 matrix-core network where it is fused there), then the exact network -- the exact
+// mode's bits for the listed clips.  fx: where their features go (a float32 graph's network reads them; NULL: an int8 graph whose caller wants none).
+// count_to: the list's count is copied there behind the cmvnw launch (kws_fast_exact_count's list, where the list itself is another), or NULL.
+static EI_IMPULSE_ERROR exact_finish_listed(kws_handle *h, const KwsDspPlan &P, const float *cep, size_t B, float *scores, float *fx, int8_t *q, int *list, int *count_to,
+                                            hipStream_t s)
+{
+    int ran_nn = 0;
+    KWS_LAUNCH_TRY("CMVN kernel", kws_launch_cmvn_nn(P, h->nn, cep, (int)B, fx, q, h->is_float ? nullptr : scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h),
+                                                     &ran_nn, s, list));
+    if (count_to) HIP_TRY(hipMemcpyAsync(count_to, list, sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (!scores || (!h->is_float && ran_nn)) return EI_IMPULSE_OK;
+    return batch_network_device(h, fx, q, B, scores, list, s);
+}
+
+// KWS_MODE_FAST for windows that arrive as cepstra (continuous mode, and batch calls that enter at the second tier): O(1) cmvnw + the network (fused for
+// float graphs), then the exact kernels over the windows the fast kernel listed as ill-conditioned (indexed by their own numbers).  Uses the handle's
+// scratch (h->mu held by the caller).
 EI_IMPULSE_ERROR cmvn_nn_fast_device(kws_handle *h, const float *mfcc, size_t B, float *scores, hipStream_t s, int ring_rows, int ring_head,
                                      float *features, int8_t *q_out)
 {
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
     // MFE block: what arrives here are the exact kernels' mel matrices, and the block's normalisation has no fast form (nothing to gain:
     // it divides by the matrix's range, not by a deviation): the exact path serves both modes
     if (h->model.dsp.block == DSP_BLOCK_MFE)
         return cmvn_nn_device(h, mfcc, B, features, h->is_float ? nullptr : q_out, scores, nullptr, nullptr, nullptr, s, ring_rows, ring_head);
-    EI_IMPULSE_ERROR e = ensure_flags(h, B);
-    if (e) return e;
+    if (EI_IMPULSE_ERROR e = ensure_flags(h, B)) return e;
     HIP_TRY(hipMemsetAsync(h->d_flags, 0, sizeof(int), s));
     HIP_TRY(hipMemsetAsync(h->d_flags2, 0, sizeof(int), s));      // kws_fast_exact_count describes the LAST fast call: this path has one fast tier
-    KwsDspPlan PR = h->dsp;
-    PR.ring_rows = ring_rows; PR.ring_head = ring_rows > 0 ? ((ring_head % ring_rows) + ring_rows) % ring_rows : 0;      // (the fast kernel's ring() wraps with one subtraction: head < rows)
-    const bool fused = scores && h->is_float && h->fast_fused_ok;       // scores == NULL: features / int8 tensor only (extract_mfcc_features)
+    const KwsDspPlan PR = ring_plan(h->dsp, ring_rows, ring_head);
     float *fx = features ? features : h->s_mfcc;
     int8_t *q = h->is_float ? nullptr : (q_out ? q_out : h->s_q);
-    int rc = 0;
-    if (fused && features) {
-        // the fused form keeps the feature matrix on chip: a caller who also wants it gets it from the feature-emitting form first
-        rc = kws_launch_fast_from_cepstra(PR, h->fast_plain, h->d_fast_plain, mfcc, (int)B, nullptr, fx, nullptr, h->nn.in_scale, h->nn.in_zp, h->d_flags,
-                                          h->d_flags + 1, h->n_cu, s);
-        if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        HIP_TRY(hipMemsetAsync(h->d_flags3, 0, sizeof(int), s));
-    }
-    const KwsFastPlan &FP = fused ? h->fast_fused_cep : h->fast_plain;
-    int *const fl = (fused && features) ? h->d_flags3 : h->d_flags;      // the feature-emitting launch's list stands (kws_internal.h: d_flags3)
-    rc = kws_launch_fast_from_cepstra(PR, FP, fused ? h->d_fast_fused_cep : h->d_fast_plain, mfcc, (int)B, scores, fused ? nullptr : fx, q,
-                                      h->nn.in_scale, h->nn.in_zp, fl, fl + 1, h->n_cu, s, nullptr, h->tap_logits);
-    if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (!fused && scores) {
-        if (h->is_float) { if ((e = nn_f32_device(h, fx, B, scores, h->tap_logits, s))) return e; }
-        else {
-            rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s);
-            if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        }
-    }
-    // exact re-run of the listed windows (indexed by their own numbers)
-    int ran_nn = 0;
-    rc = kws_launch_cmvn_nn(PR, h->nn, mfcc, (int)B, (h->is_float || features) ? fx : nullptr, q, h->is_float ? nullptr : scores, nullptr, h->pooled_tap_bytes,
-                            nullptr, nullptr, grid_cap_nn(h), &ran_nn, s, h->d_flags);
-    if (rc) return fail(KWS_ERROR_HIP, "CMVN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    HIP_TRY(hipMemcpyAsync(h->d_flags2, h->d_flags, sizeof(int), hipMemcpyDeviceToDevice, s));     // handed on = finished by the exact kernels
-    if (!scores) return EI_IMPULSE_OK;
-    if (h->is_float) rc = kws_launch_nn_f32(h->nnf, h->d_nnf, fx, (int)B, scores, h->tap_logits, h->n_cu, s, h->d_flags);
-    else if (!ran_nn) rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s, h->d_flags);
-    if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EI_IMPULSE_OK;
+    if (EI_IMPULSE_ERROR e = fast_tier_from_cepstra(h, PR, mfcc, B, scores, scores, fx, features != nullptr, q, nullptr, h->d_flags, 0, s)) return e;
+    // handed on = finished by the exact kernels
+    return exact_finish_listed(h, PR, mfcc, B, scores, (h->is_float || features) ? fx : nullptr, q, h->d_flags, h->d_flags2, s);
 }
 
 EI_IMPULSE_ERROR kws_mfcc_batch_device(kws_handle *h, const int16_t *pcm, size_t B, float *mfcc, void *stream)
@@ -621,23 +642,22 @@ EI_IMPULSE_ERROR kws_mfcc_batch_device(kws_handle *h, const int16_t *pcm, size_t
 EI_IMPULSE_ERROR kws_mfe_batch_device(kws_handle *h, const int16_t *pcm, size_t B, float *mel, float *energy, void *stream)
 {
     if (!h || !pcm || !mel) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
     HIP_TRY(hipSetDevice(h->device));
     if (h->dsp.generic) {
         KwsDspPlan P = h->dsp;
         P.mfe_mel = mel; P.mfe_energy = energy;
         return spectral_device(h, P, pcm, 0, B, nullptr, nullptr, (hipStream_t)stream);
     }
-    if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
-    int rc = kws_launch_mfe(h->dsp, pcm, 0, (int)B, mel, energy, nullptr, 0, grid_cap_mfcc(h), (hipStream_t)stream);
-    if (rc) return fail(KWS_ERROR_HIP, "MFE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (EI_IMPULSE_ERROR e = check_batch_pcm(pcm, B)) return e;
+    KWS_LAUNCH_TRY("MFE kernel", kws_launch_mfe(h->dsp, pcm, 0, (int)B, mel, energy, nullptr, 0, grid_cap_mfcc(h), (hipStream_t)stream));
     return EI_IMPULSE_OK;
 }
 
 EI_IMPULSE_ERROR kws_extract_mfe_batch_device(kws_handle *h, const int16_t *pcm, size_t B, float *features, void *stream)
 {
     if (!h || !pcm || !features) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
     HIP_TRY(hipSetDevice(h->device));
     // the MFE block hands the raw signal to feature::mfe (ei_run_dsp.h:398-400; extract_mfcc_features wraps it in the
     // pre-emphasis class first): coefficient 0 makes the kernel's y = x - cof * prev the identity, bit for bit
@@ -646,10 +666,9 @@ EI_IMPULSE_ERROR kws_extract_mfe_batch_device(kws_handle *h, const int16_t *pcm,
     hipStream_t s = (hipStream_t)stream;
     if (h->model.dsp.block == DSP_BLOCK_MFE) return mfe_block_device(h, P, pcm, 0, B, features, nullptr, s);
     // An MFCC-block model asked for the MFE block's features of its own DSP configuration: its buffers are sized for cepstra, so the mel rows go
-    // straight to `features` and are normalised in place -- by the tuned kernel within its limits (cmvn_columns<17, 20>, more than 16 columns: 3 x 17
-    // rows and a window of at least 17; <13, 16>: 4 x 13, 13), else by the general kernel's LDS form
+    // straight to `features` and are normalised in place -- by the tuned kernel within its limits, else by the general kernel's LDS form
     KwsDspPlan PN = P;
-    if (P.n_frames > (P.n_filters > 16 ? 51 : 52) || P.win_size < (P.n_filters > 16 ? 17 : 13)) PN.generic = 1;
+    if (!kws_mfe_norm_tuned_fits(P)) PN.generic = 1;
     if (PN.generic && !kws_mfe_norm_uses_lds(PN))
         return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%d frames x %d filters, window %d: an MFCC-block model has no buffer for the MFE normalisation's global-memory form",
                     P.n_frames, P.n_filters, P.win_size);
@@ -658,9 +677,8 @@ EI_IMPULSE_ERROR kws_extract_mfe_batch_device(kws_handle *h, const int16_t *pcm,
         PM.mfe_mel = features;
         if (EI_IMPULSE_ERROR e = spectral_device(h, PM, pcm, 0, B, nullptr, nullptr, s, 0)) return e;
     } else {
-        if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
-        int rc = kws_launch_mfe(P, pcm, 0, (int)B, features, nullptr, nullptr, 0, grid_cap_mfcc(h), s);
-        if (rc) return fail(KWS_ERROR_HIP, "MFE kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (EI_IMPULSE_ERROR e = check_batch_pcm(pcm, B)) return e;
+        KWS_LAUNCH_TRY("MFE kernel", kws_launch_mfe(P, pcm, 0, (int)B, features, nullptr, nullptr, 0, grid_cap_mfcc(h), s));
     }
     return mfe_norm_device(h, PN, nullptr, B, features, nullptr, s);
 }
@@ -730,9 +748,8 @@ EI_IMPULSE_ERROR kws_dev_fast_phase_profile(kws_handle *h, const int16_t *pcm, s
     if (e) return e;
     HIP_TRY(hipMemsetAsync(h->d_flags, 0, sizeof(int), nullptr));
     const bool fused = h->is_float && h->fast_fused_ok;
-    int rc = kws_launch_fast_prof(h->dsp, fused ? h->fast_fused : h->fast_plain, fused ? h->d_fast_fused : h->d_fast_plain, pcm, (int)B, scores,
-                                  h->d_flags, h->d_flags + 1, h->n_cu, prof_dev, nullptr);
-    if (rc) return fail(KWS_ERROR_HIP, "launch failed");
+    KWS_LAUNCH_TRY("profiled fast kernel", kws_launch_fast_prof(h->dsp, fused ? h->fast_fused : h->fast_plain, fused ? h->d_fast_fused : h->d_fast_plain, pcm, (int)B, scores,
+                                                                h->d_flags, h->d_flags + 1, h->n_cu, prof_dev, nullptr));
     return EI_IMPULSE_OK;
 }
 
@@ -740,8 +757,7 @@ EI_IMPULSE_ERROR kws_dev_fast_phase_profile(kws_handle *h, const int16_t *pcm, s
 EI_IMPULSE_ERROR kws_dev_mfcc_phase_profile(kws_handle *h, const int16_t *pcm, size_t B, float *features, long long *prof_dev)
 {
     HIP_TRY(hipSetDevice(h->device));
-    int rc = kws_launch_mfcc_fused_prof(h->dsp, pcm, (int)B, features, nullptr, h->nn.in_scale, h->nn.in_zp, h->n_cu * 8, prof_dev, nullptr);
-    if (rc) return fail(KWS_ERROR_HIP, "launch failed");
+    KWS_LAUNCH_TRY("profiled MFCC kernel", kws_launch_mfcc_fused_prof(h->dsp, pcm, (int)B, features, nullptr, h->nn.in_scale, h->nn.in_zp, h->n_cu * 8, prof_dev, nullptr));
     return EI_IMPULSE_OK;
 }
 
@@ -750,11 +766,9 @@ EI_IMPULSE_ERROR kws_nn_batch_device(kws_handle *h, const int8_t *q_in, size_t B
 {
     if (!h || !q_in || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     KWS_INT8_ONLY(h);
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    if (EI_IMPULSE_ERROR e = check_batch(B)) return e;
     HIP_TRY(hipSetDevice(h->device));
-    int rc = kws_launch_nn(h->nn, q_in, (int)B, scores, tap_pooled, h->pooled_tap_bytes, tap_fc, tap_out, grid_cap_nn(h), (hipStream_t)stream);
-    if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EI_IMPULSE_OK;
+    return network_device(h, nullptr, q_in, B, scores, nullptr, tap_pooled, tap_fc, tap_out, nullptr, (hipStream_t)stream);
 }
 
 EI_IMPULSE_ERROR kws_nn_f32_batch_device(kws_handle *h, const float *features, size_t B, float *scores, float *tap_logits, void *stream)
@@ -762,29 +776,22 @@ EI_IMPULSE_ERROR kws_nn_f32_batch_device(kws_handle *h, const float *features, s
     if (!h || !features || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (!h->is_float) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "kws_nn_f32_batch_device needs a float32 model; the loaded model is int8");
     HIP_TRY(hipSetDevice(h->device));
-    return nn_f32_device(h, features, B, scores, tap_logits, (hipStream_t)stream);
+    return network_device(h, features, nullptr, B, scores, tap_logits, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 EI_IMPULSE_ERROR kws_run_inference_batch_device(kws_handle *h, const float *features, size_t B, float *scores, void *stream)
 {
     if (!h || !features || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     HIP_TRY(hipSetDevice(h->device));
-    if (h->is_float) return nn_f32_device(h, features, B, scores, nullptr, (hipStream_t)stream);
+    if (h->is_float) return network_device(h, features, nullptr, B, scores, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
     std::lock_guard<std::mutex> lk(h->mu);
     EI_IMPULSE_ERROR e = ensure_scratch(h, B);
     if (e) return e;
     ScratchUse use(h, (hipStream_t)stream);
-    int rc = kws_launch_quantize(features, h->s_q, B * h->model.nn_input_frame_size, h->nn.in_scale, h->nn.in_zp, (hipStream_t)stream);
-    if (rc) return fail(KWS_ERROR_HIP, "quantise kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    KWS_LAUNCH_TRY("quantise kernel", kws_launch_quantize(features, h->s_q, B * h->model.nn_input_frame_size, h->nn.in_scale, h->nn.in_zp, (hipStream_t)stream));
     return kws_nn_batch_device(h, h->s_q, B, scores, nullptr, nullptr, nullptr, stream);
 }
 
-// extract_mfcc_features + the network for B windows in HBM.  float models: f must be a [B][n_features] buffer (the network
-// reads it); int8 models: q must be a [B][n_features] buffer, f is optional (the float feature matrix only leaves the chip
-// when somebody asks for it: the cepstra stay in LDS)
-// KWS_MODE_FAST: the fast kernel over every clip, then the exact kernels over the clips it listed as ill-conditioned (the list and
-// its length stay in HBM: nothing synchronises).  fx: feature scratch / output [B][n_features] (exact re-runs of float graphs and
-// un-fused graphs read it), q: int8 tensor [B][n_features] for int8 graphs; want_f: the caller asked for the feature matrix.
 // What follows the fast kernel of a batch call, on the clips it handed back (list d_flags; list and count stay in HBM, nothing
 // synchronises).  Second tier: their cepstra from the exact kernels -- bit-identical to the reference's, so the DCT term of the guard is
 // gone -- then the fast cmvnw + network from those cepstra (kws_fast_kernel<FROM_CEP> over the list), with the guard that is left
@@ -794,73 +801,48 @@ static EI_IMPULSE_ERROR rerun_flagged_device(kws_handle *h, const int16_t *pcm, 
 {
     static const bool skip = KWS_DEV_ENV("KWS_DEV_FAST_NO_RERUN") != nullptr;     // development aid: what the (usually empty) re-run launches cost; results are wrong when set
     if (skip) return EI_IMPULSE_OK;
-    const size_t F = h->model.nn_input_frame_size;
-    if (B > h->cep_cap) {
-        if (h->s_cep) (void)hipFree(h->s_cep);
-        h->s_cep = nullptr; h->cep_cap = 0;
-        HIP_TRY(hipMalloc((void **)&h->s_cep, B * F * sizeof(float)));
-        h->cep_cap = B;
-    }
+    if (EI_IMPULSE_ERROR e = ensure_cep(h, B)) return e;
     HIP_TRY(hipMemsetAsync(h->d_flags2, 0, sizeof(int), s));
-    int rc = kws_launch_spectral(h->dsp, pcm, 0, (int)B, h->s_cep, nullptr, 0, grid_cap_mfcc(h), s, h->d_flags);
-    if (rc) return fail(KWS_ERROR_HIP, "MFCC kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    const bool fused = scores && h->is_float && h->fast_fused_ok;
-    if (!scores || (fused && want_f) || !fused) {
-        // the feature-emitting form: features (float graphs: the network's input; or the caller's wish) and the int8 tensor
-        rc = kws_launch_fast_from_cepstra(h->dsp, h->fast_plain, h->d_fast_plain, h->s_cep, (int)B, nullptr, (h->is_float || want_f) ? fx : nullptr, q,
-                                          h->nn.in_scale, h->nn.in_zp, h->d_flags2, h->d_flags2 + 1, h->n_cu, s, h->d_flags);
-        if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (fused) HIP_TRY(hipMemsetAsync(h->d_flags3, 0, sizeof(int), s));      // the feature-emitting launch's list stands (kws_internal.h: d_flags3)
-    }
-    if (fused) {
-        int *const fl = want_f ? h->d_flags3 : h->d_flags2;
-        rc = kws_launch_fast_from_cepstra(h->dsp, h->fast_fused_cep, h->d_fast_fused_cep, h->s_cep, (int)B, scores, nullptr, nullptr, h->nn.in_scale, h->nn.in_zp,
-                                          fl, fl + 1, h->n_cu, s, h->d_flags, h->tap_logits);
-        if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    } else if (scores) {
-        if (h->is_float) rc = kws_launch_nn_f32(h->nnf, h->d_nnf, fx, (int)B, scores, h->tap_logits, h->n_cu, s, h->d_flags);
-        else rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s, h->d_flags);
-        if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    // third tier: exact cmvnw (+ the int8 matrix-core network when it is fused there) from the same cepstra, then the exact network
-    int ran_nn = 0;
-    rc = kws_launch_cmvn_nn(h->dsp, h->nn, h->s_cep, (int)B, (h->is_float || want_f) ? fx : nullptr, q, (scores && !h->is_float) ? scores : nullptr, nullptr,
-                            h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), &ran_nn, s, h->d_flags2);
-    if (rc) return fail(KWS_ERROR_HIP, "CMVN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    if (!scores) return EI_IMPULSE_OK;
-    if (h->is_float) rc = kws_launch_nn_f32(h->nnf, h->d_nnf, fx, (int)B, scores, h->tap_logits, h->n_cu, s, h->d_flags2);
-    else if (!ran_nn) rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s, h->d_flags2);
-    if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EI_IMPULSE_OK;
+    KWS_LAUNCH_TRY("MFCC kernel", kws_launch_spectral(h->dsp, pcm, 0, (int)B, h->s_cep, nullptr, 0, grid_cap_mfcc(h), s, h->d_flags));
+    float *const f = (h->is_float || want_f) ? fx : nullptr;     // features: a float32 graph's network input, or the caller's wish
+    if (EI_IMPULSE_ERROR e = fast_tier_from_cepstra(h, h->dsp, h->s_cep, B, scores, nullptr, f, want_f, q, h->d_flags, h->d_flags2, 0, s)) return e;
+    return exact_finish_listed(h, h->dsp, h->s_cep, B, scores, f, q, h->d_flags2, nullptr, s);
 }
 
+// extract_mfcc_features + the network for B windows in HBM.  float models: f must be a [B][n_features] buffer (the network
+// reads it); int8 models: q must be a [B][n_features] buffer, f is optional (the float feature matrix only leaves the chip
+// when somebody asks for it: the cepstra stay in LDS)
+static EI_IMPULSE_ERROR classify_device(kws_handle *h, const int16_t *pcm, size_t B, float *scores, float *f, int8_t *q, hipStream_t s)
+{
+    if (h->is_float) q = nullptr;
+    if (EI_IMPULSE_ERROR e = mfcc_fused_device(h, pcm, 0, B, (f || h->model.dsp.block != DSP_BLOCK_MFE) ? f : h->s_mfcc, q, s)) return e;
+    return batch_network_device(h, f, q, B, scores, nullptr, s);
+}
+
+// KWS_MODE_FAST: the fast kernel over every clip, then the exact kernels over the clips it listed as ill-conditioned (the list and
+// its length stay in HBM: nothing synchronises).  fx: feature scratch / output [B][n_features] (exact re-runs of float graphs and
+// un-fused graphs read it), q: int8 tensor [B][n_features] for int8 graphs; want_f: the caller asked for the feature matrix.
+// The routes of DESIGN 4.6, one `if` each.
 static EI_IMPULSE_ERROR classify_fast_device(kws_handle *h, const int16_t *pcm, size_t B, float *scores, float *fx, bool want_f, int8_t *q,
                                              hipStream_t s)
 {
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
-    if (((uintptr_t)pcm & 15) != 0) return fail(KWS_ERROR_BAD_ARGUMENT, "pcm must be 16-byte aligned");
-    EI_IMPULSE_ERROR e = ensure_flags(h, B);
-    if (e) return e;
+    EI_IMPULSE_ERROR e = check_batch_pcm(pcm, B);
+    if (e || (e = ensure_flags(h, B))) return e;
     HIP_TRY(hipMemsetAsync(h->d_flags, 0, sizeof(int), s));
-    const bool fused = scores && h->is_float && h->fast_fused_ok;
-    int rc = 0;
+    const auto from_pcm = [&](const KwsFastPlan &FP, const KwsFastPlan *d_plan, float *sc, float *f, int8_t *qo, int *list, float *tap) -> EI_IMPULSE_ERROR {
+        KWS_LAUNCH_TRY_OBJ("fast kernel", kws_launch_fast(h->dsp, FP, d_plan, pcm, (int)B, sc, f, qo, h->nn.in_scale, h->nn.in_zp, list, list + 1, h->n_cu, s, nullptr, tap));
+        return EI_IMPULSE_OK;
+    };
     if (h->model.dsp.block == DSP_BLOCK_MFE) {
         // extract_mfe_features (L432 classifier/ei_run_dsp.h:369-418) with the tolerance-mode front end: kws_fast_kernel<..., MFE> writes the
         // mel matrix (KissFFT-order FFT, fp32 power, fused mel products), then the block's own normalisation -- cmvnw(win, false, true) +
         // numpy::normalize, the exact kernel: it divides by the matrix's range, not by a window's deviation, so nothing is ill-conditioned
         // and no clip is handed back --, the input quantisation and the network's exact kernel
         const KwsDspPlan &P = h->dsp;
-        const int rows = P.n_frames, cols = P.n_filters;
-        if (rows > (cols > 16 ? 51 : 52) || P.win_size < (cols > 16 ? 17 : 13))
-            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%d frames x %d filters, window %d outside the MFE normalisation kernel's limits", rows, cols, P.win_size);
-        rc = kws_launch_fast(P, h->fast_plain, h->d_fast_plain, pcm, (int)B, nullptr, fx, nullptr, h->nn.in_scale, h->nn.in_zp, h->d_flags, h->d_flags + 1, h->n_cu, s);
-        if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
-        if ((e = mfe_norm_device(h, P, nullptr, B, fx, q, s))) return e;
-        if (!scores) return EI_IMPULSE_OK;
-        if (h->is_float) return nn_f32_device(h, fx, B, scores, h->tap_logits, s);
-        rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s);
-        if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        return EI_IMPULSE_OK;
+        if (!kws_mfe_norm_tuned_fits(P))
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%d frames x %d filters, window %d outside the MFE normalisation kernel's limits", P.n_frames, P.n_filters, P.win_size);
+        if ((e = from_pcm(h->fast_plain, h->d_fast_plain, nullptr, fx, nullptr, h->d_flags, nullptr)) || (e = mfe_norm_device(h, P, nullptr, B, fx, q, s))) return e;
+        return scores ? batch_network_device(h, fx, q, B, scores, nullptr, s) : EI_IMPULSE_OK;
     }
     if (h->fast_entry_tier >= 2 && (scores || want_f || q)) {
         // the graph's gain leaves the first tier no room (build_guard): every clip's cepstra come from the exact kernels, then the fast
@@ -872,90 +854,41 @@ static EI_IMPULSE_ERROR classify_fast_device(kws_handle *h, const int16_t *pcm, 
             // What is left of the guard is the network's own arithmetic (split 22-bit operands, KwsFastPlan::v_net_feat) against the clip's
             // own scores; a clip it does not clear is listed and goes through the exact network.  (configs[4].)
             HIP_TRY(hipMemsetAsync(h->d_flags2, 0, sizeof(int), s));
-            if ((e = mfcc_fused_device(h, pcm, 0, B, fx, nullptr, s))) return e;
-            if (!scores) return EI_IMPULSE_OK;                               // extract_mfcc_features only
-            rc = kws_launch_fast_from_cepstra(h->dsp, h->fast_fused_cep, h->d_fast_fused_cep, fx, (int)B, scores, nullptr, nullptr, h->nn.in_scale, h->nn.in_zp,
-                                              h->d_flags, h->d_flags + 1, h->n_cu, s, nullptr, h->tap_logits, 1);
-            if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-            rc = kws_launch_nn_f32(h->nnf, h->d_nnf, fx, (int)B, scores, h->tap_logits, h->n_cu, s, h->d_flags);
-            if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+            if ((e = mfcc_fused_device(h, pcm, 0, B, fx, nullptr, s)) || !scores) return e;                         // (no scores: extract_mfcc_features only)
+            if ((e = fast_tier_from_cepstra(h, h->dsp, fx, B, scores, scores, fx, false, nullptr, nullptr, h->d_flags, 1, s))) return e;
+            if ((e = batch_network_device(h, fx, nullptr, B, scores, h->d_flags, s))) return e;
             HIP_TRY(hipMemcpyAsync(h->d_flags2, h->d_flags, sizeof(int), hipMemcpyDeviceToDevice, s));      // those clips carry the exact mode's scores
             return EI_IMPULSE_OK;
         }
         if (h->fast_entry_tier >= 3) {
             HIP_TRY(hipMemsetAsync(h->d_flags2, 0, sizeof(int), s));
-            if (!scores) return mfcc_fused_device(h, pcm, 0, B, fx, q, s);
-            return classify_device(h, pcm, B, scores, fx, q, s);
+            return scores ? classify_device(h, pcm, B, scores, fx, q, s) : mfcc_fused_device(h, pcm, 0, B, fx, q, s);
         }
-        const size_t F = h->model.nn_input_frame_size;
-        if (B > h->cep_cap) {
-            if (h->s_cep) (void)hipFree(h->s_cep);
-            h->s_cep = nullptr; h->cep_cap = 0;
-            HIP_TRY(hipMalloc((void **)&h->s_cep, B * F * sizeof(float)));
-            h->cep_cap = B;
-        }
-        if ((e = spectral_device(h, h->dsp, pcm, 0, B, h->s_cep, nullptr, s))) return e;
+        if ((e = ensure_cep(h, B)) || (e = spectral_device(h, h->dsp, pcm, 0, B, h->s_cep, nullptr, s))) return e;
         return cmvn_nn_fast_device(h, h->s_cep, B, scores, s, 0, 0, want_f ? fx : nullptr, q);
     }
     if (scores && !h->is_float && h->fast_q_ok) {
         // int8 graph of the matrix-core shape: the network runs in the same launch on the quantised tensor it has just produced in LDS;
         // the feature matrix / the tensor only go to HBM when the caller asked for them (q is the caller's buffer or the scratch the
         // exact re-run below needs anyway -- the fast kernel writes it only in the first case)
-        rc = kws_launch_fast(h->dsp, h->fast_q, h->d_fast_q, pcm, (int)B, scores, want_f ? fx : nullptr, q != h->s_q ? q : nullptr, h->nn.in_scale, h->nn.in_zp,
-                             h->d_flags, h->d_flags + 1, h->n_cu, s, h->d_nn);
-        if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY_OBJ("fast kernel", kws_launch_fast(h->dsp, h->fast_q, h->d_fast_q, pcm, (int)B, scores, want_f ? fx : nullptr, q != h->s_q ? q : nullptr, h->nn.in_scale,
+                                                          h->nn.in_zp, h->d_flags, h->d_flags + 1, h->n_cu, s, h->d_nn));
         return rerun_flagged_device(h, pcm, B, scores, fx, want_f, q, s);
     }
 #ifdef KWS_DEV_SWITCHES
-    if (fused && KWS_DEV_ENV("KWS_DEV_FAST_SPLIT")) {
+    if (scores && h->is_float && h->fast_fused_ok && KWS_DEV_ENV("KWS_DEV_FAST_SPLIT")) {
         // development prototype ("build the two-kernel split and time it"): the spectral half + cmvnw as the
         // feature-emitting form, the features through HBM, the network half as the feat_in form of the from-cepstra kernel.  Timing only: the
         // first launch's guard assumes P = 1/4 and its list is not re-run here.
-        rc = kws_launch_fast(h->dsp, h->fast_plain, h->d_fast_plain, pcm, (int)B, nullptr, fx, nullptr, h->nn.in_scale, h->nn.in_zp, h->d_flags, h->d_flags + 1, h->n_cu, s);
-        if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("fast kernel", kws_launch_fast(h->dsp, h->fast_plain, h->d_fast_plain, pcm, (int)B, nullptr, fx, nullptr, h->nn.in_scale, h->nn.in_zp, h->d_flags,
+                                                      h->d_flags + 1, h->n_cu, s));
         HIP_TRY(hipMemsetAsync(h->d_flags3, 0, sizeof(int), s));
-        rc = kws_launch_fast_from_cepstra(h->dsp, h->fast_fused_cep, h->d_fast_fused_cep, fx, (int)B, scores, nullptr, nullptr, h->nn.in_scale, h->nn.in_zp,
-                                          h->d_flags3, h->d_flags3 + 1, h->n_cu, s, nullptr, h->tap_logits, 1);
-        if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        return EI_IMPULSE_OK;
+        return fast_tier_from_cepstra(h, h->dsp, fx, B, scores, scores, fx, false, nullptr, nullptr, h->d_flags3, 1, s);
     }
 #endif
-    if (fused && want_f) {
-        // the fused kernel keeps the feature matrix on chip: a caller who also wants it gets it from the feature-emitting form first
-        // (that launch knows no scores: its guard assumes the largest p (1 - p) there is, and its list decides for features and scores)
-        rc = kws_launch_fast(h->dsp, h->fast_plain, h->d_fast_plain, pcm, (int)B, nullptr, fx, nullptr, h->nn.in_scale, h->nn.in_zp, h->d_flags, h->d_flags + 1,
-                             h->n_cu, s);
-        if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
-        HIP_TRY(hipMemsetAsync(h->d_flags3, 0, sizeof(int), s));
-    }
-    const KwsFastPlan &FP = fused ? h->fast_fused : h->fast_plain;
-    int *const fl = (fused && want_f) ? h->d_flags3 : h->d_flags;          // the feature-emitting launch's list stands (kws_internal.h: d_flags3)
-    rc = kws_launch_fast(h->dsp, FP, fused ? h->d_fast_fused : h->d_fast_plain, pcm, (int)B, scores, fused ? nullptr : fx, fused ? nullptr : q, h->nn.in_scale,
-                         h->nn.in_zp, fl, fl + 1, h->n_cu, s, nullptr, h->tap_logits);
-    if (rc) return fail(KWS_ERROR_HIP, "fast kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
-    if (scores && !fused) {
-        if (h->is_float) { if ((e = nn_f32_device(h, fx, B, scores, h->tap_logits, s))) return e; }
-        else {
-            rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s);
-            if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        }
-    }
+    // float32 graphs (fused, or the feature-emitting form + the exact network) and the int8 graphs the fused form does not serve
+    if ((e = fast_tier(h, h->fast_fused, h->d_fast_fused, B, scores, scores, fx, want_f, q, nullptr, h->d_flags, s, from_pcm))) return e;
     return rerun_flagged_device(h, pcm, B, scores, fx, want_f, q, s);
-}
-
-static EI_IMPULSE_ERROR classify_device(kws_handle *h, const int16_t *pcm, size_t B, float *scores, float *f, int8_t *q, hipStream_t s)
-{
-    EI_IMPULSE_ERROR e;
-    if (h->is_float) {
-        e = mfcc_fused_device(h, pcm, 0, B, f, nullptr, s);
-        return e ? e : nn_f32_device(h, f, B, scores, h->tap_logits, s);
-    }
-    e = mfcc_fused_device(h, pcm, 0, B, (f || h->model.dsp.block != DSP_BLOCK_MFE) ? f : h->s_mfcc, q, s);
-    if (e) return e;
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
-    int rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s);
-    if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EI_IMPULSE_OK;
 }
 
 EI_IMPULSE_ERROR kws_run_classifier_batch_device(kws_handle *h, const int16_t *pcm, size_t B, float *scores, float *features,
@@ -1065,8 +998,7 @@ EI_IMPULSE_ERROR kws_mix_audio_device(const float *words, const int *word_len, s
     if (noise && noise_len < n) return fail(KWS_ERROR_BAD_ARGUMENT, "background track shorter than a clip");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(KWS_ERROR_HIP, "no HIP device available (libkws_mi355x has no CPU fallback)");
-    int rc = kws_launch_mix_audio(words, word_len, word_stride, noise, start, word_vol, bg_vol, (int)n, n_clips, out, (hipStream_t)stream);
-    if (rc) return fail(KWS_ERROR_HIP, "mix kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    KWS_LAUNCH_TRY("mix kernel", kws_launch_mix_audio(words, word_len, word_stride, noise, start, word_vol, bg_vol, (int)n, n_clips, out, (hipStream_t)stream));
     return EI_IMPULSE_OK;
 }
 
@@ -1076,8 +1008,7 @@ EI_IMPULSE_ERROR kws_synth_clips_device(uint32_t seed, uint32_t first_clip, uint
     int ndev = 0, dev = 0;      // no handle here: make sure the runtime is up before the first launch of the process
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || hipGetDevice(&dev) != hipSuccess)
         return fail(KWS_ERROR_HIP, "no HIP device available (libkws_mi355x has no CPU fallback)");
-    int rc = kws_launch_synth(seed, first_clip, n_clips, clip_len, out, (hipStream_t)stream);
-    if (rc) return fail(KWS_ERROR_HIP, "synth kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    KWS_LAUNCH_TRY("synth kernel", kws_launch_synth(seed, first_clip, n_clips, clip_len, out, (hipStream_t)stream));
     return EI_IMPULSE_OK;
 }
 

@@ -6,8 +6,8 @@
 //   int8, two-block matrix-core shape (kws_nn_uses_mfma)  kws_bank_nn_mfma_kernel: one launch per activation-row width for all of them,
 //                                                         quantising on load (kws_bank_kernels.hip)
 //   other int8 graphs                                     kws_bank_quantize_kernel writes all their input tensors in one pass, into each
-//                                                         member's scratch; then the member's own kws_launch_nn
-//   float32 graphs                                        the member's own nn_f32_device on the shared matrix, no logits tap
+//                                                         member's scratch; then the member's own network_device
+//   float32 graphs                                        the member's own network_device on the shared matrix, no logits tap
 // Nothing here reads a member's mode, fast counters or tap: these are the launches of KWS_MODE_EXACT.
 #include "kws_internal.h"
 #include "kws_bank.h"
@@ -96,20 +96,14 @@ static EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, 
         }
     }
     const int grid_cap = grid_cap_nn(b->m[0]);
-    int rc = kws_launch_bank_nn_mfma(b->d_rec, o16, 16, feat, (int)B, grid_cap, s);
-    if (!rc) rc = kws_launch_bank_nn_mfma(b->d_rec, o64, 64, feat, (int)B, grid_cap, s);
-    if (rc) return fail(KWS_ERROR_HIP, "bank NN kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
-    if ((rc = kws_launch_bank_quantize(feat, B * F, Q, s))) return fail(KWS_ERROR_HIP, "bank quantise kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    KWS_LAUNCH_TRY_OBJ("bank NN kernel", kws_launch_bank_nn_mfma(b->d_rec, o16, 16, feat, (int)B, grid_cap, s));
+    KWS_LAUNCH_TRY_OBJ("bank NN kernel", kws_launch_bank_nn_mfma(b->d_rec, o64, 64, feat, (int)B, grid_cap, s));
+    KWS_LAUNCH_TRY("bank quantise kernel", kws_launch_bank_quantize(feat, B * F, Q, s));
     for (size_t k = 0; k < K; ++k) {
         kws_handle *h = b->m[k];
         if (!scores[k]) continue;
         float *dst = scores[k] + row0 * h->model.labels.size();
-        if (h->is_float) {
-            if ((e = nn_f32_device(h, feat, B, dst, nullptr, s))) return e;
-        } else if (!kws_nn_uses_mfma(h->nn)) {
-            rc = kws_launch_nn(h->nn, h->s_q, (int)B, dst, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s);
-            if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        }
+        if ((h->is_float || !kws_nn_uses_mfma(h->nn)) && (e = network_device(h, feat, h->s_q, B, dst, nullptr, nullptr, nullptr, nullptr, nullptr, s))) return e;
     }
     return EI_IMPULSE_OK;
 }

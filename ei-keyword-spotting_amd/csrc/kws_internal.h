@@ -89,6 +89,15 @@ EI_IMPULSE_ERROR kws_last_error_code(void);
         hipError_t e_ = (expr);                                                                  \
         if (e_ != hipSuccess) return fail(KWS_ERROR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+// a kws_launch_* call (returns 0 or a hipError_t): "<what> launch failed: <the runtime's text>" on failure.  _OBJ: for the launches a call meets first, with
+// the hint at the usual cause
+#define KWS_LAUNCH_TRY_(what, hint, expr)                                                                                       \
+    do {                                                                                                                        \
+        const int rc_ = (expr);                                                                                                 \
+        if (rc_) return fail(KWS_ERROR_HIP, what " launch failed: %s" hint, hipGetErrorString((hipError_t)rc_));                \
+    } while (0)
+#define KWS_LAUNCH_TRY(what, expr) KWS_LAUNCH_TRY_(what, "", expr)
+#define KWS_LAUNCH_TRY_OBJ(what, expr) KWS_LAUNCH_TRY_(what, " (is the gfx950 code object present?)", expr)
 
 // ---- model blob (layout: tools/eon_import.py) -----------------------------------------------------------------------------
 
@@ -253,6 +262,7 @@ struct kws_handle {
     int *d_flags2 = nullptr;      // the same for the second tier: the clips that go to the exact cmvnw + network
     int *d_flags3 = nullptr;      // sink: when a call wants the feature matrix AND fused scores, the feature-emitting launch's list (P = 1/4) decides
                                   // for both -- the features are then the ones kws_extract_mfcc_batch_device returns -- and the fused launch's goes here
+                                  // (kws_api.cpp: fast_tier, the one place that resets and passes it)
     float *tap_logits = nullptr;  // kws_set_logits_tap: FULLY_CONNECTED outputs of the batch calls' clips (float32 graphs), device [B][labels]
     float *s_cep = nullptr;       // [B][n_features] exact cepstra of the first tier's clips (indexed by clip)
     // kws_scan.cpp: the bounded scratch of kws_scan_recordings_device and the cepstral rows of its last call (kws_windows.h); kws_destroy frees
@@ -339,7 +349,10 @@ KWS_INTERNAL EI_IMPULSE_ERROR mfcc_fused_device_plan(kws_handle *h, const KwsDsp
 // re-targeted at such a window: same tables, n_samples / n_frames / cmvnw's pad map for that row count (maps are cached on the handle)
 KWS_INTERNAL int kws_frames_for_length(const kws_handle *h, size_t n);
 KWS_INTERNAL EI_IMPULSE_ERROR kws_plan_for_length(kws_handle *h, size_t n, KwsDspPlan *out);
-KWS_INTERNAL EI_IMPULSE_ERROR nn_f32_device(kws_handle *h, const float *features, size_t B, float *scores, float *tap_logits, hipStream_t s);
+// the handle's exact network over B clips, or over the clips a list names (sel: [0] = count, [1 + i] = clip index): a float32 graph reads `features`
+// (kws_launch_nn_f32; tap_logits: where its FULLY_CONNECTED outputs go, or NULL), an int8 graph the tensor `q` (kws_launch_nn with its three taps, or NULL)
+KWS_INTERNAL EI_IMPULSE_ERROR network_device(kws_handle *h, const float *features, const int8_t *q, size_t B, float *scores, float *tap_logits, int8_t *tap_pooled,
+                                             int8_t *tap_fc, int8_t *tap_out, const int *sel, hipStream_t s);
 KWS_INTERNAL EI_IMPULSE_ERROR cmvn_nn_device(kws_handle *h, const float *mfcc, size_t B, float *features, int8_t *q, float *scores,
                                 int8_t *tap_pooled, int8_t *tap_fc, int8_t *tap_out, hipStream_t s, int ring_rows = 0, int ring_head = 0);
 }

@@ -178,14 +178,12 @@ EI_IMPULSE_ERROR kws_live_push_device(kws_live *lv, size_t n, const size_t *stre
     P1.n_frames = L.nf1;
     for (size_t g0 = 0; g0 < n_first; g0 += item_cap) {
         const int c = (int)std::min(item_cap, n_first - g0);
-        int rc = kws_launch_live_stage(pcm, lv->carry, S.meta, A, (long long)g0, c, 1, sl, L.grow, lv->cap, S.stage, S.wrap, st);
-        if (rc) return fail(KWS_ERROR_HIP, "live staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("live staging kernel", kws_launch_live_stage(pcm, lv->carry, S.meta, A, (long long)g0, c, 1, sl, L.grow, lv->cap, S.stage, S.wrap, st));
         if ((e = spectral_device(h, P0, S.stage, 0, c, first_rows + g0 * L.nf0 * ncols, nullptr, st, L.nf0 * ncols))) return e;
     }
     for (size_t g0 = 0; g0 < n_slots; g0 += item_cap) {
         const int c = (int)std::min(item_cap, n_slots - g0);
-        int rc = kws_launch_live_stage(pcm, lv->carry, S.meta, A, (long long)g0, c, 0, sl, L.grow, lv->cap, S.stage, S.wrap, st);
-        if (rc) return fail(KWS_ERROR_HIP, "live staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("live staging kernel", kws_launch_live_stage(pcm, lv->carry, S.meta, A, (long long)g0, c, 0, sl, L.grow, lv->cap, S.stage, S.wrap, st));
         if ((e = spectral_device(h, P1, S.stage, 0, c, slot_rows + g0 * L.nf1 * ncols, S.wrap, st, L.nf1 * ncols))) return e;
     }
     // 2. windows in chunks through the stream API's cmvnw + network; raw scores land where the moving average reads them
@@ -194,18 +192,15 @@ EI_IMPULSE_ERROR kws_live_push_device(kws_live *lv, size_t n, const size_t *stre
     if ((e = cnt.begin(S.acc, n_win, st))) return e;
     for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
         const int c = (int)std::min(win_chunk, n_win - g0);
-        int rc = kws_launch_live_gather(first_rows, slot_rows, lv->kept, S.meta, A, (long long)g0, c, L.nf0, L.nf1, L.ring_rows, lv->keep, (int)L.k_full,
-                                        rows, ncols, S.win, st);
-        if (rc) return fail(KWS_ERROR_HIP, "live gather kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("live gather kernel", kws_launch_live_gather(first_rows, slot_rows, lv->kept, S.meta, A, (long long)g0, c, L.nf0, L.nf1, L.ring_rows, lv->keep, (int)L.k_full,
+                                                                    rows, ncols, S.win, st));
         if ((e = kws_finish_window_chunk(h, S.win, c, raw + g0 * C, nullptr, cnt.fast, st)) || (e = cnt.chunk(st))) return e;
     }
     if ((e = cnt.end(st))) return e;
     // 3. the continuing streams' carry and retained rows (after every read of the old ones above)
-    int rc = kws_launch_live_commit(pcm, first_rows, slot_rows, S.meta, A, sl, lv->cap, L.nf0, L.nf1, lv->keep, ncols, lv->carry, lv->kept, st);
-    if (rc) return fail(KWS_ERROR_HIP, "live commit kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    KWS_LAUNCH_TRY("live commit kernel", kws_launch_live_commit(pcm, first_rows, slot_rows, S.meta, A, sl, lv->cap, L.nf0, L.nf1, lv->keep, ncols, lv->carry, lv->kept, st));
     // 4. the moving average, resumed per (stream, label)
-    if (n_win && (rc = kws_launch_live_maf(raw, scores, S.meta, A, (int)C, (int)L.k_full, lv->maf, st)))
-        return fail(KWS_ERROR_HIP, "live moving-average kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (n_win) KWS_LAUNCH_TRY("live moving-average kernel", kws_launch_live_maf(raw, scores, S.meta, A, (int)C, (int)L.k_full, lv->maf, st));
     commit_mirrors();
     return EI_IMPULSE_OK;
 }

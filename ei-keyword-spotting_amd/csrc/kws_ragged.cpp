@@ -80,13 +80,11 @@ static EI_IMPULSE_ERROR ragged_tuned(kws_handle *h, KwsRaggedScratch &S, const i
         for (size_t i = 0; i < B; ++i)
             if (((uintptr_t)S.h_clips[i].x & 15) != 0) S.h_clips[i].x = S.stage + (j++) * slot;
         HIP_TRY(hipMemcpyAsync(S.list, S.h_list.data(), n_staged * sizeof(KwsRaggedClip), hipMemcpyHostToDevice, s));
-        int rc = kws_launch_ragged_stage(S.list, (int)n_staged, S.stage, (int)slot, nullptr, s);
-        if (rc) return fail(KWS_ERROR_HIP, "staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("staging kernel", kws_launch_ragged_stage(S.list, (int)n_staged, S.stage, (int)slot, nullptr, s));
     }
     HIP_TRY(hipMemcpyAsync(S.clips, S.h_clips.data(), B * sizeof(KwsRaggedClip), hipMemcpyHostToDevice, s));
     const KwsRaggedArgs R = { S.clips, S.pad_maps, S.map_stride };
-    int rc = kws_launch_mfcc_ragged(h->dsp, R, (int)B, f, q, h->nn.in_scale, h->nn.in_zp, (int)h->model.nn_input_frame_size, grid_cap_mfcc(h), s);
-    if (rc) return fail(KWS_ERROR_HIP, "ragged MFCC kernel launch failed: %s (is the gfx950 code object present?)", hipGetErrorString((hipError_t)rc));
+    KWS_LAUNCH_TRY_OBJ("ragged MFCC kernel", kws_launch_mfcc_ragged(h->dsp, R, (int)B, f, q, h->nn.in_scale, h->nn.in_zp, (int)h->model.nn_input_frame_size, grid_cap_mfcc(h), s));
     return EI_IMPULSE_OK;
 }
 
@@ -131,19 +129,16 @@ static EI_IMPULSE_ERROR ragged_grouped(kws_handle *h, KwsRaggedScratch &S, const
         if ((e = kws_plan_for_length(h, rep[r], &P))) return e;
         P.n_samples = (int)slot[r];               // the slots' stride; the wrap sample is handed over per clip
         const KwsRaggedClip *list = S.list + first[r];
-        int rc = kws_launch_ragged_stage(list, (int)n, S.stage, (int)slot[r], S.wrap, s);
-        if (rc) return fail(KWS_ERROR_HIP, "gather kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("gather kernel", kws_launch_ragged_stage(list, (int)n, S.stage, (int)slot[r], S.wrap, s));
         if (mfe) {
             // (no pre-emphasis in front of feature::mfe: no wrap sample)
             if ((e = mfcc_fused_device_plan(h, P, S.stage, 0, n, S.packed, nullptr, s))) return e;
         } else {
             kws_handle::GenericBuf *g = nullptr;
             if ((e = generic_for(h, s, n, &g)) || (e = spectral_device(h, P, S.stage, 0, n, g->mfcc, S.wrap, s, 0))) return e;
-            rc = kws_launch_cmvn_generic(P, g->mfcc, (int)n, S.packed, nullptr, h->nn.in_scale, h->nn.in_zp, s);
-            if (rc) return fail(KWS_ERROR_HIP, "cmvnw kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+            KWS_LAUNCH_TRY("cmvnw kernel", kws_launch_cmvn_generic(P, g->mfcc, (int)n, S.packed, nullptr, h->nn.in_scale, h->nn.in_zp, s));
         }
-        rc = kws_launch_ragged_scatter(S.packed, list, (int)n, r * cols, (int)F, f, q, h->nn.in_scale, h->nn.in_zp, s);
-        if (rc) return fail(KWS_ERROR_HIP, "scatter kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("scatter kernel", kws_launch_ragged_scatter(S.packed, list, (int)n, r * cols, (int)F, f, q, h->nn.in_scale, h->nn.in_zp, s));
     }
     return EI_IMPULSE_OK;
 }
@@ -179,9 +174,6 @@ EI_IMPULSE_ERROR kws_run_classifier_ragged_device(kws_handle *h, const int16_t *
     const bool tuned = h->model.dsp.block == DSP_BLOCK_MFCC && kws_mfcc_ragged_serves(h->dsp);
     e = tuned ? ragged_tuned(h, S, pcm, offsets, lengths, B, f, q, s) : ragged_grouped(h, S, pcm, offsets, lengths, B, f, q, s);
     if (e || !scores) return e;
-    if (h->is_float) return nn_f32_device(h, f, B, scores, nullptr, s);
-    int rc = kws_launch_nn(h->nn, q, (int)B, scores, nullptr, h->pooled_tap_bytes, nullptr, nullptr, grid_cap_nn(h), s);
-    if (rc) return fail(KWS_ERROR_HIP, "NN kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return EI_IMPULSE_OK;
+    return network_device(h, f, q, B, scores, nullptr, nullptr, nullptr, nullptr, nullptr, s);
 }
 #pragma GCC visibility pop

@@ -125,14 +125,12 @@ EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, c
     P1.n_frames = L.nf1;
     for (size_t a0 = 0; a0 < (size_t)A; a0 += item_cap) {
         const int n = (int)std::min(item_cap, (size_t)A - a0);
-        int rc = kws_launch_scan_stage(pcm, d_off, d_len, d_ibase, A, (long long)a0, n, 1, slice, L.grow, S.stage, S.wrap, st);
-        if (rc) return fail(KWS_ERROR_HIP, "scan staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("scan staging kernel", kws_launch_scan_stage(pcm, d_off, d_len, d_ibase, A, (long long)a0, n, 1, slice, L.grow, S.stage, S.wrap, st));
         if ((e = spectral_device(h, P0, S.stage, 0, n, first_rows + a0 * L.nf0 * ncols, nullptr, st, L.nf0 * ncols))) return e;
     }
     for (size_t g0 = 0; g0 < n_slots; g0 += item_cap) {
         const int n = (int)std::min(item_cap, n_slots - g0);
-        int rc = kws_launch_scan_stage(pcm, d_off, d_len, d_ibase, A, (long long)g0, n, 0, slice, L.grow, S.stage, S.wrap, st);
-        if (rc) return fail(KWS_ERROR_HIP, "scan staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("scan staging kernel", kws_launch_scan_stage(pcm, d_off, d_len, d_ibase, A, (long long)g0, n, 0, slice, L.grow, S.stage, S.wrap, st));
         if ((e = spectral_device(h, P1, S.stage, 0, n, slot_rows + g0 * L.nf1 * ncols, S.wrap, st, L.nf1 * ncols))) return e;
     }
     // 2. windows in chunks through the stream API's cmvnw + network; raw scores land where the moving average reads them
@@ -141,14 +139,12 @@ EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, c
     if ((e = cnt.begin(S.acc, n_win, st))) return e;
     for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
         const int n = (int)std::min(win_chunk, n_win - g0);
-        int rc = kws_launch_scan_gather(first_rows, slot_rows, d_wbase, d_ibase, A, (long long)g0, n, L.nf0, L.nf1, L.ring_rows, rows, ncols, S.win, st);
-        if (rc) return fail(KWS_ERROR_HIP, "scan gather kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        KWS_LAUNCH_TRY("scan gather kernel", kws_launch_scan_gather(first_rows, slot_rows, d_wbase, d_ibase, A, (long long)g0, n, L.nf0, L.nf1, L.ring_rows, rows, ncols, S.win, st));
         if ((e = kws_finish_window_chunk(h, S.win, n, raw + g0 * C, nullptr, cnt.fast, st)) || (e = cnt.chunk(st))) return e;
     }
     if ((e = cnt.end(st))) return e;
     // 3. the moving average, one fresh filter per recording
-    int rc = kws_launch_scan_maf(raw, scores, d_wbase, A, (int)C, st);
-    if (rc) return fail(KWS_ERROR_HIP, "scan moving-average kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    KWS_LAUNCH_TRY("scan moving-average kernel", kws_launch_scan_maf(raw, scores, d_wbase, A, (int)C, st));
     return EI_IMPULSE_OK;
 }
 

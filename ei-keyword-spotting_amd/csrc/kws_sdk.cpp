@@ -44,8 +44,7 @@ EI_IMPULSE_ERROR kws_streams_init(kws_stream_batch *sb)          // run_classifi
         // the last step may still be writing feat[0] on the caller's stream (a hipStreamNonBlocking stream is not ordered with the
         // default stream the copy goes to)
         HIP_TRY(hipDeviceSynchronize());
-        int rc = kws_launch_unring(sb->feat[0], sb->feat[1], (int)sb->S, rows, P.n_cepstral, sb->ring_rows, sb->head, nullptr);
-        if (rc) return fail(KWS_ERROR_HIP, "copy kernel launch failed");
+        KWS_LAUNCH_TRY("copy kernel", kws_launch_unring(sb->feat[0], sb->feat[1], (int)sb->S, rows, P.n_cepstral, sb->ring_rows, sb->head, nullptr));
         HIP_TRY(hipDeviceSynchronize());
         std::swap(sb->feat[0], sb->feat[1]);
     }
@@ -140,8 +139,7 @@ EI_IMPULSE_ERROR kws_streams_step_device(kws_stream_batch *sb, const int16_t *sl
         }
     }
     if (e) return e;
-    int rc = kws_launch_maf(scores, sb->running_sum, sb->maf_buf, (int)(S * C), (int)sb->buf_idx, kMafTaps, st);
-    if (rc) return fail(KWS_ERROR_HIP, "moving-average kernel launch failed");
+    KWS_LAUNCH_TRY("moving-average kernel", kws_launch_maf(scores, sb->running_sum, sb->maf_buf, (int)(S * C), (int)sb->buf_idx, kMafTaps, st));
     if (++sb->buf_idx >= (uint32_t)kMafTaps) sb->buf_idx = 0;
     // "shift the feature buffer for new data": the ring's head moves on by one slice
     sb->head = (sb->head + nf) % sb->ring_rows;
@@ -327,7 +325,7 @@ static EI_IMPULSE_ERROR oneshot_enqueue(kws_handle *h, kws_handle::Ws &w, size_t
         *t1 = ei_read_timer_ms();
     }
     if (!e && other) e = kws_run_inference_batch_device(h, w.d_f, 1, w.d_s, w.st);
-    else if (!e) e = h->is_float ? nn_f32_device(h, w.d_f, 1, w.d_s, nullptr, w.st) : kws_nn_batch_device(h, w.d_q, 1, w.d_s, nullptr, nullptr, nullptr, w.st);
+    else if (!e) e = h->is_float ? network_device(h, w.d_f, nullptr, 1, w.d_s, nullptr, nullptr, nullptr, nullptr, nullptr, w.st) : kws_nn_batch_device(h, w.d_q, 1, w.d_s, nullptr, nullptr, nullptr, w.st);
     if (!e && hipMemcpyAsync(w.h_s, w.d_s, C * sizeof(float), hipMemcpyDeviceToHost, w.st) != hipSuccess) e = fail(KWS_ERROR_HIP, "d2h copy failed");
     (void)hipEventRecord(w.ev[2], w.st);
     return e;

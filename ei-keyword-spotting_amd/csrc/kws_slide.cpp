@@ -167,7 +167,6 @@ EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *
     if ((e = kws_upload_tables(S, { &off, &end, &wbase, &sbase, &ssrc, &send, &ibase }, st))) return e;
     const long long *d_off = S.meta, *d_end = d_off + A, *d_wbase = d_end + A, *d_sbase = d_wbase + A + 1, *d_ssrc = d_sbase + A + 1, *d_send = d_ssrc + NS,
                     *d_ibase = d_send + NS;
-    int rc = 0;
     if (shared) {
         // 1. the runs: the spectral launches of the one-shot path on items of nfi frames, each with the sample before it as its x[-1]
         KwsDspPlan PR = h->dsp;
@@ -176,9 +175,8 @@ EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *
         PR.wrap_index = PR.n_samples - 1;
         for (size_t g0 = 0; g0 < n_items; g0 += run_cap) {
             const int n = (int)std::min(run_cap, n_items - g0);
-            rc = kws_launch_slide_stage(pcm, d_ssrc, d_send, d_ibase, (int)NS, (long long)g0, n, (long long)G.ips, (long long)(G.phases * G.hop),
-                                        (long long)nfi * G.stride, (int)run_len, G.pre, S.stage, S.wrap, st);
-            if (rc) return fail(KWS_ERROR_HIP, "slide staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+            KWS_LAUNCH_TRY("slide staging kernel", kws_launch_slide_stage(pcm, d_ssrc, d_send, d_ibase, (int)NS, (long long)g0, n, (long long)G.ips, (long long)(G.phases * G.hop),
+                                                                          (long long)nfi * G.stride, (int)run_len, G.pre, S.stage, S.wrap, st));
             if ((e = spectral_device(h, PR, S.stage, 0, n, S.rows + g0 * nfi * ncols, S.wrap, st, nfi * ncols))) return e;
         }
     }
@@ -189,21 +187,18 @@ EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *
         if (shared) {
             for (size_t i0 = 0; G.pre && i0 < (size_t)n; i0 += first_cap * nfi) {
                 const int nw = (int)std::min(first_cap * nfi, (size_t)n - i0), ni = (nw + nfi - 1) / nfi;
-                rc = kws_launch_slide_stage_first(pcm, d_off, d_wbase, (int)A, (long long)(g0 + i0), nw, nfi, (int)G.S1, G.used, (long long)G.hop, (int)G.clip,
-                                                  S.stage, S.wrap, st);
-                if (rc) return fail(KWS_ERROR_HIP, "slide staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+                KWS_LAUNCH_TRY("slide staging kernel", kws_launch_slide_stage_first(pcm, d_off, d_wbase, (int)A, (long long)(g0 + i0), nw, nfi, (int)G.S1, G.used, (long long)G.hop, (int)G.clip,
+                                                                                    S.stage, S.wrap, st));
                 if ((e = spectral_device(h, PF, S.stage, 0, ni, S.first + i0 * ncols, S.wrap, st, nfi * ncols))) return e;
             }
-            rc = kws_launch_slide_gather(S.rows, S.first, d_wbase, d_sbase, d_ibase, (int)A, (long long)g0, n, (long long)G.phases, (long long)G.pitch, nfi,
-                                         G.pre, G.nf, ncols, S.win, st);
-            if (rc) return fail(KWS_ERROR_HIP, "slide gather kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+            KWS_LAUNCH_TRY("slide gather kernel", kws_launch_slide_gather(S.rows, S.first, d_wbase, d_sbase, d_ibase, (int)A, (long long)g0, n, (long long)G.phases, (long long)G.pitch, nfi,
+                                                                          G.pre, G.nf, ncols, S.win, st));
         } else {
             // the windows as aligned clips (recordings as slots, windows as their items, one hop apart), then the handle's own plan
             for (size_t i0 = 0; i0 < (size_t)n; i0 += clip_cap) {
                 const int nw = (int)std::min(clip_cap, (size_t)n - i0);
-                rc = kws_launch_slide_stage(pcm, d_off, d_end, d_wbase, (int)A, (long long)(g0 + i0), nw, 1, (long long)G.hop, 0, (int)G.clip, 0, S.stage,
-                                            nullptr, st);
-                if (rc) return fail(KWS_ERROR_HIP, "slide staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+                KWS_LAUNCH_TRY("slide staging kernel", kws_launch_slide_stage(pcm, d_off, d_end, d_wbase, (int)A, (long long)(g0 + i0), nw, 1, (long long)G.hop, 0, (int)G.clip, 0, S.stage,
+                                                                              nullptr, st));
                 if ((e = spectral_device(h, h->dsp, S.stage, 0, nw, S.win + i0 * F, nullptr, st, 0))) return e;
             }
         }

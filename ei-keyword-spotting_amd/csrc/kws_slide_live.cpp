@@ -172,15 +172,13 @@ EI_IMPULSE_ERROR kws_slide_live_push_device(kws_slide_live *sl, size_t n, const 
     }
     // per-entry tables (kws_slide_live_kernels.hip KwsSlideLiveMeta)
     if ((e = kws_upload_tables(S, { &off, &n0, &len, &sid, &w0, &pc0, &np, &rbase, &wbase }, st))) return e;
-    int rc = 0;
     if (shared && n_items) {
         // 1. the rows this push needs: nfi independent frames per item, S1 samples apart, each with its predecessor in the sample before it
         const KwsDspPlan PF = G.first_plan(h);
         for (size_t g0 = 0; g0 < n_items; g0 += item_cap) {
             const int c = (int)std::min(item_cap, n_items - g0);
-            rc = kws_launch_slide_live_stage_rows(pcm, sl->carry, S.meta, A, (long long)g0, c, (long long)n_frames, nfi, (int)G.S1, G.used, G.stride,
-                                                  (long long)G.hop, (int)G.clip, G.pre, S.stage, S.wrap, st);
-            if (rc) return fail(KWS_ERROR_HIP, "slide live staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+            KWS_LAUNCH_TRY("slide live staging kernel", kws_launch_slide_live_stage_rows(pcm, sl->carry, S.meta, A, (long long)g0, c, (long long)n_frames, nfi, (int)G.S1, G.used, G.stride,
+                                                                                         (long long)G.hop, (int)G.clip, G.pre, S.stage, S.wrap, st));
             if ((e = spectral_device(h, PF, S.stage, 0, c, S.rows + g0 * nfi * ncols, S.wrap, st, nfi * ncols))) return e;
         }
     }
@@ -190,13 +188,11 @@ EI_IMPULSE_ERROR kws_slide_live_push_device(kws_slide_live *sl, size_t n, const 
     for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
         const int c = (int)std::min(win_chunk, n_win - g0);
         if (shared) {
-            rc = kws_launch_slide_live_gather(S.rows, sl->kept, S.meta, A, (long long)g0, c, (long long)sl->hs, G.run, G.pre, ncols, S.win, st);
-            if (rc) return fail(KWS_ERROR_HIP, "slide live gather kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+            KWS_LAUNCH_TRY("slide live gather kernel", kws_launch_slide_live_gather(S.rows, sl->kept, S.meta, A, (long long)g0, c, (long long)sl->hs, G.run, G.pre, ncols, S.win, st));
         } else {
             for (size_t i0 = 0; i0 < (size_t)c; i0 += clip_cap) {
                 const int nw = (int)std::min(clip_cap, (size_t)c - i0);
-                rc = kws_launch_slide_live_stage_clips(pcm, sl->carry, S.meta, A, (long long)(g0 + i0), nw, (long long)G.hop, (int)G.clip, S.stage, st);
-                if (rc) return fail(KWS_ERROR_HIP, "slide live staging kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+                KWS_LAUNCH_TRY("slide live staging kernel", kws_launch_slide_live_stage_clips(pcm, sl->carry, S.meta, A, (long long)(g0 + i0), nw, (long long)G.hop, (int)G.clip, S.stage, st));
                 if ((e = spectral_device(h, h->dsp, S.stage, 0, nw, S.win + i0 * F, nullptr, st, 0))) return e;
             }
         }
@@ -206,8 +202,7 @@ EI_IMPULSE_ERROR kws_slide_live_push_device(kws_slide_live *sl, size_t n, const 
     }
     if ((e = cnt.end(st))) return e;
     // 3. the new carry and retained rows (after every read of the old ones above)
-    rc = kws_launch_slide_live_commit(pcm, S.rows, S.meta, A, (long long)G.hop, (int)G.clip, shared ? G.run : 0, ncols, sl->carry, sl->kept, st);
-    if (rc) return fail(KWS_ERROR_HIP, "slide live commit kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    KWS_LAUNCH_TRY("slide live commit kernel", kws_launch_slide_live_commit(pcm, S.rows, S.meta, A, (long long)G.hop, (int)G.clip, shared ? G.run : 0, ncols, sl->carry, sl->kept, st));
     commit_mirrors();
     return EI_IMPULSE_OK;
 }

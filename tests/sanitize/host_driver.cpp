@@ -134,10 +134,49 @@ static void print_gain(const char *path, kws_handle *h)
     printf("\n");
 }
 
+// --routes: which device operations the batch and stream entry points enqueue, per mode -- each call once with B = 5, a tag line in the stub's
+// record (hip_stub.cpp: KWS_STUB_RECORD) before it and the call's return code after it; tests/test_fast_routes_host.py compares the
+// operations between the tags with its table.
+extern "C" void kws_stub_note(const char *line);
+static void print_routes(const char *path, kws_handle *h)
+{
+    const size_t n = (size_t)kws_clip_samples(h), F = (size_t)kws_feature_count(h), C = (size_t)kws_label_count(h), B = 5;
+    const char *base = strrchr(path, '/') ? strrchr(path, '/') + 1 : path;
+    std::vector<int16_t> pcm(B * n + 8, 1), slice(B * (n / 4) + 8, 2);
+    std::vector<float> scores(B * C + 1), feats(B * F + 1), cep(B * F + 1);
+    std::vector<int8_t> q(B * F + 1);
+    int8_t *const qp = kws_model_is_float(h) ? nullptr : q.data();
+    char line[512];
+    for (int mode = 0; mode < 2; mode++) {
+        const char *mname = mode == KWS_MODE_FAST ? "fast" : "exact";
+        if (kws_set_mode(h, mode) != EI_IMPULSE_OK) { snprintf(line, sizeof line, "ROUTE %s %s refused", base, mname); kws_stub_note(line); continue; }
+        auto call = [&](const char *what, auto &&fn) {
+            snprintf(line, sizeof line, "ROUTE %s %s %s", base, mname, what);
+            kws_stub_note(line);
+            const int rc = (int)fn();
+            snprintf(line, sizeof line, "rc %d", rc);
+            kws_stub_note(line);
+        };
+        call("classify_features", [&] { return kws_run_classifier_batch_device(h, pcm.data(), B, scores.data(), feats.data(), qp, nullptr); });
+        call("classify_scores", [&] { return kws_run_classifier_batch_device(h, pcm.data(), B, scores.data(), nullptr, nullptr, nullptr); });
+        call("extract_mfcc", [&] { return kws_extract_mfcc_batch_device(h, pcm.data(), B, feats.data(), qp, nullptr); });
+        call("cmvn_inference_features", [&] { return kws_cmvn_inference_batch_device(h, cep.data(), B, scores.data(), feats.data(), qp, nullptr); });
+        call("cmvn_inference_scores", [&] { return kws_cmvn_inference_batch_device(h, cep.data(), B, scores.data(), nullptr, nullptr, nullptr); });
+        kws_stream_batch *sb = nullptr;
+        if (kws_streams_create(h, B, &sb) != EI_IMPULSE_OK) continue;
+        int produced = 0;
+        // (a quarter window per step: the rolling buffer is full from the fourth step on -- the first three only run the spectral stage)
+        for (const char *what : { "streams_step_1", "streams_step_2", "streams_step_3", "streams_step_4", "streams_step_5" })
+            call(what, [&] { return kws_streams_step_device(sb, slice.data(), n / 4, nullptr, scores.data(), &produced, nullptr); });
+        kws_streams_destroy(sb);
+    }
+}
+
 int main(int argc, char **argv)
 {
     const bool gain_only = argc > 1 && strcmp(argv[1], "--gain") == 0, trace_only = argc > 1 && strcmp(argv[1], "--trace") == 0;
-    for (int i = gain_only || trace_only ? 2 : 1; i < argc; i++) {
+    const bool routes_only = argc > 1 && strcmp(argv[1], "--routes") == 0;
+    for (int i = gain_only || trace_only || routes_only ? 2 : 1; i < argc; i++) {
         FILE *f = fopen(argv[i], "rb");
         if (!f) { printf("%s rc open-failed\n", argv[i]); continue; }
         std::vector<unsigned char> blob;
@@ -151,6 +190,7 @@ int main(int argc, char **argv)
         fflush(stdout);
         if (rc == EI_IMPULSE_OK && gain_only) print_gain(argv[i], h);
         else if (rc == EI_IMPULSE_OK && trace_only) print_trace(h);
+        else if (rc == EI_IMPULSE_OK && routes_only) print_routes(argv[i], h);
         else if (rc == EI_IMPULSE_OK) walk(h);
         if (rc == EI_IMPULSE_OK) kws_destroy(h);
     }

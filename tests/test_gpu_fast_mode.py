@@ -171,17 +171,22 @@ def test_fast_mode_int8_models_flip_rate_and_exact_network(name, pkg, oracle):
     s_only, _, _ = run_device(pkg, gm, pkg.MODE_FAST, pcm, want_f=False)
     assert (bits(s_only) == bits(s)).all()
     so, fo, qo = oracle_all(path, seed, B)
+    check_int8_fast_bar(name, om, s, f, q, so, fo, qo)
+    gm.close()
+
+
+def check_int8_fast_bar(name, om, s, f, q, so, fo, qo):
+    """The bar of an int8 graph's fast-mode scores, features and input tensors against the reference's (so, fo, qo) for the same clips."""
     flips = (q != qo).sum(axis=1)
     changed = (s != so).any(axis=1)
     print("\n%s fast mode, %d clips: %.4f int8 input flips per clip (%d values per clip), %d clips with a changed score, "
-          "max |feature - oracle| = %.3g" % (name, B, flips.mean(), q.shape[1], int(changed.sum()), np.abs(f - fo).max()))
+          "max |feature - oracle| = %.3g" % (name, len(s), flips.mean(), q.shape[1], int(changed.sum()), np.abs(f - fo).max()))
     assert np.abs(f - fo).max() <= FAST_FEATURE_TOL
     assert np.abs(q.astype(np.int32) - qo.astype(np.int32)).max() <= 1        # a flip is one quantisation step
     assert flips.mean() <= 0.1 and changed.mean() <= 0.02
     assert not changed[flips == 0].any()                                      # same tensor => same scores, bit for bit
     for i in np.nonzero(changed)[0][:64]:
         assert (bits(om.dequantize(om.nn_invoke(q[i]))) == bits(s[i])).all(), i
-    gm.close()
 
 
 def test_fast_mode_ill_conditioned_batch_is_rerun_exactly(pkg, gpu_models=("cfg2_mfcc40_f32.kwsm", "l476_no_yes.kwsm")):
