@@ -97,7 +97,12 @@ const char *kws_mfcc_kernel_name(const kws_handle *h)
 }
 const char *kws_nn_kernel_name(const kws_handle *h)
 {
+    // a strided or dilated block in front of a dense stack: the strided form of the trunk, then the dense kernel
+    if (h->is_float ? kws_nnf_dense(h->nnf) && kws_nnf_strided(h->nnf) : kws_nn_dense(h->nn) && kws_nn_strided(h->nn))
+        return h->is_float ? "kws_nn_f32_sd_trunk_kernel + kws_dense_f32_kernel" : "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel";
     if (h->is_float ? kws_nnf_dense(h->nnf) != nullptr : kws_nn_dense(h->nn) != nullptr) return h->is_float ? "kws_dense_f32_kernel" : "kws_dense_i8_kernel";
+    // a strided or dilated block somewhere in the graph: the strided forms
+    if (h->is_float ? kws_nnf_strided(h->nnf) : kws_nn_strided(h->nn)) return h->is_float ? "kws_nn_f32_sd_kernel" : "kws_nn_sd_kernel";
     return h->is_float ? "kws_nn_f32_kernel" : kws_nn_uses_mfma(h->nn) ? "kws_nn_mfma_kernel" : "kws_nn_kernel";
 }
 
@@ -119,6 +124,8 @@ EI_IMPULSE_ERROR kws_set_mode(kws_handle *h, int mode)
     if (!h || (mode != KWS_MODE_EXACT && mode != KWS_MODE_FAST)) return fail(KWS_ERROR_BAD_ARGUMENT, "kws_set_mode: bad argument");
     if (mode == KWS_MODE_FAST && h->is_float && kws_nnf_dense(h->nnf))
         return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a float32 graph with a dense stack has no calibrated logit gain (the guard needs one); it keeps the exact kernels");
+    if (mode == KWS_MODE_FAST && (h->is_float ? kws_nnf_strided(h->nnf) : kws_nn_strided(h->nn)))
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a graph with a strided or dilated convolution keeps the exact kernels (no fused plan, no calibrated logit gain)");
     if (mode == KWS_MODE_FAST && !h->fast_plain_ok) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "%s", h->fast_why.c_str());
     std::lock_guard<std::mutex> lk(h->mu);
     h->mode = mode;

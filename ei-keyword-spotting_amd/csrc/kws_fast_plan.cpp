@@ -720,6 +720,13 @@ static EI_IMPULSE_ERROR build_fast_fused(kws_handle *h, int wps, KwsFastPlan &F)
 
 EI_IMPULSE_ERROR build_fast_plans(kws_handle *h)
 {
+    // A strided or dilated graph has no fast mode: the fused plans and the gain calibration's host forward pass know stride-1 geometry only, so
+    // neither is built on such a plan (never calibrate on the wrong geometry); kws_set_mode answers with the reason
+    if (h->is_float ? kws_nnf_strided(h->nnf) : kws_nn_strided(h->nn)) {
+        h->fast_plain_ok = h->fast_fused_ok = h->fast_q_ok = false;
+        h->fast_why = "fast mode: a graph with a strided or dilated convolution keeps the exact kernels";
+        return EI_IMPULSE_OK;
+    }
     // float32 graphs of the tuned DSP shapes: the guard needs the graph's logit gain (kws_gain.cpp), ~50 ms of host work per model
     if (h->is_float && !h->dsp.generic && !kws_nnf_dense(h->nnf) && h->nnf.n_blocks > 0 && h->nnf.blk[0].in_w == h->dsp.n_frames && h->nnf.blk[0].in_c == h->dsp.n_cepstral)
         kws_calibrate_gain(h);

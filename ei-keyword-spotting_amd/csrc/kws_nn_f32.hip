@@ -36,7 +36,9 @@ __host__ __device__ __forceinline__ bool nnf_staged(const KwsConvBlockF32 &k) { 
 __host__ __device__ __forceinline__ int nnf_ntb_of(const KwsConvBlockF32 &k) { return k.fused_pool ? k.pool_w : (k.out_w + k.tb - 1) / k.tb; }
 __host__ __device__ __forceinline__ int nnf_rows_of(const KwsConvBlockF32 &k)       // rows of the zero-padded input image
 {
-    const int a = k.pad_left + k.in_w, b = nnf_ntb_of(k) * k.tb + k.taps - 1;  // rows the blocked walk touches (k.tb is final)
+    // rows the blocked walk touches (k.tb is final): output t, tap j reads row t * stride + j * dilation, and the last, ragged block of tb time steps is
+    // computed whole (stride 1, dilation 1: ntb * tb + taps - 1 as ever)
+    const int a = k.pad_left + k.in_w, b = (nnf_ntb_of(k) * k.tb - 1) * k.stride + (k.taps - 1) * k.dilation + 1;
     return a > b ? a : b;
 }
 // x / d for an item index: the plan's reciprocal where it is exact (x d < 2^20), a real division (~35 vector instructions) elsewhere
@@ -252,6 +254,149 @@ __device__ __forceinline__ void nnf_conv_ob(const KwsConvBlockF32 &k, const floa
     else nnf_conv<TB, 1, VEC4>(k, x, wt, y, dst, lane);
 }
 
+// ---- strided / dilated forms: output t, tap j reads image row t * stride + j * dilation, so a chain's activations are no longer one contiguous run
+//      of taps * in_c floats: the steps run tap by tap, channel by channel inside a tap -- the reference's order, products and sums rounded separately -- and
+//      the zero rows of the padded image stand in for the skipped taps exactly as in the stride-1 forms.  Weights keep their LDS layouts (nnf_w_index).
+template <int TB, int OB, bool VEC4>
+__device__ __forceinline__ void nnf_conv_sd(const KwsConvBlockF32 &k, const float *__restrict__ x, const float *__restrict__ wt,
+                                            float *__restrict__ y, const NnfDst &dst, int lane)
+{
+    const int J = k.taps * k.in_c, ocp = nnf_ocp(k);
+    const int n_ob = (k.out_c + OB - 1) / OB, n_tb = nnf_ntb(k);
+    const bool direct = nnf_direct(k);
+    const int xs = k.stride * k.in_c, ts = k.dilation * k.in_c;          // floats between the rows of two consecutive outputs / taps
+    for (int item = lane; item < n_tb * n_ob; item += 64) {
+        const int tb = nnf_div(item, n_ob, k.inv_item20), ob = item - tb * n_ob;
+        const int t0 = tb * TB, oc0 = ob * OB;
+        float acc[TB][OB];
+#pragma unroll
+        for (int i = 0; i < TB; ++i)
+#pragma unroll
+            for (int o = 0; o < OB; ++o) acc[i][o] = 0.0f;
+        const float *xp = x + t0 * xs;
+        // step j's OB weights: [j][oc] for register-blocked blocks, [oc block][j][OB] for one-time-step blocks (nnf_w_index)
+        const float *wp = TB == 1 ? wt + (size_t)ob * J * OB : wt + oc0;
+        const int wstep = TB == 1 ? OB : ocp;
+        auto load_w = [&](int j, float (&w)[OB]) {
+            if constexpr (OB == 4 && TB != 1) { const float4 v = *(const float4 *)(wp + j * wstep); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+            else if constexpr (OB == 2 && TB != 1) { const float2 v = *(const float2 *)(wp + j * wstep); w[0] = v.x; w[1] = v.y; }
+            else {
+#pragma unroll
+                for (int o = 0; o < OB; ++o) w[o] = wp[j * wstep + o];
+            }
+        };
+        if (VEC4 && (k.in_c & 3) == 0) {
+            // rows are 16-byte aligned: one 16-byte read per time row brings the activations of 4 consecutive steps of a tap
+            for (int tap = 0; tap < k.taps; ++tap) {
+                const float *xt = xp + tap * ts;
+                for (int c = 0; c < k.in_c; c += 4) {
+                    float4 xv[TB];
+                    float w[4][OB];
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) xv[i] = *(const float4 *)(xt + i * xs + c);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) load_w(tap * k.in_c + c + u, w[u]);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {                  // chain order: channels c, c+1, c+2, c+3
+#pragma unroll
+                        for (int i = 0; i < TB; ++i) {
+                            const float xs_ = u == 0 ? xv[i].x : u == 1 ? xv[i].y : u == 2 ? xv[i].z : xv[i].w;
+#pragma unroll
+                            for (int o = 0; o < OB; ++o) {
+                                const float prod = xs_ * w[u][o];
+                                acc[i][o] += prod;
+                            }
+                        }
+                    }
+                }
+            }
+        } else {
+            for (int tap = 0; tap < k.taps; ++tap) {
+                const float *xt = xp + tap * ts;
+                for (int c = 0; c < k.in_c; ++c) {
+                    float w[OB], xv[TB];
+                    load_w(tap * k.in_c + c, w);
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) xv[i] = xt[i * xs + c];
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) {
+#pragma unroll
+                        for (int o = 0; o < OB; ++o) {
+                            const float prod = xv[i] * w[o];
+                            acc[i][o] += prod;
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < OB; ++o) {
+            const int oc = oc0 + o;
+            if (oc >= k.out_c) continue;
+            const float bv = k.bias[oc], av = k.addc[oc];
+            float mx = -FLT_MAX;
+#pragma unroll
+            for (int i = 0; i < TB; ++i) {
+                if (t0 + i < k.out_w) {
+                    float v = act_clamp(acc[i][o] + bv, k.conv_min, k.conv_max);
+                    if (k.has_add) v = act_clamp(v + av, k.add_min, k.add_max);
+                    if (k.fused_pool) mx = mx < v ? v : mx;             // MAX_POOL_2D: std::max(max, v), window order
+                    else if (direct) dst.p[(dst.row0 + t0 + i) * dst.stride + oc] = v;
+                    else y[(t0 + i) * k.out_c + oc] = v;
+                }
+            }
+            if (k.fused_pool) dst.p[(dst.row0 + tb) * dst.stride + oc] = act_clamp(mx, k.pool_min, k.pool_max);
+        }
+    }
+}
+
+template <int TB>
+__device__ __forceinline__ void nnf_dwconv_sd(const KwsConvBlockF32 &k, const float *__restrict__ x, const float *__restrict__ wt,
+                                              float *__restrict__ y, const NnfDst &dst, int lane)
+{
+    const int ocp = nnf_ocp(k), n_tb = nnf_ntb(k);
+    const bool direct = nnf_direct(k);
+    const int xs = k.stride * k.in_c, ts = k.dilation * k.in_c;
+    for (int item = lane; item < n_tb * k.out_c; item += 64) {
+        const int tb = nnf_div(item, k.out_c, k.inv_outc20), oc = item - tb * k.out_c;
+        const int t0 = tb * TB;
+        const float *xp = x + t0 * xs + (k.depth_mult == 1 ? oc : oc / k.depth_mult);
+        float acc[TB];
+#pragma unroll
+        for (int i = 0; i < TB; ++i) acc[i] = 0.0f;
+        for (int tap = 0; tap < k.taps; ++tap) {
+            const float w = wt[tap * ocp + oc];
+#pragma unroll
+            for (int i = 0; i < TB; ++i) {
+                const float prod = xp[i * xs + tap * ts] * w;
+                acc[i] += prod;
+            }
+        }
+        const float bv = k.bias[oc], av = k.addc[oc];
+        float mx = -FLT_MAX;
+#pragma unroll
+        for (int i = 0; i < TB; ++i) {
+            if (t0 + i < k.out_w) {
+                float v = act_clamp(acc[i] + bv, k.conv_min, k.conv_max);
+                if (k.has_add) v = act_clamp(v + av, k.add_min, k.add_max);
+                if (k.fused_pool) mx = mx < v ? v : mx;
+                else if (direct) dst.p[(dst.row0 + t0 + i) * dst.stride + oc] = v;
+                else y[(t0 + i) * k.out_c + oc] = v;
+            }
+        }
+        if (k.fused_pool) dst.p[(dst.row0 + tb) * dst.stride + oc] = act_clamp(mx, k.pool_min, k.pool_max);
+    }
+}
+
+template <int TB, bool VEC4>
+__device__ __forceinline__ void nnf_conv_ob_sd(const KwsConvBlockF32 &k, const float *x, const float *wt, float *y, const NnfDst &dst, int lane)
+{
+    if (k.depthwise) nnf_dwconv_sd<TB>(k, x, wt, y, dst, lane);
+    else if (k.ob == 4) nnf_conv_sd<TB, 4, VEC4>(k, x, wt, y, dst, lane);
+    else if (k.ob == 2) nnf_conv_sd<TB, 2, VEC4>(k, x, wt, y, dst, lane);
+    else nnf_conv_sd<TB, 1, VEC4>(k, x, wt, y, dst, lane);
+}
+
 // LDS layout shared by host and device: weights of every block, then per wave the ping-pong input images A (even blocks) and
 // B (odd blocks), the un-pooled conv output Y (only when some block cannot pool in registers) and 128 floats for FC/softmax
 struct NnfLayout { int w_floats, a_floats, b_floats, y_floats, fc_floats, vec_floats; };
@@ -284,6 +429,19 @@ __host__ __device__ __forceinline__ NnfLayout nnf_layout(const KwsNnPlanF32 &N)
 #include "kws_nn_f32_generic.h"
 #undef KWS_NNF_TRUNK
 #undef KWS_NNF_NAME
+// the strided / dilated forms: the same text, with every block's convolution through nnf_conv_ob_sd
+#define nnf_conv_ob nnf_conv_ob_sd
+#define KWS_NNF_TRUNK 0
+#define KWS_NNF_NAME kws_nn_f32_sd_kernel
+#include "kws_nn_f32_generic.h"
+#undef KWS_NNF_TRUNK
+#undef KWS_NNF_NAME
+#define KWS_NNF_TRUNK 1
+#define KWS_NNF_NAME kws_nn_f32_sd_trunk_kernel
+#include "kws_nn_f32_generic.h"
+#undef KWS_NNF_TRUNK
+#undef KWS_NNF_NAME
+#undef nnf_conv_ob
 
 // ---------------------------------------------------------------------------------------------------------
 //  kws_dense_f32_kernel: the dense stack of a float32 graph (1 .. 4 FULLY_CONNECTED, fully_connected.h:26-60, then SOFTMAX, softmax.h:31-63).
@@ -465,7 +623,9 @@ static int launch_dense_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, c
     const int n_waves = kws_nn_f32_waves(N);
     const size_t smem = kws_nn_f32_smem_bytes(N, n_waves);
     const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / smem);
-    const void *fn = n_waves <= 8 ? (const void *)kws_nn_f32_trunk_kernel<512> : (const void *)kws_nn_f32_trunk_kernel<1024>;
+    const bool sd = kws_nnf_strided(N) != 0;                                  // the strided form of the trunk
+    const void *fn = sd ? (n_waves <= 8 ? (const void *)kws_nn_f32_sd_trunk_kernel<512> : (const void *)kws_nn_f32_sd_trunk_kernel<1024>)
+                        : (n_waves <= 8 ? (const void *)kws_nn_f32_trunk_kernel<512> : (const void *)kws_nn_f32_trunk_kernel<1024>);
     if (smem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
@@ -475,7 +635,13 @@ static int launch_dense_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, c
         const int c1 = n_clips - c0 > chunk ? c0 + chunk : n_clips, n = c1 - c0;
         int grid = (n + n_waves - 1) / n_waves;
         if (grid > n_cu * per_cu) grid = n_cu * per_cu;
-        if (n_waves <= 8)
+        if (sd && n_waves <= 8)
+            hipLaunchKernelGGL(kws_nn_f32_sd_trunk_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
+                               kws_dev_f32_prof, sel);
+        else if (sd)
+            hipLaunchKernelGGL(kws_nn_f32_sd_trunk_kernel<1024>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
+                               kws_dev_f32_prof, sel);
+        else if (n_waves <= 8)
             hipLaunchKernelGGL(kws_nn_f32_trunk_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
                                kws_dev_f32_prof, sel);
         else
@@ -500,12 +666,20 @@ int kws_launch_nn_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, const f
     const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / smem);
     int grid = (n_clips + n_waves - 1) / n_waves;
     if (grid > n_cu * per_cu * grid_mult) grid = n_cu * per_cu * grid_mult;
-    const void *fn = n_waves <= 8 ? (const void *)kws_nn_f32_kernel<512> : (const void *)kws_nn_f32_kernel<1024>;
+    const bool sd = kws_nnf_strided(N) != 0;                                  // the strided form of the same kernel
+    const void *fn = sd ? (n_waves <= 8 ? (const void *)kws_nn_f32_sd_kernel<512> : (const void *)kws_nn_f32_sd_kernel<1024>)
+                        : (n_waves <= 8 ? (const void *)kws_nn_f32_kernel<512> : (const void *)kws_nn_f32_kernel<1024>);
     if (smem > 64 * 1024) {                    // opt in to more than the default 64 KB of dynamic LDS
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
     }
-    if (n_waves <= 8)
+    if (sd && n_waves <= 8)
+        hipLaunchKernelGGL(kws_nn_f32_sd_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips,
+                           scores, tap_logits, kws_dev_f32_prof, sel);
+    else if (sd)
+        hipLaunchKernelGGL(kws_nn_f32_sd_kernel<1024>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips,
+                           scores, tap_logits, kws_dev_f32_prof, sel);
+    else if (n_waves <= 8)
         hipLaunchKernelGGL(kws_nn_f32_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips,
                            scores, tap_logits, kws_dev_f32_prof, sel);
     else

@@ -9,6 +9,7 @@
 #include "kws_nn_int8_dev.h"
 
 
+#define KWS_NN_SD 0
 #define KWS_NN_TRUNK 0
 #define KWS_NN_GENERIC_NAME kws_nn_kernel
 #include "kws_nn_int8_generic.h"
@@ -19,6 +20,23 @@
 #include "kws_nn_int8_generic.h"
 #undef KWS_NN_TRUNK
 #undef KWS_NN_GENERIC_NAME
+#undef KWS_NN_SD
+
+// the strided / dilated forms: the same text with KWS_NN_SD 1; their image rows are nn_rows_sd's
+#define nn_rows nn_rows_sd
+#define KWS_NN_SD 1
+#define KWS_NN_TRUNK 0
+#define KWS_NN_GENERIC_NAME kws_nn_sd_kernel
+#include "kws_nn_int8_generic.h"
+#undef KWS_NN_TRUNK
+#undef KWS_NN_GENERIC_NAME
+#define KWS_NN_TRUNK 1
+#define KWS_NN_GENERIC_NAME kws_nn_sd_trunk_kernel
+#include "kws_nn_int8_generic.h"
+#undef KWS_NN_TRUNK
+#undef KWS_NN_GENERIC_NAME
+#undef KWS_NN_SD
+#undef nn_rows
 
 #include "kws_dense_i8.h"
 
@@ -171,7 +189,7 @@ size_t kws_nn_smem_bytes(const KwsNnPlan &N, int n_waves)
         s += ((size_t)k.w_bytes + 15) & ~(size_t)15;
         s += k.has_lut ? (size_t)k.out_c * 256 : 0;
         s += (size_t)k.out_c * 16;                      // requantisation constants
-        const int ab = nn_rows(k) * k.in_cpad;
+        const int ab = nn_rows_sd(k) * k.in_cpad;             // (= nn_rows(k) for a stride-1, dilation-1 block)
         act[b & 1] = ab > act[b & 1] ? ab : act[b & 1];
     }
     return s + (size_t)n_waves * (((act[0] + 15) & ~15) + ((act[1] + 15) & ~15) + nn_fcx_bytes(N) + 64 * 4);
@@ -197,7 +215,9 @@ static int launch_dense_i8(const KwsNnPlan &N, const int8_t *q_in, int n_clips, 
     int nw = KWS_NN_WAVES_MAX;
     while (nw > KWS_NN_WAVES && kws_nn_smem_bytes(N, nw) > 158 * 1024) --nw;
     const size_t tsmem = kws_nn_smem_bytes(N, nw);
-    const void *fn = nw <= 12 ? (const void *)kws_nn_trunk_kernel<12> : (const void *)kws_nn_trunk_kernel<16>;
+    const bool sd = kws_nn_strided(N) != 0;                                   // the strided form of the trunk
+    const void *fn = sd ? (nw <= 12 ? (const void *)kws_nn_sd_trunk_kernel<12> : (const void *)kws_nn_sd_trunk_kernel<16>)
+                        : (nw <= 12 ? (const void *)kws_nn_trunk_kernel<12> : (const void *)kws_nn_trunk_kernel<16>);
     if (tsmem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tsmem);
         if (e != hipSuccess) return (int)e;
@@ -207,7 +227,9 @@ static int launch_dense_i8(const KwsNnPlan &N, const int8_t *q_in, int n_clips, 
         const int c1 = n_clips - c0 > chunk ? c0 + chunk : n_clips, n = c1 - c0;
         int grid = (n + nw - 1) / nw;
         if (grid > grid_cap / 4) grid = grid_cap / 4;                         // grid_cap = 4 workgroups per CU; one persistent workgroup per CU
-        if (nw <= 12) hipLaunchKernelGGL(kws_nn_trunk_kernel<12>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
+        if (sd && nw <= 12) hipLaunchKernelGGL(kws_nn_sd_trunk_kernel<12>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
+        else if (sd) hipLaunchKernelGGL(kws_nn_sd_trunk_kernel<16>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
+        else if (nw <= 12) hipLaunchKernelGGL(kws_nn_trunk_kernel<12>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
         else hipLaunchKernelGGL(kws_nn_trunk_kernel<16>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
         hipLaunchKernelGGL(kws_dense_i8_kernel, dim3(dense_grid(n)), dim3(KWS_WAVE * KWS_DENSE_WAVES), smem, stream, D, (const int8_t *)ho, 0, c0, c1, n_clips, scores, taps);
         const int rc = (int)hipGetLastError();
@@ -240,6 +262,16 @@ int kws_launch_nn(const KwsNnPlan &N, const int8_t *q_in, int n_clips, float *sc
     const size_t smem = kws_nn_smem_bytes(N, nw);
     grid = (n_clips + nw - 1) / nw;
     if (grid > (grid_cap / 4) * per_cu) grid = (grid_cap / 4) * per_cu;          // grid_cap = 4 workgroups per CU
+    if (kws_nn_strided(N)) {                       // a strided or dilated block somewhere in the graph -- the strided form of the same kernel
+        const void *fn = nw <= 12 ? (const void *)kws_nn_sd_kernel<12> : (const void *)kws_nn_sd_kernel<16>;
+        if (smem > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            if (e != hipSuccess) return (int)e;
+        }
+        if (nw <= 12) hipLaunchKernelGGL(kws_nn_sd_kernel<12>, dim3(grid), dim3(KWS_WAVE * nw), smem, stream, N, q_in, n_clips, scores, taps);
+        else hipLaunchKernelGGL(kws_nn_sd_kernel<16>, dim3(grid), dim3(KWS_WAVE * nw), smem, stream, N, q_in, n_clips, scores, taps);
+        return (int)hipGetLastError();
+    }
     if (nw <= 12) {
         if (smem > 64 * 1024) {                    // wide models: opt in to more than the default 64 KB of dynamic LDS
             hipError_t e = hipFuncSetAttribute((const void *)kws_nn_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);

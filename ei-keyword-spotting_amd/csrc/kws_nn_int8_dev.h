@@ -74,6 +74,17 @@ __host__ __device__ inline int nn_rows(const KwsConvBlock &k)
     return max(k.in_w, walk) + k.taps;
 }
 
+// ... of a strided or dilated block, in the strided forms of the generic kernel: output t, tap j reads row t * stride + j * dilation.  The furthest
+// output any lane computes is the last one of the ragged last group of KWS_POOL_MAX time steps (un-pooled walks) or of the last pooling window (pooled dot4
+// and depthwise walks: pool <= KWS_POOL_MAX outputs from (pool_w - 1) * pool_stride), stored or not.  A stride-1, dilation-1 block keeps nn_rows().
+__host__ __device__ inline int nn_rows_sd(const KwsConvBlock &k)
+{
+    if (k.stride == 1 && k.dilation == 1) return nn_rows(k);
+    const int walk = (k.out_w + KWS_POOL_MAX - 1) & ~(KWS_POOL_MAX - 1), pooled = (k.pool_w - 1) * k.pool_stride + k.pool;
+    const int last_t = max(walk, pooled) - 1;
+    return max(k.in_w + k.pad_left, last_t * k.stride + (k.taps - 1) * k.dilation + 1);
+}
+
 struct NnTaps {            // optional debug outputs for the parity tests (all int8, per clip)
     int8_t *pooled;        // concatenation of every block's pooled output [pool_w][out_c]
     int pooled_stride;
@@ -427,6 +438,7 @@ __device__ __forceinline__ void nn_mfma_clip(const Ctx &c, const KwsNnPlan &N, c
 // the matrix-core kernel covers this graph shape; anything else runs on kws_nn_kernel
 static bool nn_fits_mfma(const KwsNnPlan &N)
 {
+    if (kws_nn_strided(N)) return false;                         // (the strided forms of kws_nn_kernel)
     if (N.n_blocks != 2 || kws_nn_dense(N)) return false;        // (a dense stack behind the blocks: the trunk form of kws_nn_kernel + kws_dense_i8_kernel)
     const KwsConvBlock &a = N.blk[0], &b = N.blk[1];
     if (a.depthwise || b.depthwise) return false;

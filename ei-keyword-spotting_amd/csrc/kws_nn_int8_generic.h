@@ -1,7 +1,9 @@
 // kws_nn_int8_generic.h -- the text of kws_nn_kernel, the generic int8 network kernel.  Part of kws_nn_int8.hip, which includes it TWICE: as kws_nn_kernel
 // (KWS_NN_TRUNK 0: the kernel as it always was, token for token, so that its code object does not move) and as kws_nn_trunk_kernel (KWS_NN_TRUNK 1: the
 // form in front of a dense stack -- no head: the last block's output of list entries ci0 .. ci1 - 1 goes to handoff [ci - ci0][fc_in] in HBM, where
-// kws_dense_i8_kernel reads it).  No include guard.
+// kws_dense_i8_kernel reads it).  KWS_NN_SD 1 gives the strided / dilated forms of both (kws_nn_sd_kernel, kws_nn_sd_trunk_kernel): output t, tap j
+// of a block reads image row t * stride + j * dilation, image rows are counted by nn_rows_sd (the including file maps nn_rows to it), and a strided or dilated
+// depthwise block takes the one-output-per-lane path.  With KWS_NN_SD 0 the preprocessor leaves the text the stride-1 kernels always had.  No include guard.
 // MAXW: waves per workgroup the build allows.  16 (four per SIMD) caps the kernel at 128 VGPRs, which it overruns by 20 (176 B of
 // scratch per lane); 12 (three per SIMD) gives it 168 and no scratch -- the launcher picks by measurement (below).
 template <int MAXW>
@@ -117,7 +119,14 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
                 dbase[pw * dstride + oc] = o;
                 if (tp) tp[pw * out_c + oc] = o;
             };
+#if KWS_NN_SD
+            const int cs = k.stride, cd = k.dilation;
+            // the 4-channel depthwise path's row registers are sized at compile time for contiguous rows: a strided or dilated depthwise block takes the
+            // one-output-per-lane path below (a register window of (tb - 1) * stride + (taps - 1) * dilation + 1 rows has no bound the compiler could unroll to)
+            if (k.depthwise && k.depth_mult == 1 && (out_c & 3) == 0 && k.taps <= 8 && cs == 1 && cd == 1) {
+#else
             if (k.depthwise && k.depth_mult == 1 && (out_c & 3) == 0 && k.taps <= 8) {
+#endif
                 // integer_ops/depthwise_conv.h:64-103, one input channel per output.  A lane owns 4 consecutive channels of
                 // one pooling window (or of 8 time steps when the block is not pooled): the tb + taps - 1 activation rows
                 // it needs are read ONCE as 32-bit words (4 channels each), the 4 x taps weights as 8 words, everything
@@ -205,6 +214,15 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
 #pragma unroll
                     for (int i = 0; i < KWS_POOL_MAX; ++i) acc[i] = 0;
                     const int8_t *wrow = wb + oc * tp4;
+#if KWS_NN_SD
+                    const int8_t *xcol = cur + t0 * cs * k.in_cpad + oc / k.depth_mult;
+                    for (int tap = 0; tap < k.taps; ++tap) {
+                        const int wv = wrow[tap];
+#pragma unroll
+                        for (int i = 0; i < KWS_POOL_MAX; ++i)
+                            if (i < k.pool) acc[i] += wv * (int)xcol[(i * cs + tap * cd) * k.in_cpad];
+                    }
+#else
                     const int8_t *xcol = cur + t0 * k.in_cpad + oc / k.depth_mult;
                     for (int tap = 0; tap < k.taps; ++tap) {
                         const int wv = wrow[tap];
@@ -212,6 +230,7 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
                         for (int i = 0; i < KWS_POOL_MAX; ++i)
                             if (i < k.pool) acc[i] += wv * (int)xcol[(i + tap) * k.in_cpad];
                     }
+#endif
                     int m = (int)0x80000000;
 #pragma unroll
                     for (int i = 0; i < KWS_POOL_MAX; ++i)
@@ -287,14 +306,23 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
                     const int8_t *w0 = wb + (size_t)oc0 * k.taps * k.in_cpad;
                     const int8_t *w1 = w0 + (ob == 2 ? k.taps * k.in_cpad : 0);
                     for (int tap = 0; tap < k.taps; ++tap) {
+#if KWS_NN_SD
+                        const int8_t *xrow = cur + (t0 * cs + tap * cd) * k.in_cpad;
+                        const int xstep = cs * k.in_cpad;                                  // bytes between the rows of two consecutive outputs
+#else
                         const int8_t *xrow = cur + (t0 + tap) * k.in_cpad;
+#endif
                         for (int c16 = 0; c16 < c16n; ++c16) {
                             const int4 wa = *(const int4 *)(w0 + tap * k.in_cpad + 16 * c16);
                             const int4 wb4 = *(const int4 *)(w1 + tap * k.in_cpad + 16 * c16);
 #pragma unroll
                             for (int i = 0; i < KWS_POOL_MAX; ++i) {
                                 if (i < tb) {
+#if KWS_NN_SD
+                                    const int4 xv = *(const int4 *)(xrow + i * xstep + 16 * c16);
+#else
                                     const int4 xv = *(const int4 *)(xrow + i * k.in_cpad + 16 * c16);
+#endif
                                     int a = acc[i][0], c = acc[i][1];
                                     a = __builtin_amdgcn_sdot4(wa.x, xv.x, a, false);
                                     a = __builtin_amdgcn_sdot4(wa.y, xv.y, a, false);

@@ -358,6 +358,23 @@ static EI_IMPULSE_ERROR build_dense_i8(kws_handle *h, size_t i, int cur, int inp
     return EI_IMPULSE_OK;
 }
 
+// Stride and dilation of a conv node.  Both come from an untrusted blob, so they are bounded BEFORE any arithmetic on them: with
+// 1 <= stride <= in_w <= KWS_NN_IMAGE_MAX, 1 <= taps <= 16 and (taps - 1) * dilation < KWS_NN_IMAGE_MAX every product and sum of h_out_size / h_pad_amount
+// / nn_rows stays far inside an int.  Returns why the node is refused, or NULL.
+#define KWS_NN_IMAGE_MAX 4096
+static const char *h_conv_geometry_why(bool dw, int padding, int in_w, int f_w, int stride_w, int stride_h, int dil_w, int dil_h)
+{
+    if (stride_h != 1 || dil_h != 1) return "stride_h / dilation_height_factor other than 1 (only the time axis may be strided or dilated)";
+    if (stride_w == 1 && dil_w == 1) return nullptr;
+    if (in_w < 1 || in_w > KWS_NN_IMAGE_MAX || f_w < 1 || f_w > 16 || stride_w < 1 || stride_w > in_w || dil_w < 1 || dil_w >= KWS_NN_IMAGE_MAX ||
+        (f_w - 1) * dil_w >= KWS_NN_IMAGE_MAX)
+        return "stride / dilation outside the kernels' limits (1 <= stride <= input width, (taps - 1) * dilation below the 4096-row image bound)";
+    if (dw && dil_w > 1 && padding != 2)
+        return "SAME-padded depthwise with dilation > 1 is not served: the reference computes a depthwise convolution's padding with dilation 1 "
+               "(depthwise_conv.cc:489-492) while its loops dilate, so its output is shifted";
+    return nullptr;
+}
+
 // Recognise the Edge Impulse 1-D CNN family and fold its per-model constants.
 EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
 {
@@ -399,19 +416,23 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         const int out_c = dw ? w.dim4(3) : w.dim4(0), f_h = w.dim4(1), f_w = w.dim4(2);
         const int depth_mult = dw ? cv.p[6] : 1;
         const int padding = cv.p[0], stride_w = cv.p[1], stride_h = cv.p[2], act = cv.p[3], dil_w = cv.p[4], dil_h = cv.p[5];
-        if (x.dim4(0) != 1 || in_h != 1 || f_h != 1 || stride_w != 1 || stride_h != 1 || dil_w != 1 || dil_h != 1 || !w.is_const ||
+        if (x.dim4(0) != 1 || in_h != 1 || f_h != 1 || !w.is_const ||
             (dw ? (w.dim4(0) != 1 || depth_mult < 1 || out_c != in_c * depth_mult) : (w.dim4(3) != in_c)) || (bias && !bias->is_const) ||
             f_w > 16 || out_c > 64 || x.dims.size() != 4 || (size_t)w.nbytes != (size_t)out_c * f_w * (dw ? 1 : in_c))
-            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu is not a stride-1 1xK (depthwise) convolution over time", i);
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu is not a 1xK (depthwise) convolution over time", i);
+        if (const char *why = h_conv_geometry_why(dw, padding, in_w, f_w, stride_w, stride_h, dil_w, dil_h))
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: %s (stride %d x %d, dilation %d x %d)", i, why, stride_w, stride_h, dil_w, dil_h);
         if (cur_w && (cur_w != in_w || cur_c != in_c)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "shape mismatch into conv %zu", i);
         if (bias && (bias->type != TYPE_I32 || (int)bias->nbytes != out_c * 4)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu bias", i);
         if (w.type != TYPE_I8 || x.type != TYPE_I8 || y.type != TYPE_I8) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu tensor types", i);
-        const int out_w = h_out_size(padding, in_w, f_w, 1, 1);
-        const int pad_left = h_pad_amount(1, 1, in_w, f_w, out_w);
-        if (out_w != y.dim4(2) || y.dim4(3) != out_c) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu output shape", i);
+        const int out_w = h_out_size(padding, in_w, f_w, stride_w, dil_w);         // padding.h with the real stride and dilation; a negative total padding is 0
+        const int pad_left = h_pad_amount(stride_w, dil_w, in_w, f_w, out_w);
+        if (out_w < 1 || out_w != y.dim4(2) || y.dim4(3) != out_c)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu output shape: the tensor has %d rows, stride %d and dilation %d give %d", i, y.dim4(2), stride_w, dil_w, out_w);
         KwsConvBlock &k = N.blk[N.n_blocks];
         k.in_w = in_w; k.in_c = in_c; k.in_cpad = (in_c + 15) & ~15; k.out_c = out_c; k.taps = f_w; k.pad_left = pad_left;
         k.out_w = out_w; k.in_zp = x.zero[0]; k.out_zp = y.zero[0];
+        k.stride = (short)stride_w; k.dilation = (short)dil_w;         // (both below KWS_NN_IMAGE_MAX: h_conv_geometry_why)
         k.depthwise = dw ? 1 : 0; k.depth_mult = depth_mult;
         h_act_range(act, y.scale[0], y.zero[0], &k.act_min, &k.act_max);
         // the reference's int8 depthwise op clamps to the int8 range whatever its fused activation says
@@ -522,7 +543,7 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         }
         // un-pooled CONV_2D blocks (e.g. the pointwise halves of a depthwise-separable CNN) run on the matrix cores in the
         // generic kernel: 16-byte k-groups need activation rows of 16, 32 or 64 bytes
-        k.mfma = (!dw && k.pool == 1 && in_c <= 64 && out_c <= 32 && out_w <= 64 && f_w <= 8) ? 1 : 0;
+        k.mfma = (!dw && k.pool == 1 && in_c <= 64 && out_c <= 32 && out_w <= 64 && f_w <= 8 && stride_w == 1 && dil_w == 1) ? 1 : 0;      // (its tiles read contiguous rows)
         if (k.mfma) {
             const int cp = in_c <= 16 ? 16 : in_c <= 32 ? 32 : 64;
             if (cp != k.in_cpad) {
@@ -650,16 +671,20 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
         const int out_c = dw ? w.dim4(3) : w.dim4(0), f_h = w.dim4(1), f_w = w.dim4(2);
         const int depth_mult = dw ? cv.p[6] : 1;
         const int padding = cv.p[0], stride_w = cv.p[1], stride_h = cv.p[2], act = cv.p[3], dil_w = cv.p[4], dil_h = cv.p[5];
-        if (x.dim4(0) != 1 || in_h != 1 || f_h != 1 || stride_w != 1 || stride_h != 1 || dil_w != 1 || dil_h != 1 || !w.is_const ||
+        if (x.dim4(0) != 1 || in_h != 1 || f_h != 1 || !w.is_const ||
             (dw ? (w.dim4(0) != 1 || depth_mult < 1 || out_c != in_c * depth_mult) : (w.dim4(3) != in_c)) || (bias && !bias->is_const) ||
             f_w > 16 || out_c > 64 || x.dims.size() != 4 || (size_t)w.nbytes != sizeof(float) * out_c * f_w * (dw ? 1 : in_c))
-            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu is not a stride-1 1xK (depthwise) convolution over time", i);
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu is not a 1xK (depthwise) convolution over time", i);
+        if (const char *why = h_conv_geometry_why(dw, padding, in_w, f_w, stride_w, stride_h, dil_w, dil_h))
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: %s (stride %d x %d, dilation %d x %d)", i, why, stride_w, stride_h, dil_w, dil_h);
         if (cur_w && (cur_w != in_w || cur_c != in_c)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "shape mismatch into conv %zu", i);
-        const int out_w = h_out_size(padding, in_w, f_w, 1, 1);
-        const int pad_left = h_pad_amount(1, 1, in_w, f_w, out_w);
-        if (out_w != y.dim4(2) || y.dim4(3) != out_c) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu output shape", i);
+        const int out_w = h_out_size(padding, in_w, f_w, stride_w, dil_w);         // padding.h with the real stride and dilation; a negative total padding is 0
+        const int pad_left = h_pad_amount(stride_w, dil_w, in_w, f_w, out_w);
+        if (out_w < 1 || out_w != y.dim4(2) || y.dim4(3) != out_c)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu output shape: the tensor has %d rows, stride %d and dilation %d give %d", i, y.dim4(2), stride_w, dil_w, out_w);
         KwsConvBlockF32 &k = N.blk[N.n_blocks];
         k.in_w = in_w; k.in_c = in_c; k.out_c = out_c; k.taps = f_w; k.pad_left = pad_left; k.out_w = out_w;
+        k.stride = (short)stride_w; k.dilation = (short)dil_w;         // (both below KWS_NN_IMAGE_MAX: h_conv_geometry_why)
         k.depthwise = dw ? 1 : 0; k.depth_mult = depth_mult;
         h_act_range_f32(act, &k.conv_min, &k.conv_max);           // the float depthwise op honours its activation
         std::vector<float> wv = floats(w), bv(out_c, 0.0f), av(out_c, 0.0f);

@@ -72,7 +72,7 @@ struct KwsConvBlock {
     int in_w, in_c, in_cpad;   // time steps, channels, channels padded to a multiple of 16
     int out_c;
     int taps, pad_left;        // filter width, SAME padding on the left
-    int out_w;                 // conv output width (stride 1)
+    int out_w;                 // conv output width
     int pool, pool_stride, pool_w;   // pool window, stride, pooled width
     int in_zp;                 // input zero point (= padding value so that (x + offset) == 0)
     int out_zp, act_min, act_max;    // conv output zero point and clamp
@@ -81,6 +81,10 @@ struct KwsConvBlock {
     int mfma;                  // generic kernel: this block's convolution runs on the matrix cores (CONV_2D, no pooling,
                                // in_cpad 16 / 32 / 64, out_c <= 32, out_w <= 64)
     int w_bytes;               // bytes of w
+    short stride, dilation;    // along time: output t, tap j reads padded-image row t * stride + j * dilation.  A block with either above 1 never sets
+                               // mfma, and its graph runs on the strided forms of the generic kernel (kws_nn_sd_kernel, kws_nn_sd_trunk_kernel).  Two 16-bit
+                               // fields (the plan bounds both below 4096) in the four bytes that padded w_bytes up to the pointers: the struct the stride-1
+                               // kernels take by value keeps its size and every offset, and with them their code objects (profiles/strided_codeobj.md)
     const int8_t *w;           // conv: [out_c][taps][in_cpad], zero padded; depthwise: [out_c][taps padded to 4]
     const int32_t *bias_eff;   // [out_c] bias + input_offset * sum(w)
     const int32_t *mult;       // [out_c] per-channel quantized multiplier
@@ -153,6 +157,13 @@ struct KwsNnPlan {
     int n_labels;
 };
 static inline const KwsDensePlan *kws_nn_dense(const KwsNnPlan &N) { return N.fc_out == 0 ? N.dense : nullptr; }
+// some block of the graph is strided or dilated: the graph runs on the strided forms of the generic kernels, never on a matrix-core or fast-mode kernel
+static inline int kws_nn_strided(const KwsNnPlan &N)
+{
+    for (int b = 0; b < N.n_blocks; ++b)
+        if (N.blk[b].stride != 1 || N.blk[b].dilation != 1) return 1;
+    return 0;
+}
 
 // ---- float32 models (the reference's float TFLite-Micro kernels: reference/conv.h:28-99, add.h:179-215,
 //      pooling.h:189-237, fully_connected.h:26-60, softmax.h:31-63) -------------------------------------------
@@ -169,6 +180,8 @@ struct KwsConvBlockF32 {
     float conv_min, conv_max;      // fused activation range of the convolution
     float add_min, add_max;        // fused activation range of the ADD (ReLU: [0, max])
     float pool_min, pool_max;
+    short stride, dilation;        // along time, as KwsConvBlock's (kws_nn_f32_sd_kernel, kws_nn_f32_sd_trunk_kernel): in the four bytes that padded pool_max up to
+                                   // the pointers, so that the plan the stride-1 kernels read keeps every offset
     const float *w;                // conv: [out_c][taps][in_c]; depthwise: [taps][out_c]
     const float *bias;             // [out_c]
     const float *addc;             // [out_c] constant operand of the ADD
@@ -183,6 +196,12 @@ struct KwsNnPlanF32 {
     union { const float *fc_bias; KwsHandoff *handoff; };             // [fc_out]
 };
 static inline const KwsDensePlanF32 *kws_nnf_dense(const KwsNnPlanF32 &N) { return N.fc_out == 0 ? N.dense : nullptr; }
+static inline int kws_nnf_strided(const KwsNnPlanF32 &N)
+{
+    for (int b = 0; b < N.n_blocks; ++b)
+        if (N.blk[b].stride != 1 || N.blk[b].dilation != 1) return 1;
+    return 0;
+}
 // the trunk's output [clips][inputs] for one chunk of clips, per stream (launches on different streams may overlap); allocated on first use, freed with
 // the handle
 #define KWS_HANDOFF_SETS 8

@@ -57,7 +57,14 @@ int kws_dense_layer_count(const kws_handle *h);          /* FULLY_CONNECTED laye
                                                             at most 8 streams without waiting -- a ninth takes over the oldest buffer after a device
                                                             synchronise, which is only safe when no other thread is inside a call on that handle.  Graphs
                                                             without a dense stack, and dense-only graphs, use no such buffer */
-const char *kws_nn_kernel_name(const kws_handle *h);    /* which network kernel serves this model (diagnostics) */
+/* Conv blocks (every family above): CONV_2D 1xK / 1x1 and DEPTHWISE_CONV_2D over time, each with stride_w >= 1 and dilation_width_factor >= 1 (1 <= stride <=
+ * input rows, (taps - 1) * dilation < 4096), int8 and float32; output rows and padding follow kernels/padding.h with the real stride and dilation.  Refused with
+ * KWS_ERROR_UNSUPPORTED_MODEL (kws_last_error names the node and the reason): stride_h / dilation_height_factor other than 1; SAME-padded DEPTHWISE_CONV_2D with
+ * dilation > 1 (the reference computes that padding with dilation 1, depthwise_conv.cc:489-492, so its result is shifted); an output tensor of another width; a
+ * padded input image past the kernels' LDS budget.  A graph with a strided or dilated block runs in KWS_MODE_EXACT only: kws_set_mode(h, KWS_MODE_FAST) returns
+ * KWS_ERROR_UNSUPPORTED_MODEL and the handle goes on serving KWS_MODE_EXACT. */
+const char *kws_nn_kernel_name(const kws_handle *h);    /* which network kernel serves this model (diagnostics); "kws_nn_sd_kernel" / "kws_nn_f32_sd_kernel" (in front of a
+                                                            dense stack: "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel", float32 likewise) for a graph with a strided or dilated block */
 const char *kws_mfcc_kernel_name(const kws_handle *h);  /* the spectral kernel of int16 batches, MFCC and MFE blocks alike: "kws_mfcc8_kernel" / "kws_mfcc_kernel" (tuned shapes), "kws_mfcc8_kernel (chunked)" (general plans whose spectral stage fits the tuned kernel: chunks of at most 49 frames), "kws_spectral_lds_kernel" (general shapes), "kws_spectral_generic_kernel" (those whose arrays exceed the LDS) */
 int kws_model_is_float(const kws_handle *h);             /* 1: float32 graph (EI_CLASSIFIER_TFLITE_INPUT_QUANTIZED == 0) */
 

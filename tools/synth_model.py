@@ -45,9 +45,9 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
     def fused(v, a):                                    # TfLiteFusedActivation: 0 none, 1 relu, 2 relu_n1_to_1, 3 relu6
         return v if a == 0 else np.maximum(v, 0.0) if a == 1 else np.clip(v, -1.0, 1.0) if a == 2 else np.clip(v, 0.0, 6.0)
 
-    def windows(v, size, out_w, stride, pad_left):      # [n][out_w][size][c], rows outside the image = NaN (callers mask them)
+    def windows(v, size, out_w, stride, pad_left, dil=1):      # [n][out_w][size][c], rows outside the image = NaN (callers mask them)
         n, w, c = v.shape
-        idx = np.arange(out_w)[:, None] * stride - pad_left + np.arange(size)[None, :]
+        idx = np.arange(out_w)[:, None] * stride - pad_left + np.arange(size)[None, :] * dil
         ok = (idx >= 0) & (idx < w)
         g = v[:, np.clip(idx, 0, w - 1), :]
         return g, ok
@@ -62,14 +62,16 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
         if nd["op"] == 0:                               # RESHAPE
             n = a.shape[0]
             act[o] = a.reshape(n, -1) if len(dims) == 2 else a.reshape(n, -1, dims[-1])
-        elif nd["op"] in (1, 6):                        # CONV_2D / DEPTHWISE_CONV_2D, 1 x K, stride 1
+        elif nd["op"] in (1, 6):                        # CONV_2D / DEPTHWISE_CONV_2D, 1 x K, stride p[1] and dilation p[4] along time
             w = const[nd["in"][1]]
             b = const[nd["in"][2]]
             n, in_w, in_c = a.shape
             taps = w.shape[2]
-            out_w = in_w if p[0] == 1 else in_w - taps + 1
-            pad_left = max(0, (out_w - 1) + taps - in_w) // 2
-            g, ok = windows(a, taps, out_w, 1, pad_left)
+            stride, dil = p[1], p[4]
+            eff = (taps - 1) * dil + 1                   # kernels/padding.h: ComputeOutSize, ComputePaddingWithOffset (a negative total is 0)
+            out_w = (in_w + stride - 1) // stride if p[0] == 1 else (in_w + stride - eff) // stride
+            pad_left = max(0, (out_w - 1) * stride + eff - in_w) // 2
+            g, ok = windows(a, taps, out_w, stride, pad_left, dil)
             g = np.where(ok[None, :, :, None], g, 0.0)
             if nd["op"] == 1:
                 v = np.einsum("nwtc,otc->nwo", g, w[:, 0]) + b
@@ -185,7 +187,7 @@ def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=2
 def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((30, 7, 7), (10, 7, 7)), n_labels=4,
                      conv_bias=False, add_bias=True, num_filters=32, raw_samples=16000, fft_length=256, frame_length=0.02,
                      frame_stride=0.02, pre_cof=0.98, dsp_block="mfcc", logit_std=None, quantize_filterbank=False, edit=None, dense=None,
-                     calib=None, conv_valid=()):
+                     calib=None, conv_valid=(), conv_stride=None, conv_dilation=None):
     """blocks: sequence of
          (out_channels, taps, pool)              CONV_2D 1xK (+ optional int32 bias) -> ADD(int8 per-channel)+ReLU -> MAX_POOL
          ("dw", depth_mult, taps, pool, act)     DEPTHWISE_CONV_2D 1xK with int32 bias and fused activation -> MAX_POOL
@@ -193,7 +195,10 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
        (pool 1 = no pooling node, a negative pool = VALID padding: the ragged tail of the time axis is dropped; act: TfLiteFusedActivation 0 none, 1 relu, 3 relu6).
        A pool may also be a tuple (window, stride, valid): a MAX_POOL_2D whose stride differs from its window (overlapping or skipping windows), with
        VALID (valid true) or SAME padding.  conv_valid: indices into blocks of the convolutions with VALID padding (output rows = rows - taps + 1)
-       instead of SAME.  Neither draws anything: with integer pools and conv_valid=() every blob is the one the same arguments gave before.
+       instead of SAME.  conv_stride / conv_dilation: {index into blocks: stride_w / dilation_width_factor} of the convolutions (all three block kinds)
+       that stride or dilate along time; the output rows follow kernels/padding.h (SAME: ceil(rows / stride); VALID: (rows - ((taps - 1) * dilation + 1))
+       // stride + 1).  None of these draws anything: with integer pools, conv_valid=() and neither dict given every blob is the one the same arguments
+       gave before.
        logit_std: None = the FULLY_CONNECTED layer as drawn (random weights and biases: one class usually wins every clip by tens
        of logit units, the softmax is saturated and a score says nothing about the logits behind it); a number = the head is
        calibrated (calibrate_head): scale and biases are set so that, over standardised random feature matrices -- which is what
@@ -263,12 +268,18 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
         node(0, [tp, shape_const([1, 1, w, c_out])], [t5])
         cur = t5
 
-    def conv_rows(bi, taps):                                                # (TfLitePadding, output rows) of block bi's convolution
+    strides, dilations = dict(conv_stride or {}), dict(conv_dilation or {})
+    assert all(0 <= bi < len(blocks) for bi in list(strides) + list(dilations))
+
+    def conv_rows(bi, taps):                                                # TfLitePadding of block bi's convolution; w becomes its output rows
         nonlocal w
+        s_, eff = strides.get(bi, 1), (taps - 1) * dilations.get(bi, 1) + 1
+        assert 1 <= s_ <= w
         if bi in conv_valid:
-            assert w - taps + 1 >= 1
-            w = w - taps + 1
+            assert (w - eff) // s_ + 1 >= 1 and w >= eff
+            w = (w - eff) // s_ + 1
             return 2
+        w = (w + s_ - 1) // s_
         return 1
 
     for bi, blk in enumerate(blocks):
@@ -283,7 +294,7 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
             out_scale, out_zp = rscale(0.03, 0.12), int(rng.integers(-128, -90)) if act else int(rng.integers(-30, 40))
             padding = conv_rows(bi, taps)
             tc = T(9, [1, 1, w, c_out], scale=[out_scale], zero=[out_zp])
-            node(6, [cur, tw, tb], [tc], [padding, 1, 1, act, 1, 1, mult])    # SAME (or VALID), stride 1
+            node(6, [cur, tw, tb], [tc], [padding, strides.get(bi, 1), 1, act, dilations.get(bi, 1), 1, mult])    # SAME (or VALID)
             cur, cur_scale, cur_zp = tc, out_scale, out_zp
             add_pool(pool)
             c = c_out
@@ -296,8 +307,9 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
             bias = rng.integers(-300, 300, c_out).astype(np.int32)
             tb = T(2, [c_out], True, [cur_scale * s_ for s_ in wscales], [0] * c_out, bias.tobytes())
             out_scale, out_zp = rscale(0.03, 0.12), int(rng.integers(-128, -90)) if act else int(rng.integers(-30, 40))
+            padding = conv_rows(bi, 1)
             tc = T(9, [1, 1, w, c_out], scale=[out_scale], zero=[out_zp])
-            node(1, [cur, tw, tb], [tc], [1, 1, 1, act, 1, 1])
+            node(1, [cur, tw, tb], [tc], [padding, strides.get(bi, 1), 1, act, dilations.get(bi, 1), 1])
             cur, cur_scale, cur_zp = tc, out_scale, out_zp
             c = c_out
             continue
@@ -311,7 +323,7 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
         out_scale, out_zp = rscale(0.03, 0.12), int(rng.integers(-30, 40))
         padding = conv_rows(bi, taps)
         tc = T(9, [1, 1, w, oc], scale=[out_scale], zero=[out_zp])
-        node(1, [cur, tw, tb], [tc], [padding, 1, 1, 0, 1, 1])              # SAME (or VALID), stride 1, no activation
+        node(1, [cur, tw, tb], [tc], [padding, strides.get(bi, 1), 1, 0, dilations.get(bi, 1), 1])      # SAME (or VALID), no activation
         cur, cur_scale, cur_zp = tc, out_scale, out_zp
         if add_bias:
             t3 = T(9, [1, w, oc], scale=[cur_scale], zero=[cur_zp])
@@ -381,11 +393,17 @@ def main():
     ap.add_argument("--blocks", default="30,7,7;10,7,7", help="per block: out_channels,taps,pool | dw,depth_mult,taps,pool,act | pw,out_channels,act")
     ap.add_argument("--dense", default="", help="hidden FULLY_CONNECTED layers in front of the head: units,act;units,act (act: 0 none, 1 relu, 2 relu_n1_to_1, 3 relu6)")
     ap.add_argument("--logit-std", type=float, default=None, help="calibrate the head: zero-mean class logits of this pooled deviation on standardised features")
+    ap.add_argument("--conv-stride", default="", help="strided convolutions: block:stride;block:stride (block: index into --blocks)")
+    ap.add_argument("--conv-dilation", default="", help="dilated convolutions: block:dilation;block:dilation")
+    ap.add_argument("--conv-valid", default="", help="convolutions with VALID padding: block;block")
     a = ap.parse_args()
     blocks = tuple(tuple(v if v in ("dw", "pw") else int(v) for v in b.split(",")) for b in a.blocks.split(";") if b)      # --blocks "": dense only
     dense = tuple(tuple(int(v) for v in d.split(",")) for d in a.dense.split(";") if d) or None
     blob = synth_model_blob(a.seed, ncep=a.ncep, win_size=a.win_size, low=a.low, high=a.high, blocks=blocks,
-                            n_labels=a.labels, num_filters=a.num_filters, logit_std=a.logit_std, dense=dense)
+                            n_labels=a.labels, num_filters=a.num_filters, logit_std=a.logit_std, dense=dense,
+                            conv_valid=tuple(int(v) for v in a.conv_valid.split(";") if v),
+                            conv_stride={int(v.split(":")[0]): int(v.split(":")[1]) for v in a.conv_stride.split(";") if v} or None,
+                            conv_dilation={int(v.split(":")[0]): int(v.split(":")[1]) for v in a.conv_dilation.split(";") if v} or None)
     with open(a.out, "wb") as f:
         f.write(blob)
     print(a.out, len(blob), "bytes")
