@@ -1,4 +1,5 @@
-// kws_nn_f32.hip -- kws_nn_f32_kernel: float32 graphs (the reference's float TFLite-Micro kernels replayed).
+// kws_nn_f32.hip -- kws_nn_f32_kernel<MAXT, TRUNK, SD> (kws_nn_f32_generic.h) and kws_dense_f32_kernel: float32 graphs (the reference's float
+// TFLite-Micro kernels replayed).
 #include <algorithm>
 
 #include "kws_device.h"
@@ -58,13 +59,16 @@ __device__ __forceinline__ int nnf_w_index(const KwsConvBlockF32 &k, int J, int 
 // where a block's (pooled) output goes: the next block's zero-padded input image, or the FULLY_CONNECTED input vector
 struct NnfDst { float *p; int row0, stride; };
 
-template <int TB, int OB, bool VEC4>
+// CONV_2D float: a lane owns TB consecutive time steps x OB consecutive output channels.  SD chooses the loop nest of the chains (stride 1: one contiguous
+// run per chain; strided / dilated: tap by tap); the item split in front of it and the epilogue behind it are the same.
+template <int TB, int OB, bool VEC4, bool SD>
 __device__ __forceinline__ void nnf_conv(const KwsConvBlockF32 &k, const float *__restrict__ x, const float *__restrict__ wt,
                                          float *__restrict__ y, const NnfDst &dst, int lane)
 {
     const int J = k.taps * k.in_c, ocp = nnf_ocp(k);
     const int n_ob = (k.out_c + OB - 1) / OB, n_tb = nnf_ntb(k);
     const bool direct = nnf_direct(k);
+    const int xs = (SD ? k.stride : 1) * k.in_c, ts = (SD ? k.dilation : 1) * k.in_c;      // floats between the rows of two consecutive outputs / taps
     for (int item = lane; item < n_tb * n_ob; item += 64) {
         const int tb = nnf_div(item, n_ob, k.inv_item20), ob = item - tb * n_ob;
         const int t0 = tb * TB, oc0 = ob * OB;
@@ -73,231 +77,144 @@ __device__ __forceinline__ void nnf_conv(const KwsConvBlockF32 &k, const float *
         for (int i = 0; i < TB; ++i)
 #pragma unroll
             for (int o = 0; o < OB; ++o) acc[i][o] = 0.0f;
-        const float *xp = x + t0 * k.in_c;          // rows are contiguous: x[(t+tap)*in_c + c] == x[t*in_c + (tap*in_c + c)]
-        const float *wp = wt + oc0;
-        // software pipeline: the TB activations and the OB-wide weight vector of step j+1 are in flight while step j's
-        // TB*OB multiply-adds issue (LDS latency would otherwise be exposed once per step at 2 waves per SIMD)
-        float wn[OB], xn[TB];
-        auto load_w = [&](int j, float (&w)[OB]) {
-            if constexpr (OB == 4) { const float4 v = *(const float4 *)(wp + j * ocp); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-            else if constexpr (OB == 2) { const float2 v = *(const float2 *)(wp + j * ocp); w[0] = v.x; w[1] = v.y; }
-            else w[0] = wp[j * ocp];
-        };
-        if constexpr (TB == 1) {
-            // one time step per lane (small blocks): a chain step is a single multiply-add per output channel, so issue
-            // slots decide.  The weights of such a block sit in LDS as [oc block][step][OB] (nnf_w_index), i.e. a lane's
-            // weight stream is contiguous: 8 steps' operands are 16 * OB / 4 + 4 reads at immediate offsets from two running
-            // pointers, full batches run without clamps or predicates, the J % 8 last steps one by one.  (No double
-            // buffering: the rotating copies cost more issue slots than the exposed round trip, which the SIMD's other
-            // wave -- usually inside a register-blocked block -- fills.)
-            typedef float f2v __attribute__((ext_vector_type(2)));
-            constexpr int U = 8, NV = (OB + 1) / 2;
-            const float *wq = wt + (size_t)ob * J * OB;
-            const int Jm = J & ~(U - 1);
-            f2v a2[NV];
-#pragma unroll
-            for (int v = 0; v < NV; ++v) a2[v] = (f2v){ 0.0f, 0.0f };
-            auto step1 = [&](const float *wj, float xs_) {        // products and sums rounded separately (-ffp-contract=off)
-                if constexpr (OB == 1) { const float prod = xs_ * wj[0]; a2[0].x += prod; }
+        if constexpr (SD) {
+            // strided / dilated: output t, tap j reads image row t * stride + j * dilation, so a chain's activations are no longer one
+            // contiguous run of taps * in_c floats: the steps run tap by tap, channel by channel inside a tap -- the reference's order, products and sums
+            // rounded separately -- and the zero rows of the padded image stand in for the skipped taps as ever.  Weights keep their LDS layouts.
+            const float *xp = x + t0 * xs;
+            // step j's OB weights: [j][oc] for register-blocked blocks, [oc block][j][OB] for one-time-step blocks (nnf_w_index)
+            const float *wp = TB == 1 ? wt + (size_t)ob * J * OB : wt + oc0;
+            const int wstep = TB == 1 ? OB : ocp;
+            auto load_w = [&](int j, float (&w)[OB]) {
+                if constexpr (OB == 4 && TB != 1) { const float4 v = *(const float4 *)(wp + j * wstep); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+                else if constexpr (OB == 2 && TB != 1) { const float2 v = *(const float2 *)(wp + j * wstep); w[0] = v.x; w[1] = v.y; }
                 else {
 #pragma unroll
-                    for (int v = 0; v < NV; ++v) {
-                        const f2v wv = { wj[2 * v], wj[2 * v + 1] };
-                        const f2v prod = wv * xs_;
-                        a2[v] += prod;
-                    }
+                    for (int o = 0; o < OB; ++o) w[o] = wp[j * wstep + o];
                 }
             };
-            for (int j0 = 0; j0 < Jm; j0 += U) {
-                float w[U * OB], xs_[U];
+            if (VEC4 && (k.in_c & 3) == 0) {
+                // rows are 16-byte aligned: one 16-byte read per time row brings the activations of 4 consecutive steps of a tap
+                for (int tap = 0; tap < k.taps; ++tap) {
+                    const float *xt = xp + tap * ts;
+                    for (int c = 0; c < k.in_c; c += 4) {
+                        float4 xv[TB];
+                        float w[4][OB];
 #pragma unroll
-                for (int i = 0; i < U * OB; ++i) w[i] = wq[j0 * OB + i];
+                        for (int i = 0; i < TB; ++i) xv[i] = *(const float4 *)(xt + i * xs + c);
 #pragma unroll
-                for (int u = 0; u < U; ++u) xs_[u] = xp[j0 + u];
+                        for (int u = 0; u < 4; ++u) load_w(tap * k.in_c + c + u, w[u]);
 #pragma unroll
-                for (int u = 0; u < U; ++u) step1(w + u * OB, xs_[u]);
-            }
-            for (int j = Jm; j < J; ++j) {
-                float w[OB];
+                        for (int u = 0; u < 4; ++u) {                  // chain order: channels c, c+1, c+2, c+3
 #pragma unroll
-                for (int o = 0; o < OB; ++o) w[o] = wq[j * OB + o];
-                step1(w, xp[j]);
-            }
+                            for (int i = 0; i < TB; ++i) {
+                                const float xs_ = u == 0 ? xv[i].x : u == 1 ? xv[i].y : u == 2 ? xv[i].z : xv[i].w;
 #pragma unroll
-            for (int o = 0; o < OB; ++o) acc[0][o] = (o & 1) ? a2[o >> 1].y : a2[o >> 1].x;
-        } else if (VEC4 && (k.in_c & 3) == 0) {
-            // channel counts that are multiples of 4 (rows 16-byte aligned): FOUR chain steps per batch -- one 16-byte read
-            // per time row brings the activations of 4 consecutive steps, the batch after next is in flight meanwhile
-            // (TB + 4 LDS instructions per 4 steps instead of 4 * (TB + 1)); needs the 256-register build of the kernel
-            float4 xq[TB];
-            float wq[4][OB];
-            auto load_batch = [&](int j) {
+                                for (int o = 0; o < OB; ++o) {
+                                    const float prod = xs_ * w[u][o];
+                                    acc[i][o] += prod;
+                                }
+                            }
+                        }
+                    }
+                }
+            } else {
+                for (int tap = 0; tap < k.taps; ++tap) {
+                    const float *xt = xp + tap * ts;
+                    for (int c = 0; c < k.in_c; ++c) {
+                        float w[OB], xv[TB];
+                        load_w(tap * k.in_c + c, w);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) load_w(j + u, wq[u]);
+                        for (int i = 0; i < TB; ++i) xv[i] = xt[i * xs + c];
 #pragma unroll
-                for (int i = 0; i < TB; ++i) xq[i] = *(const float4 *)(xp + i * k.in_c + j);
-            };
-            load_batch(0);
-            for (int j = 0; j < J; j += 4) {
-                float4 xv[TB];
-                float w[4][OB];
+                        for (int i = 0; i < TB; ++i) {
 #pragma unroll
-                for (int i = 0; i < TB; ++i) xv[i] = xq[i];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int o = 0; o < OB; ++o) w[u][o] = wq[u][o];
-                load_batch(min(j + 4, J - 4));
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {                      // chain order: steps j, j+1, j+2, j+3
-#pragma unroll
-                    for (int i = 0; i < TB; ++i) {
-                        const float xs_ = u == 0 ? xv[i].x : u == 1 ? xv[i].y : u == 2 ? xv[i].z : xv[i].w;
-#pragma unroll
-                        for (int o = 0; o < OB; ++o) {
-                            const float prod = xs_ * w[u][o];
-                            acc[i][o] += prod;
+                            for (int o = 0; o < OB; ++o) {
+                                const float prod = xv[i] * w[o];
+                                acc[i][o] += prod;
+                            }
                         }
                     }
                 }
             }
         } else {
-            load_w(0, wn);
+            const float *xp = x + t0 * k.in_c;          // rows are contiguous: x[(t+tap)*in_c + c] == x[t*in_c + (tap*in_c + c)]
+            const float *wp = wt + oc0;
+            // software pipeline: the TB activations and the OB-wide weight vector of step j+1 are in flight while step j's
+            // TB*OB multiply-adds issue (LDS latency would otherwise be exposed once per step at 2 waves per SIMD)
+            float wn[OB], xn[TB];
+            auto load_w = [&](int j, float (&w)[OB]) {
+                if constexpr (OB == 4) { const float4 v = *(const float4 *)(wp + j * ocp); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+                else if constexpr (OB == 2) { const float2 v = *(const float2 *)(wp + j * ocp); w[0] = v.x; w[1] = v.y; }
+                else w[0] = wp[j * ocp];
+            };
+            if constexpr (TB == 1) {
+                // one time step per lane (small blocks): a chain step is a single multiply-add per output channel, so issue
+                // slots decide.  The weights of such a block sit in LDS as [oc block][step][OB] (nnf_w_index), i.e. a lane's
+                // weight stream is contiguous: 8 steps' operands are 16 * OB / 4 + 4 reads at immediate offsets from two running
+                // pointers, full batches run without clamps or predicates, the J % 8 last steps one by one.  (No double
+                // buffering: the rotating copies cost more issue slots than the exposed round trip, which the SIMD's other
+                // wave -- usually inside a register-blocked block -- fills.)
+                typedef float f2v __attribute__((ext_vector_type(2)));
+                constexpr int U = 8, NV = (OB + 1) / 2;
+                const float *wq = wt + (size_t)ob * J * OB;
+                const int Jm = J & ~(U - 1);
+                f2v a2[NV];
 #pragma unroll
-            for (int i = 0; i < TB; ++i) xn[i] = xp[i * k.in_c];
-            for (int j = 0; j < J; ++j) {
-                float w[OB], xv[TB];
+                for (int v = 0; v < NV; ++v) a2[v] = (f2v){ 0.0f, 0.0f };
+                auto step1 = [&](const float *wj, float xs_) {        // products and sums rounded separately (-ffp-contract=off)
+                    if constexpr (OB == 1) { const float prod = xs_ * wj[0]; a2[0].x += prod; }
+                    else {
 #pragma unroll
-                for (int o = 0; o < OB; ++o) w[o] = wn[o];
-#pragma unroll
-                for (int i = 0; i < TB; ++i) xv[i] = xn[i];
-                const int jn = min(j + 1, J - 1);
-                load_w(jn, wn);
-#pragma unroll
-                for (int i = 0; i < TB; ++i) xn[i] = xp[i * k.in_c + jn];
-#pragma unroll
-                for (int i = 0; i < TB; ++i) {
-#pragma unroll
-                    for (int o = 0; o < OB; ++o) {
-                        const float prod = xv[i] * w[o];
-                        acc[i][o] += prod;
+                        for (int v = 0; v < NV; ++v) {
+                            const f2v wv = { wj[2 * v], wj[2 * v + 1] };
+                            const f2v prod = wv * xs_;
+                            a2[v] += prod;
+                        }
                     }
+                };
+                for (int j0 = 0; j0 < Jm; j0 += U) {
+                    float w[U * OB], xs_[U];
+#pragma unroll
+                    for (int i = 0; i < U * OB; ++i) w[i] = wq[j0 * OB + i];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) xs_[u] = xp[j0 + u];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) step1(w + u * OB, xs_[u]);
                 }
-            }
-        }
+                for (int j = Jm; j < J; ++j) {
+                    float w[OB];
 #pragma unroll
-        for (int o = 0; o < OB; ++o) {
-            const int oc = oc0 + o;
-            if (oc >= k.out_c) continue;
-            const float bv = k.bias[oc], av = k.addc[oc];
-            float mx = -FLT_MAX;
-#pragma unroll
-            for (int i = 0; i < TB; ++i) {
-                if (t0 + i < k.out_w) {
-                    float v = act_clamp(acc[i][o] + bv, k.conv_min, k.conv_max);
-                    if (k.has_add) v = act_clamp(v + av, k.add_min, k.add_max);
-                    if (k.fused_pool) mx = mx < v ? v : mx;             // MAX_POOL_2D: std::max(max, v), window order
-                    else if (direct) dst.p[(dst.row0 + t0 + i) * dst.stride + oc] = v;
-                    else y[(t0 + i) * k.out_c + oc] = v;
+                    for (int o = 0; o < OB; ++o) w[o] = wq[j * OB + o];
+                    step1(w, xp[j]);
                 }
-            }
-            if (k.fused_pool) dst.p[(dst.row0 + tb) * dst.stride + oc] = act_clamp(mx, k.pool_min, k.pool_max);
-        }
-    }
-}
-
-// DEPTHWISE_CONV_2D float (reference/depthwiseconv_float.h:25-97): the chain of output (t, oc) runs over the taps of input
-// channel oc / depth_mult only.  A lane owns TB consecutive time steps of one output channel.
-template <int TB>
-__device__ __forceinline__ void nnf_dwconv(const KwsConvBlockF32 &k, const float *__restrict__ x, const float *__restrict__ wt,
-                                           float *__restrict__ y, const NnfDst &dst, int lane)
-{
-    const int ocp = nnf_ocp(k), n_tb = nnf_ntb(k);
-    const bool direct = nnf_direct(k);
-    for (int item = lane; item < n_tb * k.out_c; item += 64) {
-        const int tb = nnf_div(item, k.out_c, k.inv_outc20), oc = item - tb * k.out_c;
-        const int t0 = tb * TB;
-        const float *xp = x + t0 * k.in_c + (k.depth_mult == 1 ? oc : oc / k.depth_mult);
-        float acc[TB];
 #pragma unroll
-        for (int i = 0; i < TB; ++i) acc[i] = 0.0f;
-        for (int tap = 0; tap < k.taps; ++tap) {
-            const float w = wt[tap * ocp + oc];
+                for (int o = 0; o < OB; ++o) acc[0][o] = (o & 1) ? a2[o >> 1].y : a2[o >> 1].x;
+            } else if (VEC4 && (k.in_c & 3) == 0) {
+                // channel counts that are multiples of 4 (rows 16-byte aligned): FOUR chain steps per batch -- one 16-byte read
+                // per time row brings the activations of 4 consecutive steps, the batch after next is in flight meanwhile
+                // (TB + 4 LDS instructions per 4 steps instead of 4 * (TB + 1)); needs the 256-register build of the kernel
+                float4 xq[TB];
+                float wq[4][OB];
+                auto load_batch = [&](int j) {
 #pragma unroll
-            for (int i = 0; i < TB; ++i) {
-                const float prod = xp[(i + tap) * k.in_c] * w;
-                acc[i] += prod;
-            }
-        }
-        const float bv = k.bias[oc], av = k.addc[oc];
-        float mx = -FLT_MAX;
+                    for (int u = 0; u < 4; ++u) load_w(j + u, wq[u]);
 #pragma unroll
-        for (int i = 0; i < TB; ++i) {
-            if (t0 + i < k.out_w) {
-                float v = act_clamp(acc[i] + bv, k.conv_min, k.conv_max);
-                if (k.has_add) v = act_clamp(v + av, k.add_min, k.add_max);
-                if (k.fused_pool) mx = mx < v ? v : mx;
-                else if (direct) dst.p[(dst.row0 + t0 + i) * dst.stride + oc] = v;
-                else y[(t0 + i) * k.out_c + oc] = v;
-            }
-        }
-        if (k.fused_pool) dst.p[(dst.row0 + tb) * dst.stride + oc] = act_clamp(mx, k.pool_min, k.pool_max);
-    }
-}
-
-template <int TB, bool VEC4>
-__device__ __forceinline__ void nnf_conv_ob(const KwsConvBlockF32 &k, const float *x, const float *wt, float *y, const NnfDst &dst, int lane)
-{
-    if (k.depthwise) nnf_dwconv<TB>(k, x, wt, y, dst, lane);
-    else if (k.ob == 4) nnf_conv<TB, 4, VEC4>(k, x, wt, y, dst, lane);
-    else if (k.ob == 2) nnf_conv<TB, 2, VEC4>(k, x, wt, y, dst, lane);
-    else nnf_conv<TB, 1, VEC4>(k, x, wt, y, dst, lane);
-}
-
-// ---- strided / dilated forms: output t, tap j reads image row t * stride + j * dilation, so a chain's activations are no longer one contiguous run
-//      of taps * in_c floats: the steps run tap by tap, channel by channel inside a tap -- the reference's order, products and sums rounded separately -- and
-//      the zero rows of the padded image stand in for the skipped taps exactly as in the stride-1 forms.  Weights keep their LDS layouts (nnf_w_index).
-template <int TB, int OB, bool VEC4>
-__device__ __forceinline__ void nnf_conv_sd(const KwsConvBlockF32 &k, const float *__restrict__ x, const float *__restrict__ wt,
-                                            float *__restrict__ y, const NnfDst &dst, int lane)
-{
-    const int J = k.taps * k.in_c, ocp = nnf_ocp(k);
-    const int n_ob = (k.out_c + OB - 1) / OB, n_tb = nnf_ntb(k);
-    const bool direct = nnf_direct(k);
-    const int xs = k.stride * k.in_c, ts = k.dilation * k.in_c;          // floats between the rows of two consecutive outputs / taps
-    for (int item = lane; item < n_tb * n_ob; item += 64) {
-        const int tb = nnf_div(item, n_ob, k.inv_item20), ob = item - tb * n_ob;
-        const int t0 = tb * TB, oc0 = ob * OB;
-        float acc[TB][OB];
-#pragma unroll
-        for (int i = 0; i < TB; ++i)
-#pragma unroll
-            for (int o = 0; o < OB; ++o) acc[i][o] = 0.0f;
-        const float *xp = x + t0 * xs;
-        // step j's OB weights: [j][oc] for register-blocked blocks, [oc block][j][OB] for one-time-step blocks (nnf_w_index)
-        const float *wp = TB == 1 ? wt + (size_t)ob * J * OB : wt + oc0;
-        const int wstep = TB == 1 ? OB : ocp;
-        auto load_w = [&](int j, float (&w)[OB]) {
-            if constexpr (OB == 4 && TB != 1) { const float4 v = *(const float4 *)(wp + j * wstep); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-            else if constexpr (OB == 2 && TB != 1) { const float2 v = *(const float2 *)(wp + j * wstep); w[0] = v.x; w[1] = v.y; }
-            else {
-#pragma unroll
-                for (int o = 0; o < OB; ++o) w[o] = wp[j * wstep + o];
-            }
-        };
-        if (VEC4 && (k.in_c & 3) == 0) {
-            // rows are 16-byte aligned: one 16-byte read per time row brings the activations of 4 consecutive steps of a tap
-            for (int tap = 0; tap < k.taps; ++tap) {
-                const float *xt = xp + tap * ts;
-                for (int c = 0; c < k.in_c; c += 4) {
+                    for (int i = 0; i < TB; ++i) xq[i] = *(const float4 *)(xp + i * k.in_c + j);
+                };
+                load_batch(0);
+                for (int j = 0; j < J; j += 4) {
                     float4 xv[TB];
                     float w[4][OB];
 #pragma unroll
-                    for (int i = 0; i < TB; ++i) xv[i] = *(const float4 *)(xt + i * xs + c);
+                    for (int i = 0; i < TB; ++i) xv[i] = xq[i];
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) load_w(tap * k.in_c + c + u, w[u]);
+                    for (int u = 0; u < 4; ++u)
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {                  // chain order: channels c, c+1, c+2, c+3
+                        for (int o = 0; o < OB; ++o) w[u][o] = wq[u][o];
+                    load_batch(min(j + 4, J - 4));
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {                      // chain order: steps j, j+1, j+2, j+3
 #pragma unroll
                         for (int i = 0; i < TB; ++i) {
                             const float xs_ = u == 0 ? xv[i].x : u == 1 ? xv[i].y : u == 2 ? xv[i].z : xv[i].w;
@@ -309,15 +226,20 @@ __device__ __forceinline__ void nnf_conv_sd(const KwsConvBlockF32 &k, const floa
                         }
                     }
                 }
-            }
-        } else {
-            for (int tap = 0; tap < k.taps; ++tap) {
-                const float *xt = xp + tap * ts;
-                for (int c = 0; c < k.in_c; ++c) {
-                    float w[OB], xv[TB];
-                    load_w(tap * k.in_c + c, w);
+            } else {
+                load_w(0, wn);
 #pragma unroll
-                    for (int i = 0; i < TB; ++i) xv[i] = xt[i * xs + c];
+                for (int i = 0; i < TB; ++i) xn[i] = xp[i * k.in_c];
+                for (int j = 0; j < J; ++j) {
+                    float w[OB], xv[TB];
+#pragma unroll
+                    for (int o = 0; o < OB; ++o) w[o] = wn[o];
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) xv[i] = xn[i];
+                    const int jn = min(j + 1, J - 1);
+                    load_w(jn, wn);
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) xn[i] = xp[i * k.in_c + jn];
 #pragma unroll
                     for (int i = 0; i < TB; ++i) {
 #pragma unroll
@@ -350,13 +272,16 @@ __device__ __forceinline__ void nnf_conv_sd(const KwsConvBlockF32 &k, const floa
     }
 }
 
-template <int TB>
-__device__ __forceinline__ void nnf_dwconv_sd(const KwsConvBlockF32 &k, const float *__restrict__ x, const float *__restrict__ wt,
-                                              float *__restrict__ y, const NnfDst &dst, int lane)
+// DEPTHWISE_CONV_2D float (reference/depthwiseconv_float.h:25-97): the chain of output (t, oc) runs over the taps of input
+// channel oc / depth_mult only.  A lane owns TB consecutive time steps of one output channel.  SD: the strided / dilated form (as in nnf_conv);
+// without it both row steps are in_c, as they always were.
+template <int TB, bool SD>
+__device__ __forceinline__ void nnf_dwconv(const KwsConvBlockF32 &k, const float *__restrict__ x, const float *__restrict__ wt,
+                                           float *__restrict__ y, const NnfDst &dst, int lane)
 {
     const int ocp = nnf_ocp(k), n_tb = nnf_ntb(k);
     const bool direct = nnf_direct(k);
-    const int xs = k.stride * k.in_c, ts = k.dilation * k.in_c;
+    const int xs = (SD ? k.stride : 1) * k.in_c, ts = (SD ? k.dilation : 1) * k.in_c;      // floats between the rows of two consecutive outputs / taps
     for (int item = lane; item < n_tb * k.out_c; item += 64) {
         const int tb = nnf_div(item, k.out_c, k.inv_outc20), oc = item - tb * k.out_c;
         const int t0 = tb * TB;
@@ -388,13 +313,14 @@ __device__ __forceinline__ void nnf_dwconv_sd(const KwsConvBlockF32 &k, const fl
     }
 }
 
-template <int TB, bool VEC4>
-__device__ __forceinline__ void nnf_conv_ob_sd(const KwsConvBlockF32 &k, const float *x, const float *wt, float *y, const NnfDst &dst, int lane)
+// a block's convolution at its blocking: depthwise or not, OB output channels per lane, stride-1 or strided form
+template <int TB, bool VEC4, bool SD>
+__device__ __forceinline__ void nnf_conv_ob(const KwsConvBlockF32 &k, const float *x, const float *wt, float *y, const NnfDst &dst, int lane)
 {
-    if (k.depthwise) nnf_dwconv_sd<TB>(k, x, wt, y, dst, lane);
-    else if (k.ob == 4) nnf_conv_sd<TB, 4, VEC4>(k, x, wt, y, dst, lane);
-    else if (k.ob == 2) nnf_conv_sd<TB, 2, VEC4>(k, x, wt, y, dst, lane);
-    else nnf_conv_sd<TB, 1, VEC4>(k, x, wt, y, dst, lane);
+    if (k.depthwise) nnf_dwconv<TB, SD>(k, x, wt, y, dst, lane);
+    else if (k.ob == 4) nnf_conv<TB, 4, VEC4, SD>(k, x, wt, y, dst, lane);
+    else if (k.ob == 2) nnf_conv<TB, 2, VEC4, SD>(k, x, wt, y, dst, lane);
+    else nnf_conv<TB, 1, VEC4, SD>(k, x, wt, y, dst, lane);
 }
 
 // LDS layout shared by host and device: weights of every block, then per wave the ping-pong input images A (even blocks) and
@@ -419,29 +345,7 @@ __host__ __device__ __forceinline__ NnfLayout nnf_layout(const KwsNnPlanF32 &N)
     return L;
 }
 
-#define KWS_NNF_TRUNK 0
-#define KWS_NNF_NAME kws_nn_f32_kernel
 #include "kws_nn_f32_generic.h"
-#undef KWS_NNF_TRUNK
-#undef KWS_NNF_NAME
-#define KWS_NNF_TRUNK 1
-#define KWS_NNF_NAME kws_nn_f32_trunk_kernel
-#include "kws_nn_f32_generic.h"
-#undef KWS_NNF_TRUNK
-#undef KWS_NNF_NAME
-// the strided / dilated forms: the same text, with every block's convolution through nnf_conv_ob_sd
-#define nnf_conv_ob nnf_conv_ob_sd
-#define KWS_NNF_TRUNK 0
-#define KWS_NNF_NAME kws_nn_f32_sd_kernel
-#include "kws_nn_f32_generic.h"
-#undef KWS_NNF_TRUNK
-#undef KWS_NNF_NAME
-#define KWS_NNF_TRUNK 1
-#define KWS_NNF_NAME kws_nn_f32_sd_trunk_kernel
-#include "kws_nn_f32_generic.h"
-#undef KWS_NNF_TRUNK
-#undef KWS_NNF_NAME
-#undef nnf_conv_ob
 
 // ---------------------------------------------------------------------------------------------------------
 //  kws_dense_f32_kernel: the dense stack of a float32 graph (1 .. 4 FULLY_CONNECTED, fully_connected.h:26-60, then SOFTMAX, softmax.h:31-63).
@@ -601,6 +505,26 @@ int kws_nn_f32_waves(const KwsNnPlanF32 &N)
     return 4;
 }
 
+// The form of kws_nn_f32_kernel that serves a graph, chosen ONCE per call: the pointer this returns is the one hipFuncSetAttribute opts in to large LDS
+// and the one nnf_launch launches.  trunk: the graph has a dense stack behind its conv blocks; sd: some block is strided or dilated;
+// at most 8 waves per workgroup take the 256-register build.
+static const void *nnf_kernel_for(bool trunk, bool sd, int n_waves)
+{
+    static const void *const tab[2][2][2] = {
+        { { (const void *)kws_nn_f32_kernel<1024, false, false>, (const void *)kws_nn_f32_kernel<512, false, false> },
+          { (const void *)kws_nn_f32_kernel<1024, false, true>, (const void *)kws_nn_f32_kernel<512, false, true> } },
+        { { (const void *)kws_nn_f32_kernel<1024, true, false>, (const void *)kws_nn_f32_kernel<512, true, false> },
+          { (const void *)kws_nn_f32_kernel<1024, true, true>, (const void *)kws_nn_f32_kernel<512, true, true> } } };
+    return tab[trunk][sd][n_waves <= 8];
+}
+// (every form has the one argument list; a form ignores the arguments that are not its own)
+static void nnf_launch(const void *fn, int grid, int n_waves, size_t smem, hipStream_t stream, const KwsNnPlanF32 *d_plan, const float *features, int n_clips,
+                       float *scores, float *tap_logits, float *handoff, int ci0, int ci1, const int *sel)
+{
+    void *args[] = { &d_plan, &features, &n_clips, &scores, &tap_logits, &handoff, &ci0, &ci1, &kws_dev_f32_prof, &sel };
+    (void)hipLaunchKernel(fn, dim3(grid), dim3(KWS_WAVE * n_waves), args, smem, stream);
+}
+
 // A graph with a dense stack: the conv blocks (if any) in the trunk form of kws_nn_f32_kernel, chunk by chunk of the hand-off buffer, each chunk followed
 // by kws_dense_f32_kernel over the same list entries.
 static int launch_dense_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, const float *features, int n_clips, float *scores, float *tap_logits,
@@ -623,9 +547,7 @@ static int launch_dense_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, c
     const int n_waves = kws_nn_f32_waves(N);
     const size_t smem = kws_nn_f32_smem_bytes(N, n_waves);
     const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / smem);
-    const bool sd = kws_nnf_strided(N) != 0;                                  // the strided form of the trunk
-    const void *fn = sd ? (n_waves <= 8 ? (const void *)kws_nn_f32_sd_trunk_kernel<512> : (const void *)kws_nn_f32_sd_trunk_kernel<1024>)
-                        : (n_waves <= 8 ? (const void *)kws_nn_f32_trunk_kernel<512> : (const void *)kws_nn_f32_trunk_kernel<1024>);
+    const void *fn = nnf_kernel_for(true, kws_nnf_strided(N) != 0, n_waves);
     if (smem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
@@ -635,18 +557,7 @@ static int launch_dense_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, c
         const int c1 = n_clips - c0 > chunk ? c0 + chunk : n_clips, n = c1 - c0;
         int grid = (n + n_waves - 1) / n_waves;
         if (grid > n_cu * per_cu) grid = n_cu * per_cu;
-        if (sd && n_waves <= 8)
-            hipLaunchKernelGGL(kws_nn_f32_sd_trunk_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
-                               kws_dev_f32_prof, sel);
-        else if (sd)
-            hipLaunchKernelGGL(kws_nn_f32_sd_trunk_kernel<1024>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
-                               kws_dev_f32_prof, sel);
-        else if (n_waves <= 8)
-            hipLaunchKernelGGL(kws_nn_f32_trunk_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
-                               kws_dev_f32_prof, sel);
-        else
-            hipLaunchKernelGGL(kws_nn_f32_trunk_kernel<1024>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips, ho, c0, c1,
-                               kws_dev_f32_prof, sel);
+        nnf_launch(fn, grid, n_waves, smem, stream, d_plan, features, n_clips, nullptr, nullptr, ho, c0, c1, sel);
         hipLaunchKernelGGL(kws_dense_f32_kernel, dim3(dense_grid(n)), dim3(KWS_WAVE * KWS_DENSEF_WAVES), dsmem, stream, D, (const float *)ho, 0, c0, c1, n_clips,
                            scores, tap_logits, sel);
         const int rc = (int)hipGetLastError();
@@ -666,24 +577,11 @@ int kws_launch_nn_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, const f
     const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / smem);
     int grid = (n_clips + n_waves - 1) / n_waves;
     if (grid > n_cu * per_cu * grid_mult) grid = n_cu * per_cu * grid_mult;
-    const bool sd = kws_nnf_strided(N) != 0;                                  // the strided form of the same kernel
-    const void *fn = sd ? (n_waves <= 8 ? (const void *)kws_nn_f32_sd_kernel<512> : (const void *)kws_nn_f32_sd_kernel<1024>)
-                        : (n_waves <= 8 ? (const void *)kws_nn_f32_kernel<512> : (const void *)kws_nn_f32_kernel<1024>);
+    const void *fn = nnf_kernel_for(false, kws_nnf_strided(N) != 0, n_waves);
     if (smem > 64 * 1024) {                    // opt in to more than the default 64 KB of dynamic LDS
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
     }
-    if (sd && n_waves <= 8)
-        hipLaunchKernelGGL(kws_nn_f32_sd_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips,
-                           scores, tap_logits, kws_dev_f32_prof, sel);
-    else if (sd)
-        hipLaunchKernelGGL(kws_nn_f32_sd_kernel<1024>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips,
-                           scores, tap_logits, kws_dev_f32_prof, sel);
-    else if (n_waves <= 8)
-        hipLaunchKernelGGL(kws_nn_f32_kernel<512>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips,
-                           scores, tap_logits, kws_dev_f32_prof, sel);
-    else
-        hipLaunchKernelGGL(kws_nn_f32_kernel<1024>, dim3(grid), dim3(KWS_WAVE * n_waves), smem, stream, d_plan, features, n_clips,
-                           scores, tap_logits, kws_dev_f32_prof, sel);
+    nnf_launch(fn, grid, n_waves, smem, stream, d_plan, features, n_clips, scores, tap_logits, nullptr, 0, 0, sel);
     return (int)hipGetLastError();
 }

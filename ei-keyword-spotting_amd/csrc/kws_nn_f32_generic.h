@@ -1,16 +1,14 @@
-// kws_nn_f32_generic.h -- the text of kws_nn_f32_kernel.  Part of kws_nn_f32.hip, which includes it TWICE: as kws_nn_f32_kernel (KWS_NNF_TRUNK 0: the
-// kernel as it always was, token for token, so that its code object does not move) and as kws_nn_f32_trunk_kernel (KWS_NNF_TRUNK 1: the form in front of
-// a dense stack -- no head: the last block's output of list entries ci0 .. ci1 - 1 goes to handoff [ci - ci0][fc_in] in HBM, where kws_dense_f32_kernel
-// reads it).  No include guard.
-template <int MAXT>     // threads per workgroup the build allows: 1024 (<= 128 VGPRs) or 512 (<= 256 VGPRs, vectorised conv steps)
-__global__ __launch_bounds__(MAXT) void KWS_NNF_NAME(const KwsNnPlanF32 *__restrict__ Np, const float *__restrict__ features,
-#if KWS_NNF_TRUNK
-                                                          int n_clips, float *__restrict__ handoff, int ci0, int ci1, long long *__restrict__ prof,
-#else
-                                                          int n_clips, float *__restrict__ scores,
-                                                          float *__restrict__ tap_logits, long long *__restrict__ prof,
-#endif
-                                                          const int *__restrict__ sel)
+// kws_nn_f32_generic.h -- kws_nn_f32_kernel<MAXT, TRUNK, SD>, the generic float32 network kernel.  Included once by kws_nn_f32.hip, after the helpers it
+// calls.  One template gives every form (include/kws/kws.h names them by label; the device symbols are the instantiations):
+//   TRUNK false  the whole graph: conv blocks, FULLY_CONNECTED, SOFTMAX -> scores (tap_logits: the optional logit tap).  handoff, ci0, ci1 are not read
+//   TRUNK true   the form in front of a dense stack -- no head: the last block's output of list entries ci0 .. ci1 - 1 goes to handoff [ci - ci0][fc_in]
+//                in HBM, where kws_dense_f32_kernel reads it.  scores and tap_logits are not read
+//   SD           the strided / dilated forms: every block's convolution goes through nnf_conv_ob_sd
+// The argument list is shared; what `if constexpr` leaves out of an instantiation is not in its code.
+template <int MAXT, bool TRUNK, bool SD>     // MAXT: threads per workgroup the build allows: 1024 (<= 128 VGPRs) or 512 (<= 256 VGPRs, vectorised conv steps)
+__global__ __launch_bounds__(MAXT) void kws_nn_f32_kernel(const KwsNnPlanF32 *__restrict__ Np, const float *__restrict__ features, int n_clips,
+                                                          float *__restrict__ scores, float *__restrict__ tap_logits, float *__restrict__ handoff, int ci0,
+                                                          int ci1, long long *__restrict__ prof, const int *__restrict__ sel)
 {
     // the plan is read from memory (scalar loads, any block index); by value in the kernel arguments the compiler copies it to
     // scratch as soon as a block is indexed dynamically
@@ -23,13 +21,9 @@ __global__ __launch_bounds__(MAXT) void KWS_NNF_NAME(const KwsNnPlanF32 *__restr
     auto mark = [&](int i) { if (profiling) { const long long now = clock64(); ph[i] += now - tlast; tlast = now; } };
     // a workgroup none of whose waves has a clip (the empty re-run list of a KWS_MODE_FAST call, a short list) leaves before
     // the weights are staged: 16.5 us -> launch overhead for the empty list
-#if KWS_NNF_TRUNK
-    const int n_sel = min(sel_count(sel, n_clips), ci1);
-    if (ci0 + (int)blockIdx.x * n_waves >= n_sel) return;
-#else
-    const int n_sel = sel_count(sel, n_clips);
-    if ((int)blockIdx.x * n_waves >= n_sel) return;
-#endif
+    const int first = TRUNK ? ci0 : 0;               // the list entry of workgroup 0, wave 0
+    const int n_sel = TRUNK ? min(sel_count(sel, n_clips), ci1) : sel_count(sel, n_clips);
+    if (first + (int)blockIdx.x * n_waves >= n_sel) return;
     float *sp = (float *)smem_raw;
     int s_w_off[KWS_MAX_BLOCKS];     // float offsets into the LDS block: pointers kept in an array lose their address space (flat loads)
     for (int b = 0; b < N.n_blocks; ++b) {
@@ -44,10 +38,10 @@ __global__ __launch_bounds__(MAXT) void KWS_NNF_NAME(const KwsNnPlanF32 *__restr
     }
     const NnfLayout L = nnf_layout(N);
     const float *s_fcw = sp, *s_fcb = sp + N.fc_out * N.fc_in;
-#if !KWS_NNF_TRUNK
-    for (int i = threadIdx.x; i < N.fc_out * N.fc_in; i += blockDim.x) sp[i] = N.fc_w[i];
-    for (int i = threadIdx.x; i < N.fc_out; i += blockDim.x) sp[N.fc_out * N.fc_in + i] = N.fc_bias[i];
-#endif
+    if constexpr (!TRUNK) {
+        for (int i = threadIdx.x; i < N.fc_out * N.fc_in; i += blockDim.x) sp[i] = N.fc_w[i];
+        for (int i = threadIdx.x; i < N.fc_out; i += blockDim.x) sp[N.fc_out * N.fc_in + i] = N.fc_bias[i];
+    }
     sp += L.fc_floats;
     float *A = sp + wave * (L.a_floats + L.b_floats + L.y_floats + L.vec_floats);
     float *B = A + L.a_floats;
@@ -66,11 +60,7 @@ __global__ __launch_bounds__(MAXT) void KWS_NNF_NAME(const KwsNnPlanF32 *__restr
         const int lo = k.pad_left * k.in_c, hi = lo + k.in_w * k.in_c, tot = nnf_rows(k) * k.in_c;
         return ((lo | hi | N.n_features) & 3) == 0 && ((tot + 3) >> 2) <= 64 * NNF_PF && N.n_blocks > 1;
     }();
-#if KWS_NNF_TRUNK
-    for (int ci = ci0 + blockIdx.x * n_waves + wave; ci < n_sel; ci += gridDim.x * n_waves) {
-#else
-    for (int ci = blockIdx.x * n_waves + wave; ci < n_sel; ci += gridDim.x * n_waves) {
-#endif
+    for (int ci = first + blockIdx.x * n_waves + wave; ci < n_sel; ci += gridDim.x * n_waves) {
         const int clip = sel_clip(sel, ci);
         {
             const KwsConvBlockF32 &k = N.blk[0];
@@ -140,12 +130,13 @@ __global__ __launch_bounds__(MAXT) void KWS_NNF_NAME(const KwsNnPlanF32 *__restr
                 for (int i = lane; i < tot; i += 64)
                     if (i < lo || i >= hi) dst.p[i] = 0.0f;
             }
+            const float *wt = (const float *)smem_raw + s_w_off[b];
             switch (k.tb) {
-            case 8: nnf_conv_ob<8, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            case 7: nnf_conv_ob<7, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            case 4: nnf_conv_ob<4, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            case 2: nnf_conv_ob<2, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
-            default: nnf_conv_ob<1, (MAXT <= 512)>(k, cur, (const float *)smem_raw + s_w_off[b], Y, dst, lane); break;
+            case 8: nnf_conv_ob<8, (MAXT <= 512), SD>(k, cur, wt, Y, dst, lane); break;
+            case 7: nnf_conv_ob<7, (MAXT <= 512), SD>(k, cur, wt, Y, dst, lane); break;
+            case 4: nnf_conv_ob<4, (MAXT <= 512), SD>(k, cur, wt, Y, dst, lane); break;
+            case 2: nnf_conv_ob<2, (MAXT <= 512), SD>(k, cur, wt, Y, dst, lane); break;
+            default: nnf_conv_ob<1, (MAXT <= 512), SD>(k, cur, wt, Y, dst, lane); break;
             }
             WAVE_SYNC();
             if (b == 0 && MAXT <= 512 && pf_ok) {
@@ -180,57 +171,53 @@ __global__ __launch_bounds__(MAXT) void KWS_NNF_NAME(const KwsNnPlanF32 *__restr
             }
             mark(1 + b);
         }
-#if KWS_NNF_TRUNK
-        {
+        if constexpr (TRUNK) {
             float *dst = handoff + (size_t)(ci - ci0) * N.fc_in;
             for (int i = lane; i < N.fc_in; i += 64) dst[i] = vec[i];
             WAVE_SYNC();
-            (void)s_fcw; (void)s_fcb;
-        }
-#else
-        // FULLY_CONNECTED (fully_connected.h:26-60) + SOFTMAX (softmax.h:31-63)
-        float *lg = vec + (L.vec_floats - 64), *ex = vec;          // ex overwrites the FC input once every lane is done with it
-        const int fc_in = N.fc_in, fc_out = N.fc_out;
-        const float beta = N.beta;
-        if (lane < fc_out) {
-            const float *fw = s_fcw + lane * fc_in;
-            float total = 0.0f;
-            int d = 0;
-            for (; d + 4 <= fc_in; d += 4) {                  // four weights in flight per round trip; the chain stays in order
-                const float w0 = fw[d], w1 = fw[d + 1], w2 = fw[d + 2], w3 = fw[d + 3];
-                const float x0 = vec[d], x1 = vec[d + 1], x2 = vec[d + 2], x3 = vec[d + 3];
-                const float p0 = x0 * w0, p1 = x1 * w1, p2 = x2 * w2, p3 = x3 * w3;
-                total += p0; total += p1; total += p2; total += p3;
+        } else {
+            // FULLY_CONNECTED (fully_connected.h:26-60) + SOFTMAX (softmax.h:31-63)
+            float *lg = vec + (L.vec_floats - 64), *ex = vec;          // ex overwrites the FC input once every lane is done with it
+            const int fc_in = N.fc_in, fc_out = N.fc_out;
+            const float beta = N.beta;
+            if (lane < fc_out) {
+                const float *fw = s_fcw + lane * fc_in;
+                float total = 0.0f;
+                int d = 0;
+                for (; d + 4 <= fc_in; d += 4) {                  // four weights in flight per round trip; the chain stays in order
+                    const float w0 = fw[d], w1 = fw[d + 1], w2 = fw[d + 2], w3 = fw[d + 3];
+                    const float x0 = vec[d], x1 = vec[d + 1], x2 = vec[d + 2], x3 = vec[d + 3];
+                    const float p0 = x0 * w0, p1 = x1 * w1, p2 = x2 * w2, p3 = x3 * w3;
+                    total += p0; total += p1; total += p2; total += p3;
+                }
+                for (; d < fc_in; ++d) {
+                    const float prod = vec[d] * fw[d];
+                    total += prod;
+                }
+                const float lgt = act_clamp(total + s_fcb[lane], N.fc_min, N.fc_max);
+                lg[lane] = lgt;
+                if (tap_logits) tap_logits[(size_t)clip * fc_out + lane] = lgt;
             }
-            for (; d < fc_in; ++d) {
-                const float prod = vec[d] * fw[d];
-                total += prod;
+            WAVE_SYNC();
+            // softmax.h:31-63: max, then sum += exp((x - max) * beta) in class order, then exp(...) / sum.  Each lane evaluates
+            // its own class's exponential once; the sum adds the same values in the same order
+            float e_own = 0.0f;
+            if (lane < fc_out) {
+                float mx = -FLT_MAX;
+                for (int c = 0; c < fc_out; ++c) mx = mx < lg[c] ? lg[c] : mx;
+                e_own = expf((lg[lane] - mx) * beta);
+                ex[lane] = e_own;
             }
-            const float lgt = act_clamp(total + s_fcb[lane], N.fc_min, N.fc_max);
-            lg[lane] = lgt;
-            if (tap_logits) tap_logits[(size_t)clip * fc_out + lane] = lgt;
+            WAVE_SYNC();
+            if (lane < fc_out) {
+                float sum = 0.0f;
+                for (int c = 0; c < fc_out; ++c) sum += ex[c];
+                scores[(size_t)clip * fc_out + lane] = e_own / sum;
+            }
+            WAVE_SYNC();
         }
-        WAVE_SYNC();
-        // softmax.h:31-63: max, then sum += exp((x - max) * beta) in class order, then exp(...) / sum.  Each lane evaluates
-        // its own class's exponential once; the sum adds the same values in the same order
-        float e_own = 0.0f;
-        if (lane < fc_out) {
-            float mx = -FLT_MAX;
-            for (int c = 0; c < fc_out; ++c) mx = mx < lg[c] ? lg[c] : mx;
-            e_own = expf((lg[lane] - mx) * beta);
-            ex[lane] = e_own;
-        }
-        WAVE_SYNC();
-        if (lane < fc_out) {
-            float sum = 0.0f;
-            for (int c = 0; c < fc_out; ++c) sum += ex[c];
-            scores[(size_t)clip * fc_out + lane] = e_own / sum;
-        }
-        WAVE_SYNC();
-#endif
         mark(1 + KWS_MAX_BLOCKS);
     }
     if (profiling && lane == 0)
         for (int i = 0; i < KWS_MAX_BLOCKS + 2; ++i) prof[i] = ph[i];
 }
-

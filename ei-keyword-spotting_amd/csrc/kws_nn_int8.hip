@@ -1,42 +1,13 @@
-// kws_nn_int8.hip -- the int8 network: kws_nn_kernel (generic: any chain of conv blocks; un-pooled CONV_2D on the matrix
-// cores, depthwise in registers, the rest on v_dot4), kws_nn_mfma_kernel (the two-block shape entirely on the matrix cores) and
-// kws_cmvn_nn_kernel (cmvnw + quantise [+ network] for the stage API / continuous mode).  Replaces the EON-compiled
-// TFLite-Micro graph (MODEL/tflite-model/trained_model_compiled.cpp:312-328).
+// kws_nn_int8.hip -- the int8 network: kws_nn_kernel<MAXW, TRUNK, SD> (generic, kws_nn_int8_generic.h: any chain of conv blocks, with its head or as the
+// trunk of a dense stack, stride 1 or strided / dilated; un-pooled CONV_2D on the matrix cores, depthwise in registers, the rest on v_dot4),
+// kws_nn_mfma_kernel (the two-block shape entirely on the matrix cores) and kws_cmvn_nn_kernel (cmvnw + quantise [+ network] for the stage API /
+// continuous mode).  Replaces the EON-compiled TFLite-Micro graph (MODEL/tflite-model/trained_model_compiled.cpp:312-328).
 #include "kws_device.h"
 #include <cstdio>
 #include <cstdlib>
 
 #include "kws_nn_int8_dev.h"
-
-
-#define KWS_NN_SD 0
-#define KWS_NN_TRUNK 0
-#define KWS_NN_GENERIC_NAME kws_nn_kernel
 #include "kws_nn_int8_generic.h"
-#undef KWS_NN_TRUNK
-#undef KWS_NN_GENERIC_NAME
-#define KWS_NN_TRUNK 1
-#define KWS_NN_GENERIC_NAME kws_nn_trunk_kernel
-#include "kws_nn_int8_generic.h"
-#undef KWS_NN_TRUNK
-#undef KWS_NN_GENERIC_NAME
-#undef KWS_NN_SD
-
-// the strided / dilated forms: the same text with KWS_NN_SD 1; their image rows are nn_rows_sd's
-#define nn_rows nn_rows_sd
-#define KWS_NN_SD 1
-#define KWS_NN_TRUNK 0
-#define KWS_NN_GENERIC_NAME kws_nn_sd_kernel
-#include "kws_nn_int8_generic.h"
-#undef KWS_NN_TRUNK
-#undef KWS_NN_GENERIC_NAME
-#define KWS_NN_TRUNK 1
-#define KWS_NN_GENERIC_NAME kws_nn_sd_trunk_kernel
-#include "kws_nn_int8_generic.h"
-#undef KWS_NN_TRUNK
-#undef KWS_NN_GENERIC_NAME
-#undef KWS_NN_SD
-#undef nn_rows
 
 #include "kws_dense_i8.h"
 
@@ -195,6 +166,26 @@ size_t kws_nn_smem_bytes(const KwsNnPlan &N, int n_waves)
     return s + (size_t)n_waves * (((act[0] + 15) & ~15) + ((act[1] + 15) & ~15) + nn_fcx_bytes(N) + 64 * 4);
 }
 
+// The form of kws_nn_kernel that serves a graph, chosen ONCE per call: the pointer this returns is the one hipFuncSetAttribute opts in to large LDS and
+// the one nn_launch launches.  trunk: the graph has a dense stack behind its conv blocks; sd: some block is strided or dilated; at most
+// twelve waves per workgroup take the 168-register build.
+static const void *nn_kernel_for(bool trunk, bool sd, int nw)
+{
+    static const void *const tab[2][2][2] = {
+        { { (const void *)kws_nn_kernel<16, false, false>, (const void *)kws_nn_kernel<12, false, false> },
+          { (const void *)kws_nn_kernel<16, false, true>, (const void *)kws_nn_kernel<12, false, true> } },
+        { { (const void *)kws_nn_kernel<16, true, false>, (const void *)kws_nn_kernel<12, true, false> },
+          { (const void *)kws_nn_kernel<16, true, true>, (const void *)kws_nn_kernel<12, true, true> } } };
+    return tab[trunk][sd][nw <= 12];
+}
+// (every form has the one argument list; a form ignores the arguments that are not its own)
+static void nn_launch(const void *fn, int grid, int nw, size_t smem, hipStream_t stream, const KwsNnPlan &N, const int8_t *q_in, int n_clips,
+                      float *scores, int8_t *handoff, int ci0, int ci1, NnTaps taps)
+{
+    void *args[] = { const_cast<KwsNnPlan *>(&N), &q_in, &n_clips, &scores, &handoff, &ci0, &ci1, &taps };
+    (void)hipLaunchKernel(fn, dim3(grid), dim3(KWS_WAVE * nw), args, smem, stream);
+}
+
 // A graph with a dense stack: the conv blocks (if any) in the trunk form of the generic kernel, chunk by chunk of the hand-off buffer, each chunk followed
 // by kws_dense_i8_kernel over the same list entries.
 static int launch_dense_i8(const KwsNnPlan &N, const int8_t *q_in, int n_clips, float *scores, const NnTaps &taps, int grid_cap, hipStream_t stream)
@@ -215,9 +206,7 @@ static int launch_dense_i8(const KwsNnPlan &N, const int8_t *q_in, int n_clips, 
     int nw = KWS_NN_WAVES_MAX;
     while (nw > KWS_NN_WAVES && kws_nn_smem_bytes(N, nw) > 158 * 1024) --nw;
     const size_t tsmem = kws_nn_smem_bytes(N, nw);
-    const bool sd = kws_nn_strided(N) != 0;                                   // the strided form of the trunk
-    const void *fn = sd ? (nw <= 12 ? (const void *)kws_nn_sd_trunk_kernel<12> : (const void *)kws_nn_sd_trunk_kernel<16>)
-                        : (nw <= 12 ? (const void *)kws_nn_trunk_kernel<12> : (const void *)kws_nn_trunk_kernel<16>);
+    const void *fn = nn_kernel_for(true, kws_nn_strided(N) != 0, nw);
     if (tsmem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tsmem);
         if (e != hipSuccess) return (int)e;
@@ -227,10 +216,7 @@ static int launch_dense_i8(const KwsNnPlan &N, const int8_t *q_in, int n_clips, 
         const int c1 = n_clips - c0 > chunk ? c0 + chunk : n_clips, n = c1 - c0;
         int grid = (n + nw - 1) / nw;
         if (grid > grid_cap / 4) grid = grid_cap / 4;                         // grid_cap = 4 workgroups per CU; one persistent workgroup per CU
-        if (sd && nw <= 12) hipLaunchKernelGGL(kws_nn_sd_trunk_kernel<12>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
-        else if (sd) hipLaunchKernelGGL(kws_nn_sd_trunk_kernel<16>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
-        else if (nw <= 12) hipLaunchKernelGGL(kws_nn_trunk_kernel<12>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
-        else hipLaunchKernelGGL(kws_nn_trunk_kernel<16>, dim3(grid), dim3(KWS_WAVE * nw), tsmem, stream, N, q_in, n_clips, ho, c0, c1, taps);
+        nn_launch(fn, grid, nw, tsmem, stream, N, q_in, n_clips, nullptr, ho, c0, c1, taps);
         hipLaunchKernelGGL(kws_dense_i8_kernel, dim3(dense_grid(n)), dim3(KWS_WAVE * KWS_DENSE_WAVES), smem, stream, D, (const int8_t *)ho, 0, c0, c1, n_clips, scores, taps);
         const int rc = (int)hipGetLastError();
         if (rc) return rc;
@@ -262,29 +248,12 @@ int kws_launch_nn(const KwsNnPlan &N, const int8_t *q_in, int n_clips, float *sc
     const size_t smem = kws_nn_smem_bytes(N, nw);
     grid = (n_clips + nw - 1) / nw;
     if (grid > (grid_cap / 4) * per_cu) grid = (grid_cap / 4) * per_cu;          // grid_cap = 4 workgroups per CU
-    if (kws_nn_strided(N)) {                       // a strided or dilated block somewhere in the graph -- the strided form of the same kernel
-        const void *fn = nw <= 12 ? (const void *)kws_nn_sd_kernel<12> : (const void *)kws_nn_sd_kernel<16>;
-        if (smem > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        if (nw <= 12) hipLaunchKernelGGL(kws_nn_sd_kernel<12>, dim3(grid), dim3(KWS_WAVE * nw), smem, stream, N, q_in, n_clips, scores, taps);
-        else hipLaunchKernelGGL(kws_nn_sd_kernel<16>, dim3(grid), dim3(KWS_WAVE * nw), smem, stream, N, q_in, n_clips, scores, taps);
-        return (int)hipGetLastError();
-    }
-    if (nw <= 12) {
-        if (smem > 64 * 1024) {                    // wide models: opt in to more than the default 64 KB of dynamic LDS
-            hipError_t e = hipFuncSetAttribute((const void *)kws_nn_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(kws_nn_kernel<12>, dim3(grid), dim3(KWS_WAVE * nw), smem, stream, N, q_in, n_clips, scores, taps);
-        return (int)hipGetLastError();
-    }
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kws_nn_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    const void *fn = nn_kernel_for(false, kws_nn_strided(N) != 0, nw);
+    if (smem > 64 * 1024) {                    // wide models: opt in to more than the default 64 KB of dynamic LDS
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(kws_nn_kernel<16>, dim3(grid), dim3(KWS_WAVE * nw), smem, stream, N, q_in, n_clips, scores, taps);
+    nn_launch(fn, grid, nw, smem, stream, N, q_in, n_clips, scores, nullptr, 0, 0, taps);
     return (int)hipGetLastError();
 }
 

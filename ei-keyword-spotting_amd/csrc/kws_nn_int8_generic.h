@@ -1,27 +1,26 @@
-// kws_nn_int8_generic.h -- the text of kws_nn_kernel, the generic int8 network kernel.  Part of kws_nn_int8.hip, which includes it TWICE: as kws_nn_kernel
-// (KWS_NN_TRUNK 0: the kernel as it always was, token for token, so that its code object does not move) and as kws_nn_trunk_kernel (KWS_NN_TRUNK 1: the
-// form in front of a dense stack -- no head: the last block's output of list entries ci0 .. ci1 - 1 goes to handoff [ci - ci0][fc_in] in HBM, where
-// kws_dense_i8_kernel reads it).  KWS_NN_SD 1 gives the strided / dilated forms of both (kws_nn_sd_kernel, kws_nn_sd_trunk_kernel): output t, tap j
-// of a block reads image row t * stride + j * dilation, image rows are counted by nn_rows_sd (the including file maps nn_rows to it), and a strided or dilated
-// depthwise block takes the one-output-per-lane path.  With KWS_NN_SD 0 the preprocessor leaves the text the stride-1 kernels always had.  No include guard.
+// kws_nn_int8_generic.h -- kws_nn_kernel<MAXW, TRUNK, SD>, the generic int8 network kernel.  Included once by kws_nn_int8.hip.  One template gives every
+// form (include/kws/kws.h names them by label; the device symbols are the instantiations):
+//   TRUNK false  the whole graph: conv blocks and head -> scores.  handoff, ci0, ci1 are not read
+//   TRUNK true   the form in front of a dense stack -- no head: the last block's output of list entries ci0 .. ci1 - 1 goes to handoff [ci - ci0][fc_in]
+//                in HBM, where kws_dense_i8_kernel reads it.  scores is not read
+//   SD           the strided / dilated forms: output t, tap j of a block reads image row t * stride + j * dilation, image rows are counted
+//                by nn_rows_sd, and a strided or dilated depthwise block takes the one-output-per-lane path.  Without SD the steps are the constant 1
+//                and the rows nn_rows's: the stride-1 forms hold no test of k.stride or k.dilation.
+// The argument list is shared; what `if constexpr` leaves out of an instantiation is not in its code.
 // MAXW: waves per workgroup the build allows.  16 (four per SIMD) caps the kernel at 128 VGPRs, which it overruns by 20 (176 B of
 // scratch per lane); 12 (three per SIMD) gives it 168 and no scratch -- the launcher picks by measurement (below).
-template <int MAXW>
-__global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan N, const int8_t *__restrict__ q_in, int n_clips,
-#if KWS_NN_TRUNK
-                                                                         int8_t *__restrict__ handoff, int ci0, int ci1, NnTaps taps)
-#else
-                                                                         float *__restrict__ scores, NnTaps taps)
-#endif
+template <int MAXW, bool TRUNK, bool SD>
+__global__ __launch_bounds__(KWS_WAVE * MAXW) void kws_nn_kernel(KwsNnPlan N, const int8_t *__restrict__ q_in, int n_clips, float *__restrict__ scores,
+                                                                 int8_t *__restrict__ handoff, int ci0, int ci1, NnTaps taps)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    auto rows_of = [](const KwsConvBlock &k) { if constexpr (SD) return nn_rows_sd(k); else return nn_rows(k); };      // rows of a block's input image
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = blockDim.x >> 6;
 
     // ---- shared: weights, ADD tables and requantisation constants of every block, in block order ---------------
     const int fcw_bytes = nn_head_fcw_bytes(N), fcx_bytes = nn_fcx_bytes(N);
-#if !KWS_NN_TRUNK
-    const NnHeadTab head = nn_head_stage(N, smem_raw, fcw_bytes);
-#endif
+    NnHeadTab head = { nullptr, nullptr, nullptr, nullptr };
+    if constexpr (!TRUNK) head = nn_head_stage(N, smem_raw, fcw_bytes);
     unsigned char *const blocks_base = smem_raw + fcw_bytes + ((KWS_HEAD_REST + 15) & ~15);
     unsigned char *sp = blocks_base;
     int act_b[2] = { 0, 0 };                           // block b reads buffer b & 1: each is sized for its own blocks
@@ -35,7 +34,7 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
         sp += lbytes;
         for (int i = threadIdx.x; i < k.out_c; i += blockDim.x) ((int4 *)sp)[i] = make_int4(k.bias_eff[i], k.mult[i], k.shift[i], 0);
         sp += k.out_c * 16;
-        const int ab = nn_rows(k) * k.in_cpad;
+        const int ab = rows_of(k) * k.in_cpad;
         act_b[b & 1] = max(act_b[b & 1], ab);
     }
     act_b[0] = (act_b[0] + 15) & ~15; act_b[1] = (act_b[1] + 15) & ~15;
@@ -53,18 +52,13 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
     const bool profiling = taps.prof != nullptr && blockIdx.x == 0 && wave == 0;
     long long ph[KWS_MAX_BLOCKS + 2] = { 0 }, tlast = profiling ? clock64() : 0;
     auto mark = [&](int i) { if (profiling) { const long long now = clock64(); ph[i] += now - tlast; tlast = now; } };
-#if KWS_NN_TRUNK
-    const int n_sel = min(sel_count(taps.sel, n_clips), ci1);
-    for (int ci = ci0 + blockIdx.x * n_waves + wave; ci < n_sel; ci += gridDim.x * n_waves) {
-#else
-    const int n_sel = sel_count(taps.sel, n_clips);
-    for (int ci = blockIdx.x * n_waves + wave; ci < n_sel; ci += gridDim.x * n_waves) {
-#endif
+    const int n_sel = TRUNK ? min(sel_count(taps.sel, n_clips), ci1) : sel_count(taps.sel, n_clips);
+    for (int ci = (TRUNK ? ci0 : 0) + blockIdx.x * n_waves + wave; ci < n_sel; ci += gridDim.x * n_waves) {
         const int clip = sel_clip(taps.sel, ci);
         // ---- stage the int8 input as [pad_left + t][in_cpad], padding = zero point ((x + offset) == 0) -------
         {
             const KwsConvBlock &k = N.blk[0];
-            const int rows = nn_rows(k);
+            const int rows = rows_of(k);
             const int zp4 = (int)((unsigned)(k.in_zp & 0xff) * 0x01010101u);
             for (int i = lane * 16; i < rows * k.in_cpad; i += 64 * 16) *(int4 *)(actA + i) = make_int4(zp4, zp4, zp4, zp4);
             WAVE_SYNC();
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
             const int4 *rqt = (const int4 *)bp;
             bp += k.out_c * 16;
             const bool last = (b + 1 == N.n_blocks);
-            const int nrows = last ? 0 : nn_rows(N.blk[b + 1]);
+            const int nrows = last ? 0 : rows_of(N.blk[b + 1]);
             const int ncp = last ? k.out_c : N.blk[b + 1].in_cpad;
             const int npl = last ? 0 : N.blk[b + 1].pad_left;
             if (!last) {
@@ -119,14 +113,10 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
                 dbase[pw * dstride + oc] = o;
                 if (tp) tp[pw * out_c + oc] = o;
             };
-#if KWS_NN_SD
-            const int cs = k.stride, cd = k.dilation;
+            const int cs = SD ? k.stride : 1, cd = SD ? k.dilation : 1;      // image rows between two consecutive outputs / taps
             // the 4-channel depthwise path's row registers are sized at compile time for contiguous rows: a strided or dilated depthwise block takes the
             // one-output-per-lane path below (a register window of (tb - 1) * stride + (taps - 1) * dilation + 1 rows has no bound the compiler could unroll to)
             if (k.depthwise && k.depth_mult == 1 && (out_c & 3) == 0 && k.taps <= 8 && cs == 1 && cd == 1) {
-#else
-            if (k.depthwise && k.depth_mult == 1 && (out_c & 3) == 0 && k.taps <= 8) {
-#endif
                 // integer_ops/depthwise_conv.h:64-103, one input channel per output.  A lane owns 4 consecutive channels of
                 // one pooling window (or of 8 time steps when the block is not pooled): the tb + taps - 1 activation rows
                 // it needs are read ONCE as 32-bit words (4 channels each), the 4 x taps weights as 8 words, everything
@@ -214,7 +204,6 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
 #pragma unroll
                     for (int i = 0; i < KWS_POOL_MAX; ++i) acc[i] = 0;
                     const int8_t *wrow = wb + oc * tp4;
-#if KWS_NN_SD
                     const int8_t *xcol = cur + t0 * cs * k.in_cpad + oc / k.depth_mult;
                     for (int tap = 0; tap < k.taps; ++tap) {
                         const int wv = wrow[tap];
@@ -222,15 +211,6 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
                         for (int i = 0; i < KWS_POOL_MAX; ++i)
                             if (i < k.pool) acc[i] += wv * (int)xcol[(i * cs + tap * cd) * k.in_cpad];
                     }
-#else
-                    const int8_t *xcol = cur + t0 * k.in_cpad + oc / k.depth_mult;
-                    for (int tap = 0; tap < k.taps; ++tap) {
-                        const int wv = wrow[tap];
-#pragma unroll
-                        for (int i = 0; i < KWS_POOL_MAX; ++i)
-                            if (i < k.pool) acc[i] += wv * (int)xcol[(i + tap) * k.in_cpad];
-                    }
-#endif
                     int m = (int)0x80000000;
 #pragma unroll
                     for (int i = 0; i < KWS_POOL_MAX; ++i)
@@ -306,23 +286,15 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
                     const int8_t *w0 = wb + (size_t)oc0 * k.taps * k.in_cpad;
                     const int8_t *w1 = w0 + (ob == 2 ? k.taps * k.in_cpad : 0);
                     for (int tap = 0; tap < k.taps; ++tap) {
-#if KWS_NN_SD
                         const int8_t *xrow = cur + (t0 * cs + tap * cd) * k.in_cpad;
                         const int xstep = cs * k.in_cpad;                                  // bytes between the rows of two consecutive outputs
-#else
-                        const int8_t *xrow = cur + (t0 + tap) * k.in_cpad;
-#endif
                         for (int c16 = 0; c16 < c16n; ++c16) {
                             const int4 wa = *(const int4 *)(w0 + tap * k.in_cpad + 16 * c16);
                             const int4 wb4 = *(const int4 *)(w1 + tap * k.in_cpad + 16 * c16);
 #pragma unroll
                             for (int i = 0; i < KWS_POOL_MAX; ++i) {
                                 if (i < tb) {
-#if KWS_NN_SD
                                     const int4 xv = *(const int4 *)(xrow + i * xstep + 16 * c16);
-#else
-                                    const int4 xv = *(const int4 *)(xrow + i * k.in_cpad + 16 * c16);
-#endif
                                     int a = acc[i][0], c = acc[i][1];
                                     a = __builtin_amdgcn_sdot4(wa.x, xv.x, a, false);
                                     a = __builtin_amdgcn_sdot4(wa.y, xv.y, a, false);
@@ -360,18 +332,13 @@ __global__ __launch_bounds__(KWS_WAVE * MAXW) void KWS_NN_GENERIC_NAME(KwsNnPlan
             mark(1 + b);
             int8_t *tmp = cur; cur = nxt; nxt = tmp;
         }
-#if KWS_NN_TRUNK
-        {
+        if constexpr (TRUNK) {
             int8_t *dst = handoff + (size_t)(ci - ci0) * N.fc_in;
             for (int i = lane; i < N.fc_in; i += 64) dst[i] = fcx[i];
             WAVE_SYNC();
-        }
-#else
-        nn_head(N, head, fcx, lgv, lane, clip, scores, taps);
-#endif
+        } else nn_head(N, head, fcx, lgv, lane, clip, scores, taps);
         mark(1 + KWS_MAX_BLOCKS);
     }
     if (profiling && lane == 0)
         for (int i = 0; i < KWS_MAX_BLOCKS + 2; ++i) taps.prof[i] = ph[i];
 }
-

@@ -64,7 +64,9 @@ int kws_dense_layer_count(const kws_handle *h);          /* FULLY_CONNECTED laye
  * padded input image past the kernels' LDS budget.  A graph with a strided or dilated block runs in KWS_MODE_EXACT only: kws_set_mode(h, KWS_MODE_FAST) returns
  * KWS_ERROR_UNSUPPORTED_MODEL and the handle goes on serving KWS_MODE_EXACT. */
 const char *kws_nn_kernel_name(const kws_handle *h);    /* which network kernel serves this model (diagnostics); "kws_nn_sd_kernel" / "kws_nn_f32_sd_kernel" (in front of a
-                                                            dense stack: "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel", float32 likewise) for a graph with a strided or dilated block */
+                                                            dense stack: "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel", float32 likewise) for a graph with a strided or dilated block.
+                                                            The strings are LABELS of the kernels' forms, stable across releases, not device symbols: the generic kernels are
+                                                            templates (kws_nn_kernel<MAXW, TRUNK, SD>, kws_nn_f32_kernel<MAXT, TRUNK, SD>) and a profiler shows their instantiations */
 const char *kws_mfcc_kernel_name(const kws_handle *h);  /* the spectral kernel of int16 batches, MFCC and MFE blocks alike: "kws_mfcc8_kernel" / "kws_mfcc_kernel" (tuned shapes), "kws_mfcc8_kernel (chunked)" (general plans whose spectral stage fits the tuned kernel: chunks of at most 49 frames), "kws_spectral_lds_kernel" (general shapes), "kws_spectral_generic_kernel" (those whose arrays exceed the LDS) */
 int kws_model_is_float(const kws_handle *h);             /* 1: float32 graph (EI_CLASSIFIER_TFLITE_INPUT_QUANTIZED == 0) */
 

@@ -89,7 +89,7 @@ def routes_of(trace):
 # One block per distinct sequence: the operations, then (indented) every "<model> <mode> <call>" that enqueues exactly them.  "entry2:" / "entry3:": the
 # development build with KWS_DEV_FAST_ENTRY=2 / 3.  Template arguments of kws_fast_kernel: <NZ, DG, PROF, FROM_CEP, NET, QCP, MFE>.
 ROUTES_TABLE = """
-kws_mfcc8_kernel<true, 8, 40, false, true, 2> ; kws_nn_f32_kernel<512> ; rc 0
+kws_mfcc8_kernel<true, 8, 40, false, true, 2> ; kws_nn_f32_kernel<512, false, false> ; rc 0
     cfg2_mfcc40_f32.kwsm exact classify_features
     cfg2_mfcc40_f32.kwsm exact classify_scores
     cfg5_dscnn_mfcc40_f32.kwsm exact classify_features
@@ -101,7 +101,7 @@ kws_mfcc8_kernel<true, 8, 40, false, true, 2> ; rc 0
     cfg5_dscnn_mfcc40_int8.kwsm exact extract_mfcc
     entry2:cfg2_mfcc40_int8.kwsm exact extract_mfcc
     entry3:cfg2_mfcc40_int8.kwsm exact extract_mfcc
-kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<512> ; rc 0
+kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<512, false, false> ; rc 0
     cfg2_mfcc40_f32.kwsm exact cmvn_inference_features
     cfg2_mfcc40_f32.kwsm exact cmvn_inference_scores
     cfg5_dscnn_mfcc40_f32.kwsm exact cmvn_inference_features
@@ -143,26 +143,26 @@ kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; rc 0
     entry3:cfg2_mfcc40_int8.kwsm fast streams_step_1
     entry3:cfg2_mfcc40_int8.kwsm fast streams_step_2
     entry3:cfg2_mfcc40_int8.kwsm fast streams_step_3
-kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<512> ; kws_maf_kernel ; rc 0
+kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<512, false, false> ; kws_maf_kernel ; rc 0
     cfg2_mfcc40_f32.kwsm exact streams_step_4
     cfg2_mfcc40_f32.kwsm exact streams_step_5
     cfg5_dscnn_mfcc40_f32.kwsm exact streams_step_4
     cfg5_dscnn_mfcc40_f32.kwsm exact streams_step_5
-memset_async 4 ; kws_fast_kernel<4, 5, false, false, false, 0, false> ; memset_async 4 ; kws_fast_kernel_w3<4, 5, false, false, true, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<512> ; rc 0
+memset_async 4 ; kws_fast_kernel<4, 5, false, false, false, 0, false> ; memset_async 4 ; kws_fast_kernel_w3<4, 5, false, false, true, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<512, false, false> ; rc 0
     cfg2_mfcc40_f32.kwsm fast classify_features
-memset_async 4 ; kws_fast_kernel_w3<4, 5, false, false, true, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<512> ; rc 0
+memset_async 4 ; kws_fast_kernel_w3<4, 5, false, false, true, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<512, false, false> ; rc 0
     cfg2_mfcc40_f32.kwsm fast classify_scores
 memset_async 4 ; kws_fast_kernel<4, 5, false, false, false, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_cmvn_nn_kernel<false> ; rc 0
     cfg2_mfcc40_f32.kwsm fast extract_mfcc
     cfg2_mfcc40_int8.kwsm fast extract_mfcc
     cfg5_dscnn_mfcc40_int8.kwsm fast extract_mfcc
-memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<512> ; rc 0
+memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<512, false, false> ; rc 0
     cfg2_mfcc40_f32.kwsm fast cmvn_inference_features
     cfg5_dscnn_mfcc40_f32.kwsm fast cmvn_inference_features
-memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<512> ; rc 0
+memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<512, false, false> ; rc 0
     cfg2_mfcc40_f32.kwsm fast cmvn_inference_scores
     cfg5_dscnn_mfcc40_f32.kwsm fast cmvn_inference_scores
-kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<512> ; kws_maf_kernel ; rc 0
+kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<512, false, false> ; kws_maf_kernel ; rc 0
     cfg2_mfcc40_f32.kwsm fast streams_step_4
     cfg2_mfcc40_f32.kwsm fast streams_step_5
     cfg5_dscnn_mfcc40_f32.kwsm fast streams_step_4
@@ -205,28 +205,28 @@ kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; memset_async 4 ; mems
     entry2:cfg2_mfcc40_int8.kwsm fast streams_step_5
     entry3:cfg2_mfcc40_int8.kwsm fast streams_step_4
     entry3:cfg2_mfcc40_int8.kwsm fast streams_step_5
-memset_async 4 ; memset_async 4 ; kws_mfcc8_kernel<true, 8, 40, false, true, 2> ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_nn_f32_kernel<512> ; memcpy_async 4 ; rc 0
+memset_async 4 ; memset_async 4 ; kws_mfcc8_kernel<true, 8, 40, false, true, 2> ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_nn_f32_kernel<512, false, false> ; memcpy_async 4 ; rc 0
     cfg5_dscnn_mfcc40_f32.kwsm fast classify_features
     cfg5_dscnn_mfcc40_f32.kwsm fast classify_scores
 memset_async 4 ; memset_async 4 ; kws_mfcc8_kernel<true, 8, 40, false, true, 2> ; rc 0
     cfg5_dscnn_mfcc40_f32.kwsm fast extract_mfcc
     entry3:cfg2_mfcc40_int8.kwsm fast extract_mfcc
-kws_mfcc8_kernel<true, 8, 40, false, true, 2> ; kws_nn_kernel<16> ; rc 0
+kws_mfcc8_kernel<true, 8, 40, false, true, 2> ; kws_nn_kernel<16, false, false> ; rc 0
     cfg5_dscnn_mfcc40_int8.kwsm exact classify_features
     cfg5_dscnn_mfcc40_int8.kwsm exact classify_scores
-kws_cmvn_nn_kernel<false> ; kws_nn_kernel<16> ; rc 0
+kws_cmvn_nn_kernel<false> ; kws_nn_kernel<16, false, false> ; rc 0
     cfg5_dscnn_mfcc40_int8.kwsm exact cmvn_inference_features
     cfg5_dscnn_mfcc40_int8.kwsm exact cmvn_inference_scores
-kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; kws_cmvn_nn_kernel<false> ; kws_nn_kernel<16> ; kws_maf_kernel ; rc 0
+kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; kws_cmvn_nn_kernel<false> ; kws_nn_kernel<16, false, false> ; kws_maf_kernel ; rc 0
     cfg5_dscnn_mfcc40_int8.kwsm exact streams_step_4
     cfg5_dscnn_mfcc40_int8.kwsm exact streams_step_5
-memset_async 4 ; kws_fast_kernel<4, 5, false, false, false, 0, false> ; kws_nn_kernel<16> ; memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_nn_kernel<16> ; kws_cmvn_nn_kernel<false> ; kws_nn_kernel<16> ; rc 0
+memset_async 4 ; kws_fast_kernel<4, 5, false, false, false, 0, false> ; kws_nn_kernel<16, false, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_nn_kernel<16, false, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_kernel<16, false, false> ; rc 0
     cfg5_dscnn_mfcc40_int8.kwsm fast classify_features
     cfg5_dscnn_mfcc40_int8.kwsm fast classify_scores
-memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_nn_kernel<16> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_kernel<16> ; rc 0
+memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_nn_kernel<16, false, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_kernel<16, false, false> ; rc 0
     cfg5_dscnn_mfcc40_int8.kwsm fast cmvn_inference_features
     cfg5_dscnn_mfcc40_int8.kwsm fast cmvn_inference_scores
-kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_nn_kernel<16> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_kernel<16> ; kws_maf_kernel ; rc 0
+kws_mfcc_kernel<9, false, false, 8, 40, false, false, 0> ; memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_nn_kernel<16, false, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_kernel<16, false, false> ; kws_maf_kernel ; rc 0
     cfg5_dscnn_mfcc40_int8.kwsm fast streams_step_4
     cfg5_dscnn_mfcc40_int8.kwsm fast streams_step_5
 kws_mfcc8_kernel<true, 12, 32, false, false, 2> ; kws_nn_mfma_kernel<16> ; rc 0
@@ -313,62 +313,62 @@ memset_async 4 ; kws_fast_kernel<4, 4, false, false, false, 0, false> ; memset_a
 kws_mfcc_kernel<9, false, false, 4, 32, false, false, 0> ; memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_nn_mfma_kernel<16> ; kws_cmvn_nn_kernel<true> ; memcpy_async 4 ; kws_maf_kernel ; rc 0
     l476_no_yes.kwsm fast streams_step_4
     l476_no_yes.kwsm fast streams_step_5
-kws_mfcc8_kernel<true, 4, 32, false, false, 2> ; kws_nn_f32_kernel<1024> ; rc 0
+kws_mfcc8_kernel<true, 4, 32, false, false, 2> ; kws_nn_f32_kernel<1024, false, false> ; rc 0
     l476_no_yes_f32.kwsm exact classify_features
     l476_no_yes_f32.kwsm exact classify_scores
     entry2:l476_no_yes_f32.kwsm exact classify_features
     entry2:l476_no_yes_f32.kwsm exact classify_scores
     entry3:l476_no_yes_f32.kwsm exact classify_features
     entry3:l476_no_yes_f32.kwsm exact classify_scores
-kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<1024> ; rc 0
+kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<1024, false, false> ; rc 0
     l476_no_yes_f32.kwsm exact cmvn_inference_features
     l476_no_yes_f32.kwsm exact cmvn_inference_scores
     entry2:l476_no_yes_f32.kwsm exact cmvn_inference_features
     entry2:l476_no_yes_f32.kwsm exact cmvn_inference_scores
     entry3:l476_no_yes_f32.kwsm exact cmvn_inference_features
     entry3:l476_no_yes_f32.kwsm exact cmvn_inference_scores
-kws_mfcc_kernel<9, false, false, 4, 32, false, false, 0> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<1024> ; kws_maf_kernel ; rc 0
+kws_mfcc_kernel<9, false, false, 4, 32, false, false, 0> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<1024, false, false> ; kws_maf_kernel ; rc 0
     l476_no_yes_f32.kwsm exact streams_step_4
     l476_no_yes_f32.kwsm exact streams_step_5
     entry2:l476_no_yes_f32.kwsm exact streams_step_4
     entry2:l476_no_yes_f32.kwsm exact streams_step_5
     entry3:l476_no_yes_f32.kwsm exact streams_step_4
     entry3:l476_no_yes_f32.kwsm exact streams_step_5
-memset_async 4 ; kws_fast_kernel<4, 4, false, false, false, 0, false> ; memset_async 4 ; kws_fast_kernel_w3<4, 4, false, false, true, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 4, 32, false, false, 2> ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<1024> ; rc 0
+memset_async 4 ; kws_fast_kernel<4, 4, false, false, false, 0, false> ; memset_async 4 ; kws_fast_kernel_w3<4, 4, false, false, true, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 4, 32, false, false, 2> ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<1024, false, false> ; rc 0
     l476_no_yes_f32.kwsm fast classify_features
-memset_async 4 ; kws_fast_kernel_w3<4, 4, false, false, true, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 4, 32, false, false, 2> ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<1024> ; rc 0
+memset_async 4 ; kws_fast_kernel_w3<4, 4, false, false, true, 0, false> ; memset_async 4 ; kws_mfcc8_kernel<false, 4, 32, false, false, 2> ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; kws_nn_f32_kernel<1024, false, false> ; rc 0
     l476_no_yes_f32.kwsm fast classify_scores
-memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<1024> ; rc 0
+memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<1024, false, false> ; rc 0
     l476_no_yes_f32.kwsm fast cmvn_inference_features
     entry2:l476_no_yes_f32.kwsm fast cmvn_inference_features
     entry3:l476_no_yes_f32.kwsm fast cmvn_inference_features
-memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<1024> ; rc 0
+memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<1024, false, false> ; rc 0
     l476_no_yes_f32.kwsm fast cmvn_inference_scores
     entry2:l476_no_yes_f32.kwsm fast cmvn_inference_scores
     entry3:l476_no_yes_f32.kwsm fast cmvn_inference_scores
-kws_mfcc_kernel<9, false, false, 4, 32, false, false, 0> ; memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<1024> ; kws_maf_kernel ; rc 0
+kws_mfcc_kernel<9, false, false, 4, 32, false, false, 0> ; memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; kws_nn_f32_kernel<1024, false, false> ; kws_maf_kernel ; rc 0
     l476_no_yes_f32.kwsm fast streams_step_4
     l476_no_yes_f32.kwsm fast streams_step_5
     entry2:l476_no_yes_f32.kwsm fast streams_step_4
     entry2:l476_no_yes_f32.kwsm fast streams_step_5
     entry3:l476_no_yes_f32.kwsm fast streams_step_4
     entry3:l476_no_yes_f32.kwsm fast streams_step_5
-kws_mfcc8_kernel<false, 4, 32, false, false, 2> ; kws_mfe_norm_kernel ; kws_quantize_kernel ; kws_nn_kernel<16> ; rc 0
+kws_mfcc8_kernel<false, 4, 32, false, false, 2> ; kws_mfe_norm_kernel ; kws_quantize_kernel ; kws_nn_kernel<16, false, false> ; rc 0
     mfe_block.kwsm exact classify_features
     mfe_block.kwsm exact classify_scores
 kws_mfcc8_kernel<false, 4, 32, false, false, 2> ; kws_mfe_norm_kernel ; kws_quantize_kernel ; rc 0
     mfe_block.kwsm exact extract_mfcc
-kws_unring_kernel ; kws_mfe_norm_kernel ; kws_quantize_kernel ; kws_nn_kernel<16> ; rc 0
+kws_unring_kernel ; kws_mfe_norm_kernel ; kws_quantize_kernel ; kws_nn_kernel<16, false, false> ; rc 0
     mfe_block.kwsm exact cmvn_inference_features
     mfe_block.kwsm exact cmvn_inference_scores
     mfe_block.kwsm fast cmvn_inference_features
     mfe_block.kwsm fast cmvn_inference_scores
-kws_mfcc_kernel<9, false, false, 4, 32, false, false, 0> ; kws_unring_kernel ; kws_mfe_norm_kernel ; kws_quantize_kernel ; kws_nn_kernel<16> ; kws_maf_kernel ; rc 0
+kws_mfcc_kernel<9, false, false, 4, 32, false, false, 0> ; kws_unring_kernel ; kws_mfe_norm_kernel ; kws_quantize_kernel ; kws_nn_kernel<16, false, false> ; kws_maf_kernel ; rc 0
     mfe_block.kwsm exact streams_step_4
     mfe_block.kwsm exact streams_step_5
     mfe_block.kwsm fast streams_step_4
     mfe_block.kwsm fast streams_step_5
-memset_async 4 ; kws_fast_kernel<4, 4, false, false, false, 0, true> ; kws_mfe_norm_kernel ; kws_quantize_kernel ; kws_nn_kernel<16> ; rc 0
+memset_async 4 ; kws_fast_kernel<4, 4, false, false, false, 0, true> ; kws_mfe_norm_kernel ; kws_quantize_kernel ; kws_nn_kernel<16, false, false> ; rc 0
     mfe_block.kwsm fast classify_features
     mfe_block.kwsm fast classify_scores
 memset_async 4 ; kws_fast_kernel<4, 4, false, false, false, 0, true> ; kws_mfe_norm_kernel ; kws_quantize_kernel ; rc 0
@@ -378,7 +378,7 @@ memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; memset_async 
     entry2:cfg2_mfcc40_int8.kwsm fast classify_scores
 memset_async 4 ; kws_mfcc8_kernel<false, 8, 40, false, false, 2> ; memset_async 4 ; memset_async 4 ; kws_fast_kernel<4, 4, false, true, false, 0, false> ; kws_cmvn_nn_kernel<false> ; memcpy_async 4 ; rc 0
     entry2:cfg2_mfcc40_int8.kwsm fast extract_mfcc
-memset_async 4 ; memset_async 4 ; kws_mfcc8_kernel<true, 4, 32, false, false, 2> ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_nn_f32_kernel<1024> ; memcpy_async 4 ; rc 0
+memset_async 4 ; memset_async 4 ; kws_mfcc8_kernel<true, 4, 32, false, false, 2> ; kws_fast_kernel<4, 4, false, true, true, 0, false> ; kws_nn_f32_kernel<1024, false, false> ; memcpy_async 4 ; rc 0
     entry2:l476_no_yes_f32.kwsm fast classify_features
     entry2:l476_no_yes_f32.kwsm fast classify_scores
     entry3:l476_no_yes_f32.kwsm fast classify_features

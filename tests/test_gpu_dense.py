@@ -78,7 +78,7 @@ def test_network_int8_all_taps(name, gpu_models, expected, fixture_npz):
     _, _, hidden, last, _, _ = D.graph_layout(D.dense_blob(name))
     assert gm.dense_layer_count == len(hidden) + 1 and gm.nn_kernel == "kws_dense_i8_kernel"
     hid = np.concatenate([taps[i] for i in hidden], axis=1) if hidden else np.zeros((D.N_INPUTS, 0), np.int8)
-    blk = D.block_outputs(D.dense_blob(name))               # the conv blocks' share of the tap: written by kws_nn_trunk_kernel
+    blk = D.block_outputs(D.dense_blob(name))               # the conv blocks' share of the tap: written by the trunk form of kws_nn_kernel
     trunk = np.concatenate([taps[i] for i in blk], axis=1) if blk else np.zeros((D.N_INPUTS, 0), np.int8)
     assert gm.pooled_tap_bytes == trunk.shape[1] + hid.shape[1]
     for B in BATCHES + D.EXTRA_BATCHES.get(name, ()):

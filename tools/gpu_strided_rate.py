@@ -7,7 +7,8 @@ Four graphs, each as the int8 graph and as its float32 twin (tools/dequantize_mo
   g40_s2   49 x 40 features (the cfg2 DSP block), the same blocks, first block at stride 2
   g40_s1   its stride-1 twin
 (the shipped graphs' SAME pools of 7 do not divide 25 rows without padding, which no kernel here serves: both forms pool VALID, 7 then 3.)
-A stride-1 form runs kws_nn_kernel / kws_nn_f32_kernel, its stride-2 form kws_nn_sd_kernel / kws_nn_f32_sd_kernel: the same generic text.
+A stride-1 form runs kws_nn_kernel / kws_nn_f32_kernel, its stride-2 form kws_nn_sd_kernel / kws_nn_f32_sd_kernel (labels: the SD instantiations of the same
+templates).
 
 Timed with device events, every handle warmed up first, the handles alternating inside each of --repeats rounds in this one command:
   net    the network launch alone (kws_nn_batch_device / kws_nn_f32_batch_device on the resident int8 tensors / feature matrices), --steps launches
