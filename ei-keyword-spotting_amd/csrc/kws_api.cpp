@@ -85,6 +85,7 @@ int kws_frame_count(const kws_handle *h) { return h->dsp.n_frames; }
 int kws_filter_count(const kws_handle *h) { return h->dsp.n_filters; }
 int kws_pooled_tap_bytes(const kws_handle *h) { return h->pooled_tap_bytes; }
 int kws_dense_layer_count(const kws_handle *h) { return h ? h->n_dense : 0; }
+int kws_conv2d_block_count(const kws_handle *h) { return h ? h->n_conv2d : 0; }
 int kws_model_is_float(const kws_handle *h) { return h->is_float ? 1 : 0; }
 // (the tuned kernel of the int16 batch paths; float samples -- the SDK's signal_t callback -- run kws_mfcc_kernel, the same arithmetic on
 // the older lane layout)
@@ -97,6 +98,8 @@ const char *kws_mfcc_kernel_name(const kws_handle *h)
 }
 const char *kws_nn_kernel_name(const kws_handle *h)
 {
+    // a 2-D graph: the 2-D trunk, then the dense kernel
+    if (h->n_conv2d) return h->is_float ? "kws_nn2d_f32_trunk_kernel + kws_dense_f32_kernel" : "kws_nn2d_trunk_kernel + kws_dense_i8_kernel";
     // a strided or dilated block in front of a dense stack: the strided form of the trunk, then the dense kernel
     if (h->is_float ? kws_nnf_dense(h->nnf) && kws_nnf_strided(h->nnf) : kws_nn_dense(h->nn) && kws_nn_strided(h->nn))
         return h->is_float ? "kws_nn_f32_sd_trunk_kernel + kws_dense_f32_kernel" : "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel";
@@ -122,6 +125,8 @@ EI_IMPULSE_ERROR ensure_scratch(kws_handle *h, size_t B)
 EI_IMPULSE_ERROR kws_set_mode(kws_handle *h, int mode)
 {
     if (!h || (mode != KWS_MODE_EXACT && mode != KWS_MODE_FAST)) return fail(KWS_ERROR_BAD_ARGUMENT, "kws_set_mode: bad argument");
+    if (mode == KWS_MODE_FAST && h->n_conv2d)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a 2-D convolutional graph keeps the exact kernels (no fused plan, no calibrated logit gain)");
     if (mode == KWS_MODE_FAST && h->is_float && kws_nnf_dense(h->nnf))
         return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a float32 graph with a dense stack has no calibrated logit gain (the guard needs one); it keeps the exact kernels");
     if (mode == KWS_MODE_FAST && (h->is_float ? kws_nnf_strided(h->nnf) : kws_nn_strided(h->nn)))
@@ -735,6 +740,17 @@ int kws_dev_f32_blocking(const kws_handle *h, int block, int out[8])
     out[0] = k.tb; out[1] = k.ob; out[2] = k.fused_pool; out[3] = k.ntb; out[4] = k.rows; out[5] = k.depthwise;
     out[6] = waves; out[7] = (int)kws_nn_f32_smem_bytes(N, waves);
     return 0;
+}
+
+// development / test aid (not in the public headers): the handle's exact network over the clips a device list names (sel: [0] = count, [1 + i] = clip index
+// -- the route batch_network_device takes when a fast tier hands clips back), for graphs no fast tier reaches (2-D graphs: tests/test_gpu_conv2d_graphs.py).
+// in: the feature matrices (float32 graph) or the int8 input tensors, [B][features]; scores of clips the list does not name are left alone.
+EI_IMPULSE_ERROR kws_dev_network_sel(kws_handle *h, const void *in, size_t B, float *scores, const int *sel, void *stream)
+{
+    if (!h || !in || !scores || !sel) return fail(KWS_ERROR_BAD_ARGUMENT, "kws_dev_network_sel: null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    std::lock_guard<std::mutex> lk(h->mu);
+    return network_device(h, (const float *)in, (const int8_t *)in, B, scores, nullptr, nullptr, nullptr, nullptr, sel, (hipStream_t)stream);
 }
 
 // development aid (not in the public headers): per-phase shader-clock totals of wave 0 of the float network kernel

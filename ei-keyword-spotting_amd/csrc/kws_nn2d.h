@@ -1,0 +1,29 @@
+// kws_nn2d.h -- the 2-D trunks: what kws_nn2d_int8.hip / kws_nn2d_f32.hip share with the plan builder (kws_plan.cpp) and with the launchers
+// of the dense stacks (kws_nn_int8.hip launch_dense_i8, kws_nn_f32.hip launch_dense_f32), which call them chunk by chunk of the hand-off buffer.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "kws_plan.h"
+
+// waves per workgroup: the most that fit the LDS budget (158 KB int8, 150 KB float: the 1-D kernels' budgets), from 16 down to 4; the waves of a workgroup
+// share one copy of the weights
+#define KWS_NN2D_WAVES_MIN 4
+#define KWS_NN2D_WAVES_MAX 16
+#define KWS_NN2D_LDS_I8 (158 * 1024)
+#define KWS_NN2D_LDS_F32 (150 * 1024)
+
+// LDS bytes at n_waves waves per workgroup, and the wave count the launcher picks (0: the graph does not fit at KWS_NN2D_WAVES_MIN -- refused at kws_create);
+// kws_plan.cpp
+size_t kws_nn2d_smem_bytes(const KwsNn2dPlan &N, int n_waves);
+int kws_nn2d_waves(const KwsNn2dPlan &N);
+size_t kws_nn2d_f32_smem_bytes(const KwsNn2dPlanF32 &N, int n_waves);
+int kws_nn2d_f32_waves(const KwsNn2dPlanF32 &N);
+
+// The trunk over list entries ci0 .. ci1 - 1 (sel: kws_device.h's clip list, or NULL): every block, the last one's output -- flattened NHWC, the bytes /
+// floats of the reference's tensor -- to handoff [ci - ci0][out_n].  int8: tap_pooled (or NULL) receives every block's pooled output per clip, one after
+// another, rows of pooled_stride bytes.  Returns 0 or a hipError_t.
+// Weak references: the launchers are defined in the trunks' own translation units, and a link without those units (a host-only build of the library's other
+// units) leaves them NULL.  The dense launchers test for that and answer hipErrorInvalidDeviceFunction: a missing kernel is an error, never a fall-back.
+__attribute__((weak)) int kws_launch_nn2d_trunk(const KwsNn2dPlan &N, const int8_t *q_in, int n_clips, int8_t *handoff, int ci0, int ci1, int8_t *tap_pooled, int pooled_stride,
+                          const int *sel, int n_cu, hipStream_t stream);
+__attribute__((weak)) int kws_launch_nn2d_f32_trunk(const KwsNn2dPlanF32 &N, const float *features, int n_clips, float *handoff, int ci0, int ci1, const int *sel, int n_cu,
+                              hipStream_t stream);

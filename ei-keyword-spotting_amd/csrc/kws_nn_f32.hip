@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "kws_device.h"
+#include "kws_nn2d.h"
 
 // ---------------------------------------------------------------------------------------------------------
 //  Kernel 2f: float32 models.  One wave per clip.  Every accumulation replays the reference's sequential
@@ -537,13 +538,27 @@ static int launch_dense_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, c
         if (e != hipSuccess) return (int)e;
     }
     auto dense_grid = [&](int n) { const int g = (n + 63) / 64; return g > n_cu * 8 ? n_cu * 8 : g; };
-    if (N.n_blocks == 0) {
+    const KwsNn2dPlanF32 *const trunk2d = N.handoff->trunk2d_f32;     // a 2-D graph: kws_nn2d_f32_trunk_kernel fills the hand-off
+    if (N.n_blocks == 0 && !trunk2d) {
         hipLaunchKernelGGL(kws_dense_f32_kernel, dim3(dense_grid(n_clips)), dim3(KWS_WAVE * KWS_DENSEF_WAVES), dsmem, stream, D, features, 1, 0, n_clips, n_clips,
                            scores, tap_logits, sel);
         return (int)hipGetLastError();
     }
     float *ho = (float *)kws_handoff_for(N.handoff, (void *)stream);
     if (!ho) return (int)hipErrorOutOfMemory;
+    if (trunk2d) {
+        if (!kws_launch_nn2d_f32_trunk) return (int)hipErrorInvalidDeviceFunction;      // (linked without kws_nn2d_f32.hip: kws_nn2d.h)
+        const int chunk = (int)(N.handoff->bytes / (sizeof(float) * (size_t)N.fc_in));
+        for (int c0 = 0; c0 < n_clips; c0 += chunk) {
+            const int c1 = n_clips - c0 > chunk ? c0 + chunk : n_clips;
+            int rc = kws_launch_nn2d_f32_trunk(*trunk2d, features, n_clips, ho, c0, c1, sel, n_cu, stream);
+            if (rc) return rc;
+            hipLaunchKernelGGL(kws_dense_f32_kernel, dim3(dense_grid(c1 - c0)), dim3(KWS_WAVE * KWS_DENSEF_WAVES), dsmem, stream, D, (const float *)ho, 0, c0, c1, n_clips,
+                               scores, tap_logits, sel);
+            if ((rc = (int)hipGetLastError())) return rc;
+        }
+        return 0;
+    }
     const int n_waves = kws_nn_f32_waves(N);
     const size_t smem = kws_nn_f32_smem_bytes(N, n_waves);
     const int per_cu = (int)std::max<size_t>(1, (160 * 1024) / smem);

@@ -375,6 +375,226 @@ static const char *h_conv_geometry_why(bool dw, int padding, int in_w, int f_w, 
     return nullptr;
 }
 
+// ---- 2-D convolutional graphs -------------------------------------------------------------------------------------------------------
+// A graph belongs to the family when the tensor flowing into its first convolution is [1][H][W][C] with H > 1 and W > 1 (H: frames, W: cepstral / mel
+// columns, as Keras' Reshape((frames, columns, 1)) lays them out).  [1][1][W][C] stays with the 1-D planner, its refusals included.
+static bool h_is_2d(const Model &m, size_t i, int cur)
+{
+    if (i >= m.n.size() || (m.n[i].op != OP_CONV_2D && m.n[i].op != OP_DEPTHWISE_CONV_2D)) return false;
+    const Tensor &x = m.t[cur];
+    return x.dims.size() == 4 && x.dims[0] == 1 && x.dims[1] > 1 && x.dims[2] > 1;
+}
+
+// LDS of the 2-D trunks at n_waves waves per workgroup -- per workgroup the weights and per-channel constants of every block, per wave two ping-pong
+// images, laid out as kws_nn2d_trunk_kernel / kws_nn2d_f32_trunk_kernel walk them -- and the wave count their launchers pick (kws_nn2d.h).  Host arithmetic
+// on the plan alone, so it lives with the plan builder: kws_create refuses a graph that does not fit before any kernel is involved.
+size_t kws_nn2d_smem_bytes(const KwsNn2dPlan &N, int n_waves)
+{
+    size_t s = 0;
+    int img_b[2] = { 0, 0 };
+    for (int b = 0; b < N.n_blocks; ++b) {
+        const KwsConv2dBlock &k = N.blk[b];
+        s += (((size_t)k.w_bytes + 15) & ~(size_t)15) + (size_t)k.g.out_c * 16;
+        img_b[b & 1] = std::max(img_b[b & 1], kws_nn2d_img_bytes(k.g, 1));
+    }
+    return s + (size_t)n_waves * (size_t)(img_b[0] + img_b[1]);
+}
+int kws_nn2d_waves(const KwsNn2dPlan &N)
+{
+    for (int nw = KWS_NN2D_WAVES_MAX; nw >= KWS_NN2D_WAVES_MIN; --nw)
+        if (kws_nn2d_smem_bytes(N, nw) <= KWS_NN2D_LDS_I8) return nw;
+    return 0;
+}
+size_t kws_nn2d_f32_smem_bytes(const KwsNn2dPlanF32 &N, int n_waves)
+{
+    size_t s = 0;
+    int img_b[2] = { 0, 0 };
+    for (int b = 0; b < N.n_blocks; ++b) {
+        const KwsConv2dGeom &g = N.blk[b].g;
+        s += sizeof(float) * (size_t)(((g.out_c * g.kh * g.krow + 3) & ~3) + ((g.out_c + 3) & ~3));
+        img_b[b & 1] = std::max(img_b[b & 1], kws_nn2d_img_bytes(g, 4));
+    }
+    return s + (size_t)n_waves * (size_t)(img_b[0] + img_b[1]);
+}
+int kws_nn2d_f32_waves(const KwsNn2dPlanF32 &N)
+{
+    for (int nw = KWS_NN2D_WAVES_MAX; nw >= KWS_NN2D_WAVES_MIN; --nw)
+        if (kws_nn2d_f32_smem_bytes(N, nw) <= KWS_NN2D_LDS_F32) return nw;
+    return 0;
+}
+
+struct H2dBlock { KwsConv2dGeom g; const Node *cv; int x_id, y_id, act, pool_act; };
+
+// The blocks of a 2-D graph from conv node i on: CONV_2D [-> MAX_POOL_2D], RESHAPEs that keep the quantisation skipped.  Everything comes from an untrusted
+// blob, so every dim, filter side and stride is bounded BEFORE any arithmetic on it (sides <= 1024, filters and pools <= 7, strides <= 7: every product of
+// kernels/padding.h stays far inside an int).  On return i / cur stand behind the last block.
+static EI_IMPULSE_ERROR h_nn2d_walk(const Model &m, size_t &i, int &cur, bool is_float, std::vector<H2dBlock> &blocks)
+{
+    const uint32_t want = is_float ? TYPE_F32 : TYPE_I8;
+    auto same_quant = [&](int a, int b) {
+        if (is_float) return true;
+        return !m.t[a].scale.empty() && !m.t[b].scale.empty() && !m.t[a].zero.empty() && !m.t[b].zero.empty() && m.t[a].scale[0] == m.t[b].scale[0] &&
+               m.t[a].zero[0] == m.t[b].zero[0];
+    };
+    auto skip_reshapes = [&]() {
+        while (i < m.n.size() && m.n[i].op == OP_RESHAPE && m.n[i].in[0] == cur) {
+            if (!same_quant(cur, m.n[i].out[0])) return false;
+            cur = m.n[i].out[0];
+            i++;
+        }
+        return true;
+    };
+    int ch = 0, cw = 0, cc = 0;
+    while (i < m.n.size() && (m.n[i].op == OP_CONV_2D || m.n[i].op == OP_DEPTHWISE_CONV_2D)) {
+        if ((int)blocks.size() >= KWS_MAX_BLOCKS) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "more than %d conv blocks", KWS_MAX_BLOCKS);
+        const Node &cv = m.n[i];
+        if (cv.op == OP_DEPTHWISE_CONV_2D)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: DEPTHWISE_CONV_2D inside a 2-D graph is not served (the 2-D family is CONV_2D and MAX_POOL_2D)", i);
+        if (cv.in[0] != cur) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: input is not the flowing tensor", i);
+        const Tensor &x = m.t[cur], &w = m.t[cv.in[1]], &y = m.t[cv.out[0]];
+        const Tensor *bias = (cv.in.size() > 2 && cv.in[2] >= 0) ? &m.t[cv.in[2]] : nullptr;
+        if (x.dims.size() != 4 || w.dims.size() != 4 || y.dims.size() != 4 || x.dims[0] != 1 || y.dims[0] != 1)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: input, filter and output must be 4-D tensors of one batch", i);
+        if (x.type != want || w.type != want || y.type != want) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu tensor types", i);
+        H2dBlock B{};
+        KwsConv2dGeom &g = B.g;
+        g.in_h = x.dims[1]; g.in_w = x.dims[2]; g.in_c = x.dims[3];
+        g.out_c = w.dims[0]; g.kh = w.dims[1]; g.kw = w.dims[2];
+        if (g.in_h > KWS_NN2D_DIM_MAX || g.in_w > KWS_NN2D_DIM_MAX || g.in_c > 64 || g.out_c > 64 || g.kh > KWS_NN2D_K_MAX || g.kw > KWS_NN2D_K_MAX ||
+            w.dims[3] != g.in_c)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: a %d x %d filter over %d (filter: %d) -> %d channels on a %d x %d image is outside the 2-D kernels' "
+                        "limits (filter sides 1 .. %d, at most 64 channels, image sides up to %d)", i, g.kh, g.kw, g.in_c, w.dims[3], g.out_c, g.in_h, g.in_w,
+                        KWS_NN2D_K_MAX, KWS_NN2D_DIM_MAX);
+        if (!w.is_const || (bias && (!bias->is_const || bias->type != (is_float ? TYPE_F32 : TYPE_I32) || (long)bias->nbytes != 4l * g.out_c)))
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: the filter and the bias (%d values, %s) must be constants", i, g.out_c, is_float ? "float32" : "int32");
+        const int padding = cv.p[0];
+        g.sw = cv.p[1]; g.sh = cv.p[2]; B.act = cv.p[3];
+        if (g.sh < 1 || g.sh > KWS_NN2D_STRIDE_MAX || g.sw < 1 || g.sw > KWS_NN2D_STRIDE_MAX)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: stride %d x %d is outside 1 .. %d", i, g.sh, g.sw, KWS_NN2D_STRIDE_MAX);
+        if (cv.p[4] != 1 || cv.p[5] != 1)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: dilation %d x %d: a 2-D graph's convolutions are not dilated", i, cv.p[5], cv.p[4]);
+        if ((padding != 1 && padding != 2) || B.act < 0 || B.act > 3)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: padding %d / fused activation %d", i, padding, B.act);
+        if (ch && (ch != g.in_h || cw != g.in_w || cc != g.in_c)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "shape mismatch into conv %zu", i);
+        g.out_h = h_out_size(padding, g.in_h, g.kh, g.sh, 1); g.out_w = h_out_size(padding, g.in_w, g.kw, g.sw, 1);
+        if (g.out_h < 1 || g.out_w < 1 || y.dims[1] != g.out_h || y.dims[2] != g.out_w || y.dims[3] != g.out_c)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu output shape: the tensor is %d x %d x %d, kernels/padding.h gives %d x %d x %d", i, y.dims[1], y.dims[2],
+                        y.dims[3], g.out_h, g.out_w, g.out_c);
+        g.pad_t = h_pad_amount(g.sh, 1, g.in_h, g.kh, g.out_h); g.pad_l = h_pad_amount(g.sw, 1, g.in_w, g.kw, g.out_w);
+        B.cv = &cv; B.x_id = cur; B.y_id = cv.out[0];
+        cur = cv.out[0];
+        i++;
+        if (!skip_reshapes()) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "reshape changes quantisation");
+        if (i < m.n.size() && m.n[i].op == OP_ADD)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "ADD %zu: a per-channel ADD inside a 2-D graph is not served (its convolutions carry their bias and activation)", i);
+        g.ph = g.pw = g.psh = g.psw = 1; g.ppt = g.ppl = 0; g.has_pool = 0;
+        g.pool_h = g.out_h; g.pool_w = g.out_w;
+        if (i < m.n.size() && m.n[i].op == OP_MAX_POOL_2D) {
+            const Node &pl = m.n[i];
+            if (pl.in[0] != cur || !same_quant(cur, pl.out[0])) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu input", i);
+            const Tensor &px = m.t[cur], &py = m.t[pl.out[0]];
+            if (px.dims.size() != 4 || py.dims.size() != 4 || px.dims[1] != g.out_h || px.dims[2] != g.out_w || px.dims[3] != g.out_c || py.type != want)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: its input is not the convolution's %d x %d x %d output", i, g.out_h, g.out_w, g.out_c);
+            g.psw = pl.p[1]; g.psh = pl.p[2]; g.pw = pl.p[3]; g.ph = pl.p[4]; B.pool_act = pl.p[5];
+            if (g.ph < 1 || g.ph > KWS_NN2D_K_MAX || g.pw < 1 || g.pw > KWS_NN2D_K_MAX || g.psh < 1 || g.psh > KWS_NN2D_K_MAX || g.psw < 1 || g.psw > KWS_NN2D_K_MAX)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: window %d x %d / stride %d x %d is outside 1 .. %d", i, g.ph, g.pw, g.psh, g.psw, KWS_NN2D_K_MAX);
+            if ((pl.p[0] != 1 && pl.p[0] != 2) || B.pool_act < 0 || B.pool_act > 3 || (!is_float && B.pool_act != 0))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: padding %d / fused activation %d", i, pl.p[0], B.pool_act);
+            g.pool_h = h_out_size(pl.p[0], g.out_h, g.ph, g.psh, 1); g.pool_w = h_out_size(pl.p[0], g.out_w, g.pw, g.psw, 1);
+            if (g.pool_h < 1 || g.pool_w < 1 || py.dims[0] != 1 || py.dims[1] != g.pool_h || py.dims[2] != g.pool_w || py.dims[3] != g.out_c)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu output shape: the tensor is %d x %d x %d, kernels/padding.h gives %d x %d x %d", i, py.dims[1],
+                            py.dims[2], py.dims[3], g.pool_h, g.pool_w, g.out_c);
+            g.ppt = h_pad_amount(g.psh, 1, g.out_h, g.ph, g.pool_h); g.ppl = h_pad_amount(g.psw, 1, g.out_w, g.pw, g.pool_w);
+            // every window holds a value of the image (SAME: the last window may be ragged; a stride past the window skips values, never leaves the image)
+            if ((g.pool_h - 1) * g.psh - g.ppt >= g.out_h || (g.pool_w - 1) * g.psw - g.ppl >= g.out_w || g.ppt >= g.ph || g.ppl >= g.pw)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: a window lies outside the image", i);
+            g.has_pool = 1;
+            cur = pl.out[0];
+            i++;
+            if (!skip_reshapes()) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "reshape changes quantisation");
+        }
+        // the padded image: what the furthest tap of the last output reads, and at least the image behind its padding (VALID: trailing rows / columns no
+        // output reads are staged all the same)
+        g.img_rows = std::max(g.pad_t + g.in_h, (g.out_h - 1) * g.sh + g.kh);
+        g.img_cols = std::max(g.pad_l + g.in_w, (g.out_w - 1) * g.sw + g.kw);
+        g.krow = g.kw * g.in_c; g.krow4 = (g.krow + 3) & ~3;
+        const int row = g.img_cols * g.in_c;
+        g.img_pitch = is_float ? (row | 1) : 4 * (((row + 3) / 4) | 1);             // an odd number of dwords
+        ch = g.pool_h; cw = g.pool_w; cc = g.out_c;
+        blocks.push_back(B);
+    }
+    return EI_IMPULSE_OK;
+}
+
+static EI_IMPULSE_ERROR build_nn2d_i8(kws_handle *h, size_t &i, int &cur)
+{
+    const Model &m = h->model;
+    KwsNn2dPlan &P = h->nn2d;
+    memset(&P, 0, sizeof(P));
+    std::vector<H2dBlock> blocks;
+    if (EI_IMPULSE_ERROR e = h_nn2d_walk(m, i, cur, false, blocks)) return e;
+    P.n_features = (int)m.nn_input_frame_size;
+    if (blocks[0].g.in_h * blocks[0].g.in_w * blocks[0].g.in_c != P.n_features)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "first conv does not consume the feature vector");
+    for (size_t b = 0; b < blocks.size(); b++) {
+        const H2dBlock &B = blocks[b];
+        const Node &cv = *B.cv;
+        const Tensor &x = m.t[B.x_id], &w = m.t[cv.in[1]], &y = m.t[B.y_id];
+        const Tensor *bias = (cv.in.size() > 2 && cv.in[2] >= 0) ? &m.t[cv.in[2]] : nullptr;
+        KwsConv2dBlock &k = P.blk[b];
+        k.g = B.g;
+        const KwsConv2dGeom &g = k.g;
+        k.in_zp = x.zero[0]; k.out_zp = y.zero[0];
+        h_act_range(B.act, y.scale[0], y.zero[0], &k.act_min, &k.act_max);
+        // weights -> [out_c][kh][krow4]: a filter row's kw * in_c operands are contiguous in the NHWC image too; zero padded to whole dot4 words
+        // bias_eff = bias + input_offset * sum(w)   (integer_ops/conv.h:64-113)
+        std::vector<int8_t> wp((size_t)g.out_c * g.kh * g.krow4, 0);
+        k.w_bytes = (int)wp.size();
+        std::vector<int32_t> beff(g.out_c), mult(g.out_c), shift(g.out_c);
+        const int8_t *wd = (const int8_t *)w.data.data();
+        const int32_t *bd = bias ? (const int32_t *)bias->data.data() : nullptr;
+        const int32_t in_off = -x.zero[0];
+        const bool per_channel = w.scale.size() > 1;
+        if (w.data.size() < (size_t)g.out_c * g.kh * g.krow || (bias && bias->data.size() < (size_t)g.out_c * 4))
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv block %zu: constant data", b);
+        if (per_channel && ((int)w.scale.size() != g.out_c || w.qdim != 0)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv block %zu: per-channel scale count", b);
+        for (int oc = 0; oc < g.out_c; oc++) {
+            int64_t wsum = 0, wabs = 0;
+            for (int fy = 0; fy < g.kh; fy++)
+                for (int j = 0; j < g.krow; j++) {
+                    const int8_t v = wd[((size_t)oc * g.kh + fy) * g.krow + j];
+                    wp[((size_t)oc * g.kh + fy) * g.krow4 + j] = v;
+                    wsum += v; wabs += std::abs((int)v);
+                }
+            beff[oc] = (int32_t)((bd ? bd[oc] : 0) + (int64_t)in_off * wsum);
+            const double eff = (double)x.scale[0] * (double)(per_channel ? w.scale[oc] : w.scale[0]) / (double)y.scale[0];
+            int sh;
+            h_quantize_multiplier(eff, &mult[oc], &sh);          // kernel_util_lite.cc:89-103
+            shift[oc] = sh;
+            if (mult[oc] < 0 || sh < -31) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv block %zu channel %d: requantisation multiplier", b, oc);
+            // the left-shift bound of DESIGN 4.2, as for the 1-D blocks: the kernel pools raw accumulators on the strength of a monotonic requantisation
+            if (sh > 0 && h_left_shift_overflows(wabs, in_off, bd ? bd[oc] : 0, sh))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv block %zu channel %d: requantisation shifts left by %d and (sum|w| * max|x| + |bias|) << %d "
+                            "can pass 2^31 - 1", b, oc, sh, sh);
+        }
+        EI_IMPULSE_ERROR e;
+        if ((e = h->upload(wp, &k.w))) return e;
+        if ((e = h->upload(beff, &k.bias_eff))) return e;
+        if ((e = h->upload(mult, &k.mult))) return e;
+        if ((e = h->upload(shift, &k.shift))) return e;
+        P.tap_bytes += g.pool_h * g.pool_w * g.out_c;
+        P.n_blocks++;
+    }
+    const KwsConv2dGeom &lg = P.blk[P.n_blocks - 1].g;
+    P.out_n = lg.pool_h * lg.pool_w * lg.out_c;
+    if (kws_nn2d_waves(P) == 0)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "int8 2-D model needs %zu B of LDS at %d waves per workgroup (at most %d): its images do not fit the kernel's LDS budget",
+                    kws_nn2d_smem_bytes(P, KWS_NN2D_WAVES_MIN), KWS_NN2D_WAVES_MIN, 158 * 1024);
+    h->pooled_tap_bytes += P.tap_bytes;
+    h->n_conv2d = P.n_blocks;
+    return EI_IMPULSE_OK;
+}
+
 // Recognise the Edge Impulse 1-D CNN family and fold its per-model constants.
 EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
 {
@@ -405,6 +625,14 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         return true;
     };
     if (!skip_reshapes()) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "reshape changes quantisation");
+    if (h_is_2d(m, i, cur)) {
+        // a 2-D graph: its blocks in a plan of their own, then the dense stack -- always, a single FULLY_CONNECTED included
+        if (EI_IMPULSE_ERROR e = build_nn2d_i8(h, i, cur)) return e;
+        if (i >= m.n.size() || m.n[i].op != OP_FULLY_CONNECTED) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected FULLY_CONNECTED after the conv blocks");
+        if (EI_IMPULSE_ERROR e = build_dense_i8(h, i, cur, h->nn2d.out_n)) return e;
+        h->handoff.trunk2d = &h->nn2d;
+        return EI_IMPULSE_OK;
+    }
     while (i < m.n.size() && (m.n[i].op == OP_CONV_2D || m.n[i].op == OP_DEPTHWISE_CONV_2D)) {
         if (N.n_blocks >= KWS_MAX_BLOCKS) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "more than %d conv blocks", KWS_MAX_BLOCKS);
         const Node &cv = m.n[i];
@@ -638,6 +866,49 @@ static long h_first_non_finite(const std::vector<float> &v)
     return -1;
 }
 
+// the float twin of build_nn2d_i8: constants uploaded as they are ([out_c][kh][kw * in_c] is the filter tensor's own order), finite weights required (a
+// zero-padded tap multiplies its weight by 0 where the reference skips it: h_first_non_finite)
+static EI_IMPULSE_ERROR build_nn2d_f32(kws_handle *h, size_t &i, int &cur)
+{
+    const Model &m = h->model;
+    KwsNn2dPlanF32 &P = h->nn2df;
+    memset(&P, 0, sizeof(P));
+    std::vector<H2dBlock> blocks;
+    if (EI_IMPULSE_ERROR e = h_nn2d_walk(m, i, cur, true, blocks)) return e;
+    P.n_features = (int)m.nn_input_frame_size;
+    if (blocks[0].g.in_h * blocks[0].g.in_w * blocks[0].g.in_c != P.n_features)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "first conv does not consume the feature vector");
+    auto floats = [](const Tensor &t) { return std::vector<float>((const float *)t.data.data(), (const float *)t.data.data() + t.data.size() / 4); };
+    for (size_t b = 0; b < blocks.size(); b++) {
+        const H2dBlock &B = blocks[b];
+        const Node &cv = *B.cv;
+        const Tensor &w = m.t[cv.in[1]];
+        const Tensor *bias = (cv.in.size() > 2 && cv.in[2] >= 0) ? &m.t[cv.in[2]] : nullptr;
+        KwsConv2dBlockF32 &k = P.blk[b];
+        k.g = B.g;
+        const KwsConv2dGeom &g = k.g;
+        h_act_range_f32(B.act, &k.conv_min, &k.conv_max);
+        h_act_range_f32(B.pool_act, &k.pool_min, &k.pool_max);
+        std::vector<float> wv = floats(w), bv((size_t)g.out_c, 0.0f);
+        if (wv.size() != (size_t)g.out_c * g.kh * g.krow) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv block %zu: filter size", b);
+        if (const long bad = h_first_non_finite(wv); bad >= 0)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv block %zu: weight tensor %d holds a non-finite value (element %ld): the float kernels need finite weights", b,
+                        cv.in[1], bad);
+        if (bias) { bv = floats(*bias); if (bv.size() != (size_t)g.out_c) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv block %zu: bias size", b); }
+        EI_IMPULSE_ERROR e;
+        if ((e = h->upload(wv, &k.w))) return e;
+        if ((e = h->upload(bv, &k.bias))) return e;
+        P.n_blocks++;
+    }
+    const KwsConv2dGeom &lg = P.blk[P.n_blocks - 1].g;
+    P.out_n = lg.pool_h * lg.pool_w * lg.out_c;
+    if (kws_nn2d_f32_waves(P) == 0)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "float 2-D model needs %zu B of LDS at %d waves per workgroup (at most %d): its images do not fit the kernel's LDS budget",
+                    kws_nn2d_f32_smem_bytes(P, KWS_NN2D_WAVES_MIN), KWS_NN2D_WAVES_MIN, 150 * 1024);
+    h->n_conv2d = P.n_blocks;
+    return EI_IMPULSE_OK;
+}
+
 static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
 {
     const Model &m = h->model;
@@ -660,6 +931,13 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
     };
     auto floats = [](const Tensor &t) { return std::vector<float>((const float *)t.data.data(), (const float *)t.data.data() + t.nbytes / 4); };
     skip_reshapes();
+    // a 2-D graph: its blocks in a plan of their own (this one keeps n_blocks = 0), then the dense stack -- always, a single FULLY_CONNECTED included
+    int inputs2d = 0;
+    if (h_is_2d(m, i, cur)) {
+        if (EI_IMPULSE_ERROR e = build_nn2d_f32(h, i, cur)) return e;
+        if (i >= m.n.size() || m.n[i].op != OP_FULLY_CONNECTED) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected FULLY_CONNECTED after the conv blocks");
+        inputs2d = h->nn2df.out_n;
+    }
     while (i < m.n.size() && (m.n[i].op == OP_CONV_2D || m.n[i].op == OP_DEPTHWISE_CONV_2D)) {
         if (N.n_blocks >= KWS_MAX_BLOCKS) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "more than %d conv blocks", KWS_MAX_BLOCKS);
         const Node &cv = m.n[i];
@@ -749,7 +1027,7 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
         KwsDensePlanF32 &D = h->densef;
         memset(&D, 0, sizeof(D));
         D.n_labels = N.n_labels;
-        const int inputs = N.n_blocks ? N.blk[N.n_blocks - 1].pool_w * N.blk[N.n_blocks - 1].out_c : N.n_features;
+        const int inputs = inputs2d ? inputs2d : N.n_blocks ? N.blk[N.n_blocks - 1].pool_w * N.blk[N.n_blocks - 1].out_c : N.n_features;
         int k_in = inputs;
         while (i < m.n.size() && m.n[i].op == OP_FULLY_CONNECTED) {
             const int li = D.n_layers;
@@ -795,6 +1073,7 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
         N.fc_in = inputs; N.fc_out = 0;                  // the trunk form of kws_nn_f32_kernel sizes its output vector by fc_in; it has no head
         N.dense = &D; N.handoff = &h->handoff;
         handoff_init(h, sizeof(float) * (size_t)inputs);
+        if (inputs2d) h->handoff.trunk2d_f32 = &h->nn2df;
         h->n_dense = D.n_layers;
         if (N.n_blocks > 0 && kws_nn_f32_smem_bytes(N, 4) > 150 * 1024) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "float model too large for the kernel's LDS budget");
         void *d = nullptr;

@@ -202,6 +202,51 @@ static inline int kws_nnf_strided(const KwsNnPlanF32 &N)
         if (N.blk[b].stride != 1 || N.blk[b].dilation != 1) return 1;
     return 0;
 }
+// ---- 2-D convolutional graphs: CONV_2D (KH x KW, both spatial axes live) [-> MAX_POOL_2D] blocks in front of a dense stack.  Plans of
+//      their own -- the structs above are taken by value by the 1-D kernels and keep their layout -- read by kws_nn2d_trunk_kernel (kws_nn2d_int8.hip) /
+//      kws_nn2d_f32_trunk_kernel (kws_nn2d_f32.hip) alone.  The graph's KwsNnPlan / KwsNnPlanF32 has n_blocks = 0 and its dense stack; the trunk is
+//      reached through the hand-off (KwsHandoff::trunk2d / trunk2d_f32): the trunk is what fills those buffers.
+#define KWS_NN2D_K_MAX 7                   // filter and pool window, per axis
+#define KWS_NN2D_STRIDE_MAX 4              // convolution stride, per axis (pool strides: up to KWS_NN2D_K_MAX)
+#define KWS_NN2D_DIM_MAX 1024              // image height / width (bounds every product of the geometry far inside an int)
+struct KwsConv2dGeom {
+    int in_h, in_w, in_c, out_c;
+    int kh, kw, sh, sw, pad_t, pad_l;      // filter, stride, SAME padding above / left of the image (kernels/padding.h)
+    int out_h, out_w;                      // conv output
+    int ph, pw, psh, psw, ppt, ppl;        // pool window, stride, padding above / left (no pooling node: 1, 1, 1, 1, 0, 0)
+    int pool_h, pool_w;                    // pooled output (= out_h, out_w without a pooling node)
+    int has_pool;                          // a MAX_POOL_2D follows (float: a window of one value still goes through std::max and the pool's clamp)
+    int img_rows, img_cols;                // the padded input image in LDS: rows x columns (pixels) -- what the furthest tap of the furthest output reads
+    int img_pitch;                         // elements (bytes / floats) per image row: img_cols * in_c rounded up to an ODD number of dwords, so that the rows a
+                                           // wave's lanes read at once start on different LDS banks
+    int krow, krow4;                       // operands of one filter row: kw * in_c, and rounded up to a multiple of 4 (int8: dot4 words; zero weights)
+};
+struct KwsConv2dBlock {
+    KwsConv2dGeom g;
+    int in_zp, out_zp, act_min, act_max;
+    int w_bytes;
+    const int8_t *w;                       // [out_c][kh][krow4], zero padded
+    const int32_t *bias_eff;               // [out_c] bias + input_offset * sum(w)
+    const int32_t *mult, *shift;           // [out_c]
+};
+struct KwsNn2dPlan {
+    int n_blocks, n_features, out_n;       // out_n: the last block's pooled output, flattened NHWC (= the dense stack's inputs)
+    int tap_bytes;                         // of every block's pooled output, one after another (the conv blocks' share of tap_pooled)
+    KwsConv2dBlock blk[KWS_MAX_BLOCKS];
+};
+struct KwsConv2dBlockF32 {
+    KwsConv2dGeom g;
+    float conv_min, conv_max, pool_min, pool_max;
+    const float *w;                        // [out_c][kh][krow] (the filter tensor as it is)
+    const float *bias;                     // [out_c] (zeros where the node has none: the reference adds 0.0f)
+};
+struct KwsNn2dPlanF32 {
+    int n_blocks, n_features, out_n;
+    KwsConv2dBlockF32 blk[KWS_MAX_BLOCKS];
+};
+// bytes of image b's LDS buffer: the padded image plus 16 bytes the last filter row's zero-weight tail may read (int8), rounded to 16
+__host__ __device__ static inline int kws_nn2d_img_bytes(const KwsConv2dGeom &g, int elem) { return (g.img_rows * g.img_pitch * elem + 16 + 15) & ~15; }
+
 // the trunk's output [clips][inputs] for one chunk of clips, per stream (launches on different streams may overlap); allocated on first use, freed with
 // the handle
 #define KWS_HANDOFF_SETS 8
@@ -210,5 +255,8 @@ struct KwsHandoff {
     struct { void *stream; void *buf; int used; } set[KWS_HANDOFF_SETS];
     int next;
     size_t bytes;              // of every buffer: KWS_HANDOFF_BYTES (the development build reads KWS_DEV_HANDOFF_BYTES at kws_create: tests that walk several chunks)
+    // a 2-D graph: the trunk that fills the buffers (host plans owned by the handle), else NULL
+    const KwsNn2dPlan *trunk2d;
+    const KwsNn2dPlanF32 *trunk2d_f32;
 };
 void *kws_handoff_for(KwsHandoff *H, void *stream);      // kws_plan.cpp; NULL when the allocation fails

@@ -63,8 +63,22 @@ int kws_dense_layer_count(const kws_handle *h);          /* FULLY_CONNECTED laye
  * dilation > 1 (the reference computes that padding with dilation 1, depthwise_conv.cc:489-492, so its result is shifted); an output tensor of another width; a
  * padded input image past the kernels' LDS budget.  A graph with a strided or dilated block runs in KWS_MODE_EXACT only: kws_set_mode(h, KWS_MODE_FAST) returns
  * KWS_ERROR_UNSUPPORTED_MODEL and the handle goes on serving KWS_MODE_EXACT. */
+/* 2-D convolutional graphs (Edge Impulse's "2D Convolutional" classifier): the tensor flowing into the first convolution is [1][H][W][C] with H > 1
+ * and W > 1 (H: frames, W: cepstral / mel columns, Keras' Reshape((frames, columns, 1))).  1 .. 8 blocks, each CONV_2D (filter KH x KW with 1 <= KH, KW <= 7,
+ * stride 1 .. 4 per axis, dilation 1, SAME or VALID, constant bias or none, fused activation 0 .. 3, at most 64 channels in and out, int8 per-channel or per-tensor
+ * weights, or float32) optionally followed by MAX_POOL_2D (window and stride 1 .. 7 per axis, SAME or VALID); then a flatten, 1 .. 4 FULLY_CONNECTED within the
+ * dense-stack limits above (at most 4096 inputs: a graph whose last block leaves more than that is refused; the stock two-block graph leaves 13 x 4 x 16 = 832 on 49 x 13 features and 13 x 10 x 16 = 2080 on 49 x 40) and SOFTMAX.  Such a graph ALWAYS ends
+ * in the dense stack's kernels, a single FULLY_CONNECTED included, so the hand-off buffers and their stream rules above apply.  Refused with
+ * KWS_ERROR_UNSUPPORTED_MODEL (kws_last_error names the node and the reason): DEPTHWISE_CONV_2D or a per-channel ADD inside such a graph, dilation other than 1, a
+ * filter, stride or pool outside the bounds, an output tensor whose dims disagree with kernels/padding.h, an image that does not fit the kernels' LDS budget at four
+ * waves per workgroup, non-finite float weights, an int8 MAX_POOL_2D with a fused activation, and left-shifting requantisation past the bound of the 1-D blocks.
+ * KWS_MODE_EXACT only: kws_set_mode(h, KWS_MODE_FAST) returns KWS_ERROR_UNSUPPORTED_MODEL and the handle goes on serving KWS_MODE_EXACT.  No matrix-core
+ * kernel serves the blocks: the trunk runs on v_dot4 (int8) / in-order float chains.  tap_pooled of kws_nn_batch_device holds every block's (pooled) output in NHWC
+ * order, one after another, then the hidden dense outputs; kws_pooled_tap_bytes says how many. */
+int kws_conv2d_block_count(const kws_handle *h);         /* CONV_2D blocks of a 2-D graph; 0 for every other graph */
 const char *kws_nn_kernel_name(const kws_handle *h);    /* which network kernel serves this model (diagnostics); "kws_nn_sd_kernel" / "kws_nn_f32_sd_kernel" (in front of a
-                                                            dense stack: "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel", float32 likewise) for a graph with a strided or dilated block.
+                                                            dense stack: "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel", float32 likewise) for a graph with a strided or dilated block;
+                                                            "kws_nn2d_trunk_kernel + kws_dense_i8_kernel" / "kws_nn2d_f32_trunk_kernel + kws_dense_f32_kernel" for a 2-D graph.
                                                             The strings are LABELS of the kernels' forms, stable across releases, not device symbols: the generic kernels are
                                                             templates (kws_nn_kernel<MAXW, TRUNK, SD>, kws_nn_f32_kernel<MAXT, TRUNK, SD>) and a profiler shows their instantiations */
 const char *kws_mfcc_kernel_name(const kws_handle *h);  /* the spectral kernel of int16 batches, MFCC and MFE blocks alike: "kws_mfcc8_kernel" / "kws_mfcc_kernel" (tuned shapes), "kws_mfcc8_kernel (chunked)" (general plans whose spectral stage fits the tuned kernel: chunks of at most 49 frames), "kws_spectral_lds_kernel" (general shapes), "kws_spectral_generic_kernel" (those whose arrays exceed the LDS) */

@@ -52,6 +52,17 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
         g = v[:, np.clip(idx, 0, w - 1), :]
         return g, ok
 
+    def out_pad(size, k, stride, padding):             # kernels/padding.h: (output size, padding in front); a negative total is 0
+        out = (size + stride - 1) // stride if padding == 1 else (size - k) // stride + 1
+        return out, max(0, (out - 1) * stride + k - size) // 2
+
+    def padded2d(v, kh, kw, sh, sw, padding, fill):    # [n][H][W][C] behind its padding, large enough for every window of every output
+        n, hh, ww, c = v.shape
+        (oh, pt), (ow, pl) = out_pad(hh, kh, sh, padding), out_pad(ww, kw, sw, padding)
+        ap = np.full((n, max(pt + hh, (oh - 1) * sh + kh), max(pl + ww, (ow - 1) * sw + kw), c), fill, np.float64)
+        ap[:, pt:pt + hh, pl:pl + ww] = v
+        return ap, oh, ow
+
     for nd in nodes:
         if nd["op"] == stop_before_op:
             break
@@ -61,7 +72,28 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
         a = act.get(nd["in"][0])
         if nd["op"] == 0:                               # RESHAPE
             n = a.shape[0]
-            act[o] = a.reshape(n, -1) if len(dims) == 2 else a.reshape(n, -1, dims[-1])
+            if len(dims) == 4 and dims[1] > 1 and dims[2] > 1:          # a 2-D image [n][H][W][C] (blocks2d=)
+                act[o] = a.reshape(n, dims[1], dims[2], dims[3])
+            else:
+                act[o] = a.reshape(n, -1) if len(dims) == 2 else a.reshape(n, -1, dims[-1])
+        elif nd["op"] == 1 and a.ndim == 4:             # CONV_2D over both axes: filter [O][KH][KW][C], stride (p[2], p[1]), no dilation
+            w = const[nd["in"][1]]
+            b = const[nd["in"][2]] if len(nd["in"]) > 2 and nd["in"][2] >= 0 else 0.0
+            kh, kw, sh, sw = w.shape[1], w.shape[2], p[2], p[1]
+            ap, oh, ow = padded2d(a, kh, kw, sh, sw, p[0], 0.0)
+            v = np.zeros((a.shape[0], oh, ow, w.shape[0]))
+            for fy in range(kh):
+                for fx in range(kw):
+                    v += np.einsum("nhwc,oc->nhwo", ap[:, fy:fy + (oh - 1) * sh + 1:sh, fx:fx + (ow - 1) * sw + 1:sw], w[:, fy, fx])
+            act[o] = fused(v + b, p[3])
+        elif nd["op"] == 3 and a.ndim == 4:             # MAX_POOL_2D over both axes: window (p[4], p[3]), stride (p[2], p[1])
+            ph, pw, sh, sw = p[4], p[3], p[2], p[1]
+            ap, oh, ow = padded2d(a, ph, pw, sh, sw, p[0], -np.inf)
+            v = np.full((a.shape[0], oh, ow, a.shape[3]), -np.inf)
+            for fy in range(ph):
+                for fx in range(pw):
+                    v = np.maximum(v, ap[:, fy:fy + (oh - 1) * sh + 1:sh, fx:fx + (ow - 1) * sw + 1:sw])
+            act[o] = fused(v, p[5])
         elif nd["op"] in (1, 6):                        # CONV_2D / DEPTHWISE_CONV_2D, 1 x K, stride p[1] and dilation p[4] along time
             w = const[nd["in"][1]]
             b = const[nd["in"][2]]
@@ -187,7 +219,7 @@ def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=2
 def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((30, 7, 7), (10, 7, 7)), n_labels=4,
                      conv_bias=False, add_bias=True, num_filters=32, raw_samples=16000, fft_length=256, frame_length=0.02,
                      frame_stride=0.02, pre_cof=0.98, dsp_block="mfcc", logit_std=None, quantize_filterbank=False, edit=None, dense=None,
-                     calib=None, conv_valid=(), conv_stride=None, conv_dilation=None):
+                     calib=None, conv_valid=(), conv_stride=None, conv_dilation=None, blocks2d=None):
     """blocks: sequence of
          (out_channels, taps, pool)              CONV_2D 1xK (+ optional int32 bias) -> ADD(int8 per-channel)+ReLU -> MAX_POOL
          ("dw", depth_mult, taps, pool, act)     DEPTHWISE_CONV_2D 1xK with int32 bias and fused activation -> MAX_POOL
@@ -210,6 +242,11 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
        bias, fused activation act) between the flattened output of the last block and the head.  A graph with hidden layers is always calibrated
        (calibrate_hidden, then calibrate_head with logit_std or 1.5) on standardised random feature matrices, or on calib ([n][features]) where the
        DSP block's output is not of that kind (the MFE block's).  With dense=None every blob is the one the same arguments gave before.
+       blocks2d: None, or the blocks of a 2-D convolutional graph (Edge Impulse's "2D Convolutional" classifier), which then REPLACE blocks: the features are
+       reshaped to [1][frames][columns][1] and every block is (out_channels, kh, kw, pool) or (out_channels, kh, kw, pool, options) -- a CONV_2D kh x kw with
+       int32 bias and fused ReLU, then MAX_POOL_2D pool x pool at stride pool, SAME padding (pool 0 / 1: no pooling node).  options (a dict): stride=(h, w),
+       valid=True (VALID convolution), act=0 .. 3, bias=False (no bias tensor), pool=(h, w) window, pool_stride=(h, w), pool_valid=True.  A flatten, dense=,
+       the head and softmax follow as ever.  It draws nothing when blocks2d is None: every blob is the one the same arguments gave before.
        edit: a callable edit(tensors, nodes) run on the finished graph just before it is serialised -- the way to any quantisation
        parameter, constant or node option outside the drawn bands (tests/kws_testlib.py QUANT_EDGES).  It draws nothing from the
        model's generator: with edit=None every blob is the one the same arguments gave before."""
@@ -245,9 +282,48 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
     in_scale, in_zp = rscale(0.03, 0.06), int(rng.integers(-20, 5))
     t_in = T(9, [1, F], scale=[in_scale], zero=[in_zp])
     cur, cur_scale, cur_zp, w, c = t_in, in_scale, in_zp, n_frames, ncep
-    t = T(9, [1, 1, w, c], scale=[cur_scale], zero=[cur_zp])
-    node(0, [cur, shape_const([1, 1, w, c])], [t])
-    cur = t
+    if blocks2d is not None:
+        blocks = ()
+        hh, w, c = n_frames, ncep, 1
+        t = T(9, [1, hh, w, 1], scale=[cur_scale], zero=[cur_zp])
+        node(0, [cur, shape_const([1, hh, w, 1])], [t])
+        cur = t
+        for blk in blocks2d:
+            oc, kh, kw, pool = blk[:4]
+            opt = dict(blk[4]) if len(blk) > 4 else {}
+            (sh, sw), valid, act = opt.get("stride", (1, 1)), bool(opt.get("valid", False)), opt.get("act", 1)
+            wq = rng.integers(-127, 128, (oc, kh, kw, c)).astype(np.int8)
+            wscales = [rscale(0.001, 0.005) for _ in range(oc)]
+            tw = T(9, [oc, kh, kw, c], True, wscales, [0] * oc, wq.tobytes())
+            ins = [cur, tw]
+            if opt.get("bias", True):
+                bias = rng.integers(-300, 300, oc).astype(np.int32)
+                ins.append(T(2, [oc], True, [cur_scale * s_ for s_ in wscales], [0] * oc, bias.tobytes()))
+            out_scale, out_zp = rscale(0.03, 0.12), int(rng.integers(-128, -90)) if act in (1, 3) else int(rng.integers(-30, 40))
+            if valid:                                                   # ComputeOutSize (kernels/padding.h)
+                assert hh >= kh and w >= kw
+                hh, w = (hh - kh) // sh + 1, (w - kw) // sw + 1
+            else:
+                hh, w = (hh + sh - 1) // sh, (w + sw - 1) // sw
+            tc = T(9, [1, hh, w, oc], scale=[out_scale], zero=[out_zp])
+            node(1, ins, [tc], [2 if valid else 1, sw, sh, act, 1, 1])
+            cur, cur_scale, cur_zp, c = tc, out_scale, out_zp, oc
+            ph, pw = opt.get("pool", (pool, pool) if pool > 1 else (1, 1))
+            psh, psw = opt.get("pool_stride", (ph, pw))
+            if (ph, pw) != (1, 1) or (psh, psw) != (1, 1):
+                if opt.get("pool_valid", False):
+                    assert hh >= ph and w >= pw
+                    hh, w, pad = (hh - ph) // psh + 1, (w - pw) // psw + 1, 2
+                else:
+                    hh, w, pad = (hh + psh - 1) // psh, (w + psw - 1) // psw, 1
+                tp = T(9, [1, hh, w, oc], scale=[cur_scale], zero=[cur_zp])
+                node(3, [cur], [tp], [pad, psw, psh, pw, ph, 0])
+                cur = tp
+        w = hh * w                                                      # the flatten below: NHWC order
+    else:
+        t = T(9, [1, 1, w, c], scale=[cur_scale], zero=[cur_zp])
+        node(0, [cur, shape_const([1, 1, w, c])], [t])
+        cur = t
     def add_pool(pool):
         nonlocal cur, w
         if pool in (0, 1):
@@ -396,10 +472,20 @@ def main():
     ap.add_argument("--conv-stride", default="", help="strided convolutions: block:stride;block:stride (block: index into --blocks)")
     ap.add_argument("--conv-dilation", default="", help="dilated convolutions: block:dilation;block:dilation")
     ap.add_argument("--conv-valid", default="", help="convolutions with VALID padding: block;block")
+    ap.add_argument("--blocks2d", default="", help="a 2-D convolutional graph instead of --blocks: out_channels,kh,kw,pool per block, e.g. \"8,3,3,2;16,3,3,2\"; "
+                    "options after a colon, k=v pairs: stride=HxW valid=1 act=N bias=0 pool=HxW pool_stride=HxW pool_valid=1")
     a = ap.parse_args()
     blocks = tuple(tuple(v if v in ("dw", "pw") else int(v) for v in b.split(",")) for b in a.blocks.split(";") if b)      # --blocks "": dense only
     dense = tuple(tuple(int(v) for v in d.split(",")) for d in a.dense.split(";") if d) or None
-    blob = synth_model_blob(a.seed, ncep=a.ncep, win_size=a.win_size, low=a.low, high=a.high, blocks=blocks,
+    def block2d(text):
+        head, _, tail = text.partition(":")
+        opt = {}
+        for kv in tail.split():
+            k, v = kv.split("=")
+            opt[k] = tuple(int(x) for x in v.split("x")) if k in ("stride", "pool", "pool_stride") else bool(int(v)) if k in ("valid", "bias", "pool_valid") else int(v)
+        return tuple(int(v) for v in head.split(",")) + ((opt,) if opt else ())
+    blocks2d = tuple(block2d(b) for b in a.blocks2d.split(";") if b) or None
+    blob = synth_model_blob(a.seed, blocks2d=blocks2d, ncep=a.ncep, win_size=a.win_size, low=a.low, high=a.high, blocks=blocks,
                             n_labels=a.labels, num_filters=a.num_filters, logit_std=a.logit_std, dense=dense,
                             conv_valid=tuple(int(v) for v in a.conv_valid.split(";") if v),
                             conv_stride={int(v.split(":")[0]): int(v.split(":")[1]) for v in a.conv_stride.split(";") if v} or None,
