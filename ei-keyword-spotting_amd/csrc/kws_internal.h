@@ -18,6 +18,7 @@
 #include "../../include/kws/kws.h"
 #include "kws_plan.h"
 #include "kws_nn2d.h"
+#include "kws_nnres.h"
 #include "kws_fast.h"
 
 // launchers in kws_mfcc.hip, kws_nn_int8.hip, kws_nn_f32.hip, kws_misc.hip
@@ -184,6 +185,10 @@ struct kws_handle {
     KwsNn2dPlan nn2d{};
     KwsNn2dPlanF32 nn2df{};
     int n_conv2d = 0;
+    // residual graphs: the trunk's plan (handoff.trunkres / trunkres_f32 point to it; nn / nnf then hold no block) and its tensor + tensor ADD count
+    KwsResPlan nnres{};
+    KwsResPlanF32 nnresf{};
+    int n_res_adds = 0;
     std::vector<void *> dev_allocs;
     // kws_spectral_lds_kernel's frames per chunk, measured per handle on its own first large calls (kws_api.cpp generic_chunk_begin / _end)
     struct GenericTune { int choice = 0, phase = 0, armed = 0; size_t clips = 0; hipEvent_t ev[2] = { nullptr, nullptr }; double ms_per_clip[2] = { 0.0, 0.0 };

@@ -4,6 +4,7 @@
 
 #include "kws_device.h"
 #include "kws_nn2d.h"
+#include "kws_nnres.h"
 
 // ---------------------------------------------------------------------------------------------------------
 //  Kernel 2f: float32 models.  One wave per clip.  Every accumulation replays the reference's sequential
@@ -539,19 +540,21 @@ static int launch_dense_f32(const KwsNnPlanF32 &N, const KwsNnPlanF32 *d_plan, c
     }
     auto dense_grid = [&](int n) { const int g = (n + 63) / 64; return g > n_cu * 8 ? n_cu * 8 : g; };
     const KwsNn2dPlanF32 *const trunk2d = N.handoff->trunk2d_f32;     // a 2-D graph: kws_nn2d_f32_trunk_kernel fills the hand-off
-    if (N.n_blocks == 0 && !trunk2d) {
+    const KwsResPlanF32 *const trunkres = N.handoff->trunkres_f32;   // a residual graph: kws_nnres_f32_trunk_kernel fills the hand-off
+    if (N.n_blocks == 0 && !trunk2d && !trunkres) {
         hipLaunchKernelGGL(kws_dense_f32_kernel, dim3(dense_grid(n_clips)), dim3(KWS_WAVE * KWS_DENSEF_WAVES), dsmem, stream, D, features, 1, 0, n_clips, n_clips,
                            scores, tap_logits, sel);
         return (int)hipGetLastError();
     }
     float *ho = (float *)kws_handoff_for(N.handoff, (void *)stream);
     if (!ho) return (int)hipErrorOutOfMemory;
-    if (trunk2d) {
-        if (!kws_launch_nn2d_f32_trunk) return (int)hipErrorInvalidDeviceFunction;      // (linked without kws_nn2d_f32.hip: kws_nn2d.h)
+    if (trunk2d || trunkres) {
+        if (trunk2d ? !kws_launch_nn2d_f32_trunk : !kws_launch_nnres_f32_trunk) return (int)hipErrorInvalidDeviceFunction;      // (linked without the trunk's unit: kws_nn2d.h, kws_nnres.h)
         const int chunk = (int)(N.handoff->bytes / (sizeof(float) * (size_t)N.fc_in));
         for (int c0 = 0; c0 < n_clips; c0 += chunk) {
             const int c1 = n_clips - c0 > chunk ? c0 + chunk : n_clips;
-            int rc = kws_launch_nn2d_f32_trunk(*trunk2d, features, n_clips, ho, c0, c1, sel, n_cu, stream);
+            int rc = trunk2d ? kws_launch_nn2d_f32_trunk(*trunk2d, features, n_clips, ho, c0, c1, sel, n_cu, stream)
+                             : kws_launch_nnres_f32_trunk(*trunkres, features, n_clips, ho, c0, c1, sel, n_cu, stream);
             if (rc) return rc;
             hipLaunchKernelGGL(kws_dense_f32_kernel, dim3(dense_grid(c1 - c0)), dim3(KWS_WAVE * KWS_DENSEF_WAVES), dsmem, stream, D, (const float *)ho, 0, c0, c1, n_clips,
                                scores, tap_logits, sel);

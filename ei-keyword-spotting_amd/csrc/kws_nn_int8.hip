@@ -11,6 +11,7 @@
 
 #include "kws_dense_i8.h"
 #include "kws_nn2d.h"
+#include "kws_nnres.h"
 
 template <int CP>
 __global__ __launch_bounds__(KWS_WAVE * KWS_NN_WAVES) void kws_nn_mfma_kernel(KwsNnPlan N, const int8_t *__restrict__ q_in, int n_clips,
@@ -199,7 +200,8 @@ static int launch_dense_i8(const KwsNnPlan &N, const int8_t *q_in, int n_clips, 
     }
     auto dense_grid = [&](int n) { const int g = (n + 16 * KWS_DENSE_WAVES - 1) / (16 * KWS_DENSE_WAVES); return g > grid_cap ? grid_cap : g; };
     const KwsNn2dPlan *const trunk2d = N.handoff->trunk2d;     // a 2-D graph: kws_nn2d_trunk_kernel fills the hand-off
-    if (N.n_blocks == 0 && !trunk2d) {
+    const KwsResPlan *const trunkres = N.handoff->trunkres;     // a residual graph: kws_nnres_trunk_kernel fills the hand-off
+    if (N.n_blocks == 0 && !trunk2d && !trunkres) {
         hipLaunchKernelGGL(kws_dense_i8_kernel, dim3(dense_grid(n_clips)), dim3(KWS_WAVE * KWS_DENSE_WAVES), smem, stream, D, q_in, 1, 0, n_clips, n_clips, scores, taps);
         return (int)hipGetLastError();
     }
@@ -209,7 +211,7 @@ static int launch_dense_i8(const KwsNnPlan &N, const int8_t *q_in, int n_clips, 
     while (nw > KWS_NN_WAVES && kws_nn_smem_bytes(N, nw) > 158 * 1024) --nw;
     const size_t tsmem = kws_nn_smem_bytes(N, nw);
     const void *fn = nn_kernel_for(true, kws_nn_strided(N) != 0, nw);
-    if (!trunk2d && tsmem > 64 * 1024) {
+    if (!trunk2d && !trunkres && tsmem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tsmem);
         if (e != hipSuccess) return (int)e;
     }
@@ -221,6 +223,10 @@ static int launch_dense_i8(const KwsNnPlan &N, const int8_t *q_in, int n_clips, 
         if (trunk2d) {
             if (!kws_launch_nn2d_trunk) return (int)hipErrorInvalidDeviceFunction;      // (linked without kws_nn2d_int8.hip: kws_nn2d.h)
             const int rc = kws_launch_nn2d_trunk(*trunk2d, q_in, n_clips, ho, c0, c1, taps.pooled, taps.pooled_stride, taps.sel, grid_cap / 4, stream);
+            if (rc) return rc;
+        } else if (trunkres) {
+            if (!kws_launch_nnres_trunk) return (int)hipErrorInvalidDeviceFunction;     // (linked without kws_nnres_int8.hip: kws_nnres.h)
+            const int rc = kws_launch_nnres_trunk(*trunkres, q_in, n_clips, ho, c0, c1, taps.pooled, taps.pooled_stride, taps.sel, grid_cap / 4, stream);
             if (rc) return rc;
         } else nn_launch(fn, grid, nw, tsmem, stream, N, q_in, n_clips, nullptr, ho, c0, c1, taps);
         hipLaunchKernelGGL(kws_dense_i8_kernel, dim3(dense_grid(n)), dim3(KWS_WAVE * KWS_DENSE_WAVES), smem, stream, D, (const int8_t *)ho, 0, c0, c1, n_clips, scores, taps);

@@ -595,6 +595,10 @@ static EI_IMPULSE_ERROR build_nn2d_i8(kws_handle *h, size_t &i, int &cur)
     return EI_IMPULSE_OK;
 }
 
+// residual graphs (below, behind the float helpers)
+static bool h_is_residual(const Model &m);
+static EI_IMPULSE_ERROR build_nnres_i8(kws_handle *h, size_t &i, int &cur);
+
 // Recognise the Edge Impulse 1-D CNN family and fold its per-model constants.
 EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
 {
@@ -624,6 +628,13 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         }
         return true;
     };
+    if (h_is_residual(m)) {
+        // a residual graph: its steps in a plan of their own, then the dense stack -- always, as for a 2-D graph
+        if (EI_IMPULSE_ERROR e = build_nnres_i8(h, i, cur)) return e;
+        if (EI_IMPULSE_ERROR e = build_dense_i8(h, i, cur, h->nnres.out_n)) return e;
+        h->handoff.trunkres = &h->nnres;
+        return EI_IMPULSE_OK;
+    }
     if (!skip_reshapes()) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "reshape changes quantisation");
     if (h_is_2d(m, i, cur)) {
         // a 2-D graph: its blocks in a plan of their own, then the dense stack -- always, a single FULLY_CONNECTED included
@@ -909,6 +920,455 @@ static EI_IMPULSE_ERROR build_nn2d_f32(kws_handle *h, size_t &i, int &cur)
     return EI_IMPULSE_OK;
 }
 
+// ---- residual graphs ------------------------------------------------------------------------------------------------------------------
+// A graph is residual when at least one ADD has two non-constant inputs; every other graph takes the path it always took.
+static bool h_is_residual(const Model &m)
+{
+    for (const Node &nd : m.n)
+        if (nd.op == OP_ADD && !m.t[nd.in[0]].is_const && !m.t[nd.in[1]].is_const) return true;
+    return false;
+}
+
+// LDS of the residual trunks at n_waves waves per workgroup, laid out as kws_nnres_trunk_kernel / kws_nnres_f32_trunk_kernel walk it -- per workgroup every
+// step's constants, per wave the KWS_RES_SLOTS image slots -- and the wave count their launchers pick (kws_nnres.h)
+size_t kws_nnres_smem_bytes(const KwsResPlan &N, int n_waves)
+{
+    size_t s = 0;
+    for (int k = 0; k < N.n_steps; ++k)
+        s += N.st[k].g.kind == KWS_RES_CONV ? (((size_t)N.st[k].w_bytes + 15) & ~(size_t)15) + (size_t)N.st[k].g.out_c * 16 : (size_t)KWS_NNRES_ADD_TAB_BYTES;
+    return s + (size_t)n_waves * (size_t)N.wave_bytes;
+}
+int kws_nnres_waves(const KwsResPlan &N)
+{
+    for (int nw = KWS_NNRES_WAVES_MAX; nw >= KWS_NNRES_WAVES_MIN; --nw)
+        if (kws_nnres_smem_bytes(N, nw) <= KWS_NNRES_LDS_I8) return nw;
+    return 0;
+}
+size_t kws_nnres_f32_smem_bytes(const KwsResPlanF32 &N, int n_waves)
+{
+    size_t s = 0;
+    for (int k = 0; k < N.n_steps; ++k) {
+        const KwsResGeom &g = N.st[k].g;
+        if (g.kind != KWS_RES_CONV) continue;
+        s += sizeof(float) * (size_t)((N.st[k].w_lds ? (g.out_c * g.kh * g.krow + 3) & ~3 : 0) + ((g.out_c + 3) & ~3));
+    }
+    return s + (size_t)n_waves * (size_t)N.wave_bytes;
+}
+int kws_nnres_f32_waves(const KwsResPlanF32 &N)
+{
+    for (int nw = KWS_NNRES_WAVES_MAX; nw >= KWS_NNRES_WAVES_MIN; --nw)
+        if (kws_nnres_f32_smem_bytes(N, nw) <= KWS_NNRES_LDS_F32) return nw;
+    return 0;
+}
+
+// one tensor's image: its dims as its convolutions see them, who makes and who last reads it, the margin and extent its consumers need, its slot
+struct HResImage {
+    int h = 0, w = 0, c = 0, tid = -1;     // tid: a model tensor that carries its quantisation
+    int producer = -1, last_use = -1, uses = 0;     // steps (-1: the reshaped input)
+    int mt = 0, ml = 0, ext_r = 0, ext_c = 0;       // margin above / left; rows / columns from the tensor's (0, 0) the furthest tap of any consumer reads
+    int slot = -1, rows = 0, pitch = 0, bytes = 0, base = 0;
+};
+struct HResStep { KwsResGeom g; const Node *nd; int a, b, dst, x_id, y_id, act, pool_act, pad_t, pad_l; };
+struct HResGraph { std::vector<HResImage> img; std::vector<HResStep> st; int final_img = -1, wave_bytes = 0, n_adds = 0; };
+
+// The steps of a residual graph: every node up to the first FULLY_CONNECTED, in node order.  RESHAPEs that keep the quantisation are renamings: a tensor id
+// maps to an image and to how its dims spell that image -- as they are ([1][H][W][C]), with H and W exchanged (one of them 1: the same bytes, what Keras'
+// Conv1D exports do around their pools), or otherwise (3-D, ...: only another RESHAPE may read it).  Everything comes from an untrusted blob: ids are
+// bounds-checked by the parser; here a node may read only the input, constants and outputs of EARLIER nodes, a tensor has one producer, and every dim,
+// filter side, stride and pool is bounded BEFORE any arithmetic on it (h_nn2d_walk's manner).  On return i stands at the first FULLY_CONNECTED and cur is
+// the flattened tensor it reads.
+static EI_IMPULSE_ERROR h_res_walk(const Model &m, size_t &i, int &cur, bool is_float, HResGraph &G)
+{
+    const uint32_t want = is_float ? TYPE_F32 : TYPE_I8;
+    const int elem = is_float ? 4 : 1;
+    enum { PLAIN = 0, SWAPPED = 1, OTHER = 2, FLAT_IN = 3 };
+    const int nt = (int)m.t.size();
+    std::vector<int> img_of(nt, -1), kind_of(nt, OTHER);       // img_of: -1 not produced yet, -2 consumed by a fused pool
+    std::vector<char> produced(nt, 0);
+    auto quant_ok = [&](int a) {
+        const Tensor &t = m.t[a];
+        if (t.type != want || t.is_const) return false;
+        return is_float || (!t.scale.empty() && !t.zero.empty() && t.zero[0] >= -128 && t.zero[0] <= 127);
+    };
+    auto same_quant = [&](int a, int b) { return is_float || (m.t[a].scale[0] == m.t[b].scale[0] && m.t[a].zero[0] == m.t[b].zero[0]); };
+    auto produce = [&](size_t node, int tid) -> EI_IMPULSE_ERROR {
+        if (produced[tid] || m.t[tid].is_const || tid == (int)m.t_in)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: tensor %d has a second producer (or is a constant / the input)", node, tid);
+        if (!quant_ok(tid)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: output tensor %d: type / quantisation", node, tid);
+        produced[tid] = 1;
+        return EI_IMPULSE_OK;
+    };
+    // how dims spell image g: PLAIN, SWAPPED, OTHER (same element count), or -1
+    auto spell = [&](const HResImage &g, const std::vector<int> &d) {
+        if (d.size() == 4 && d[0] == 1 && d[1] == g.h && d[2] == g.w && d[3] == g.c) return (int)PLAIN;
+        if (d.size() == 4 && d[0] == 1 && d[1] == g.w && d[2] == g.h && d[3] == g.c && (g.h == 1 || g.w == 1)) return (int)SWAPPED;
+        long n = 1;
+        for (int v : d) { if (v < 1 || v > (1 << 24)) return -1; n *= v; if (n > (1l << 28)) return -1; }
+        return n == (long)g.h * g.w * g.c ? (int)OTHER : -1;
+    };
+    auto readable = [&](size_t node, int tid, const char *what) -> EI_IMPULSE_ERROR {
+        if (img_of[tid] == -2)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: %s tensor %d is the input of a fused MAX_POOL_2D: a pool shares its input with another consumer", node, what, tid);
+        if (img_of[tid] < 0 || kind_of[tid] == FLAT_IN)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: %s tensor %d is no image an earlier node produced", node, what, tid);
+        return EI_IMPULSE_OK;
+    };
+    if (!quant_ok((int)m.t_in)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "input tensor type / quantisation");
+    produced[m.t_in] = 1; kind_of[m.t_in] = FLAT_IN; img_of[m.t_in] = -3;      // the feature vector: only RESHAPEs read it
+    int in_img = -1, flat = -1;
+    for (; i < m.n.size(); ++i) {
+        const Node &nd = m.n[i];
+        if (nd.op == OP_FULLY_CONNECTED) break;
+        if (flat >= 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: only FULLY_CONNECTED layers may follow the flattening RESHAPE", i);
+        const int x = nd.in[0], y = nd.out[0];
+        if (nd.op == OP_RESHAPE) {
+            if (!produced[x] || m.t[x].is_const) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: RESHAPE reads tensor %d, which no earlier node produced", i, x);
+            if (EI_IMPULSE_ERROR e = produce(i, y)) return e;
+            if (!same_quant(x, y)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "reshape changes quantisation");
+            const std::vector<int> &d = m.t[y].dims;
+            if (kind_of[x] == FLAT_IN) {
+                if (d.size() == 4 && d[0] == 1) {          // the reshaped input: the first image
+                    if (d[1] > KWS_NN2D_DIM_MAX || d[2] > KWS_NN2D_DIM_MAX || d[3] > 64 || (size_t)d[1] * d[2] * d[3] != m.nn_input_frame_size)
+                        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: the input RESHAPE to %d x %d x %d does not hold the %u features (image sides up to %d, 64 channels)",
+                                    i, d[1], d[2], d[3], m.nn_input_frame_size, KWS_NN2D_DIM_MAX);
+                    if (in_img >= 0) {
+                        const int k = spell(G.img[in_img], d);
+                        if (k != PLAIN && k != SWAPPED) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: a second shape of the input", i);
+                        img_of[y] = in_img; kind_of[y] = k;
+                        continue;
+                    }
+                    HResImage g;
+                    g.h = d[1]; g.w = d[2]; g.c = d[3]; g.tid = y; g.ext_r = g.h; g.ext_c = g.w;
+                    in_img = (int)G.img.size();
+                    G.img.push_back(g);
+                    img_of[y] = in_img; kind_of[y] = PLAIN;
+                } else { img_of[y] = -3; kind_of[y] = FLAT_IN; }
+                continue;
+            }
+            if (EI_IMPULSE_ERROR e = readable(i, x, "RESHAPE input")) return e;
+            const HResImage &g = G.img[img_of[x]];
+            const int k = spell(g, d);
+            if (k < 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: RESHAPE changes the element count", i);
+            img_of[y] = img_of[x]; kind_of[y] = k;
+            if (d.size() == 2 && d[0] == 1) { flat = y; G.final_img = img_of[x]; }       // the flatten
+            continue;
+        }
+        if ((int)G.st.size() >= KWS_RES_STEPS_MAX && nd.op != OP_MAX_POOL_2D)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: more than %d steps (CONV_2D / ADD) in a residual graph", i, KWS_RES_STEPS_MAX);
+        if (nd.op == OP_DEPTHWISE_CONV_2D)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: DEPTHWISE_CONV_2D inside a residual graph is not served (the family is CONV_2D, ADD and MAX_POOL_2D)", i);
+        if (nd.op == OP_CONV_2D) {
+            if (EI_IMPULSE_ERROR e = readable(i, x, "conv input")) return e;
+            if (kind_of[x] != PLAIN) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: its input is a renamed tensor (only MAX_POOL_2D and ADD read those)", i);
+            if (EI_IMPULSE_ERROR e = produce(i, y)) return e;
+            HResImage &src = G.img[img_of[x]];
+            const Tensor &w = m.t[nd.in[1]], &yt = m.t[y];
+            const Tensor *bias = (nd.in.size() > 2 && nd.in[2] >= 0) ? &m.t[nd.in[2]] : nullptr;
+            if (w.dims.size() != 4 || yt.dims.size() != 4 || yt.dims[0] != 1 || w.type != want)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: filter and output must be 4-D tensors of the graph's type, one batch", i);
+            HResStep S{};
+            KwsResGeom &g = S.g;
+            g.kind = KWS_RES_CONV;
+            g.in_c = src.c; g.out_c = w.dims[0]; g.kh = w.dims[1]; g.kw = w.dims[2];
+            if (g.out_c > 64 || g.kh > KWS_RES_K_MAX || g.kw > KWS_RES_K_MAX || w.dims[3] != g.in_c)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: a %d x %d filter over %d (filter: %d) -> %d channels is outside the residual kernels' limits (filter "
+                            "sides 1 .. %d, at most 64 channels)", i, g.kh, g.kw, g.in_c, w.dims[3], g.out_c, KWS_RES_K_MAX);
+            if (!w.is_const || (bias && (!bias->is_const || bias->type != (is_float ? TYPE_F32 : TYPE_I32) || (long)bias->nbytes != 4l * g.out_c)))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: the filter and the bias (%d values, %s) must be constants", i, g.out_c, is_float ? "float32" : "int32");
+            const int padding = nd.p[0];
+            g.sw = nd.p[1]; g.sh = nd.p[2]; S.act = nd.p[3];
+            if (g.sh < 1 || g.sh > KWS_NN2D_STRIDE_MAX || g.sw < 1 || g.sw > KWS_NN2D_STRIDE_MAX)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: stride %d x %d is outside 1 .. %d", i, g.sh, g.sw, KWS_NN2D_STRIDE_MAX);
+            if (nd.p[4] != 1 || nd.p[5] != 1)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: dilation %d x %d: a residual graph's convolutions are not dilated", i, nd.p[5], nd.p[4]);
+            if ((padding != 1 && padding != 2) || S.act < 0 || S.act > 3)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: padding %d / fused activation %d", i, padding, S.act);
+            g.out_h = h_out_size(padding, src.h, g.kh, g.sh, 1); g.out_w = h_out_size(padding, src.w, g.kw, g.sw, 1);
+            if (g.out_h < 1 || g.out_w < 1 || yt.dims[1] != g.out_h || yt.dims[2] != g.out_w || yt.dims[3] != g.out_c)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu output shape: the tensor is %d x %d x %d, kernels/padding.h gives %d x %d x %d", i, yt.dims[1], yt.dims[2],
+                            yt.dims[3], g.out_h, g.out_w, g.out_c);
+            S.pad_t = h_pad_amount(g.sh, 1, src.h, g.kh, g.out_h); S.pad_l = h_pad_amount(g.sw, 1, src.w, g.kw, g.out_w);
+            g.krow = g.kw * g.in_c; g.krow4 = (g.krow + 3) & ~3;
+            src.mt = std::max(src.mt, S.pad_t); src.ml = std::max(src.ml, S.pad_l);
+            src.ext_r = std::max(src.ext_r, (g.out_h - 1) * g.sh + g.kh - S.pad_t);
+            src.ext_c = std::max(src.ext_c, (g.out_w - 1) * g.sw + g.kw - S.pad_l);
+            src.uses++; src.last_use = (int)G.st.size();
+            S.nd = &nd; S.a = S.b = img_of[x]; S.x_id = x; S.y_id = y;
+            g.ph = g.pw = g.psh = g.psw = 1; g.pool_h = g.out_h; g.pool_w = g.out_w;
+            HResImage o;
+            o.h = g.out_h; o.w = g.out_w; o.c = g.out_c; o.tid = y; o.ext_r = o.h; o.ext_c = o.w; o.producer = (int)G.st.size();
+            S.dst = (int)G.img.size();
+            G.img.push_back(o);
+            img_of[y] = S.dst; kind_of[y] = PLAIN;
+            G.st.push_back(S);
+            continue;
+        }
+        if (nd.op == OP_ADD) {
+            const int x2 = nd.in[1];
+            if (m.t[x].is_const || m.t[x2].is_const)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "ADD %zu: a constant operand inside a residual graph is not served (its convolutions carry their bias and "
+                            "activation)", i);
+            if (!produced[x] || !produced[x2]) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "ADD %zu reads a tensor no earlier node produced", i);
+            if (EI_IMPULSE_ERROR e = readable(i, x, "ADD operand")) return e;
+            if (EI_IMPULSE_ERROR e = readable(i, x2, "ADD operand")) return e;
+            const Tensor &ta = m.t[x], &tb = m.t[x2], &to = m.t[y];
+            if (ta.dims.size() != 4 || ta.dims != tb.dims || ta.dims != to.dims)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "ADD %zu: its operands and its output must have identical 4-D dims (a broadcasting ADD is not served)", i);
+            if (kind_of[x] == OTHER || kind_of[x] != kind_of[x2] || nd.p[0] < 0 || nd.p[0] > 3)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "ADD %zu: operand shapes / fused activation %d", i, nd.p[0]);
+            if (EI_IMPULSE_ERROR e = produce(i, y)) return e;
+            HResStep S{};
+            KwsResGeom &g = S.g;
+            HResImage &A = G.img[img_of[x]];
+            g.kind = KWS_RES_ADD;
+            g.in_c = g.out_c = A.c; g.kh = g.kw = g.sh = g.sw = 1; g.out_h = A.h; g.out_w = A.w;
+            g.ph = g.pw = g.psh = g.psw = 1; g.pool_h = g.out_h; g.pool_w = g.out_w;
+            S.act = nd.p[0]; S.nd = &nd; S.a = img_of[x]; S.b = img_of[x2]; S.x_id = x; S.y_id = y;
+            for (int k : { S.a, S.b }) { G.img[k].uses++; G.img[k].last_use = (int)G.st.size(); }
+            HResImage o;
+            o.h = g.out_h; o.w = g.out_w; o.c = g.out_c; o.tid = y; o.ext_r = o.h; o.ext_c = o.w; o.producer = (int)G.st.size();
+            S.dst = (int)G.img.size();
+            G.img.push_back(o);
+            img_of[y] = S.dst; kind_of[y] = kind_of[x];
+            G.st.push_back(S);
+            G.n_adds++;
+            continue;
+        }
+        if (nd.op == OP_MAX_POOL_2D) {
+            if (EI_IMPULSE_ERROR e = readable(i, x, "pool input")) return e;
+            HResImage &im = G.img[img_of[x]];
+            if (im.producer < 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: its input is no step's output (a pool is fused into the step that makes its input)", i);
+            HResStep &S = G.st[im.producer];
+            KwsResGeom &g = S.g;
+            if (im.uses > 0 || g.has_pool)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: a pool shares its input with another consumer (it is fused into the step that makes its input)", i);
+            if (kind_of[x] == OTHER) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: input shape", i);
+            if (EI_IMPULSE_ERROR e = produce(i, y)) return e;
+            if (!same_quant(x, y)) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu input", i);
+            const bool sw = kind_of[x] == SWAPPED;             // the node's height axis is the image's width
+            g.psw = nd.p[sw ? 2 : 1]; g.psh = nd.p[sw ? 1 : 2]; g.pw = nd.p[sw ? 4 : 3]; g.ph = nd.p[sw ? 3 : 4]; S.pool_act = nd.p[5];
+            if (g.ph < 1 || g.ph > KWS_NN2D_K_MAX || g.pw < 1 || g.pw > KWS_NN2D_K_MAX || g.psh < 1 || g.psh > KWS_NN2D_K_MAX || g.psw < 1 || g.psw > KWS_NN2D_K_MAX)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: window %d x %d / stride %d x %d is outside 1 .. %d", i, g.ph, g.pw, g.psh, g.psw, KWS_NN2D_K_MAX);
+            if ((nd.p[0] != 1 && nd.p[0] != 2) || S.pool_act < 0 || S.pool_act > 3 || (!is_float && S.pool_act != 0))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: padding %d / fused activation %d", i, nd.p[0], S.pool_act);
+            g.pool_h = h_out_size(nd.p[0], g.out_h, g.ph, g.psh, 1); g.pool_w = h_out_size(nd.p[0], g.out_w, g.pw, g.psw, 1);
+            const std::vector<int> &d = m.t[y].dims;
+            if (g.pool_h < 1 || g.pool_w < 1 || d.size() != 4 || d[0] != 1 || d[1] != (sw ? g.pool_w : g.pool_h) || d[2] != (sw ? g.pool_h : g.pool_w) || d[3] != g.out_c)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu output shape: kernels/padding.h gives %d x %d x %d", i, g.pool_h, g.pool_w, g.out_c);
+            g.ppt = h_pad_amount(g.psh, 1, g.out_h, g.ph, g.pool_h); g.ppl = h_pad_amount(g.psw, 1, g.out_w, g.pw, g.pool_w);
+            if ((g.pool_h - 1) * g.psh - g.ppt >= g.out_h || (g.pool_w - 1) * g.psw - g.ppl >= g.out_w || g.ppt >= g.ph || g.ppl >= g.pw)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "pool %zu: a window lies outside the image", i);
+            g.has_pool = 1;
+            for (int t = 0; t < nt; ++t) if (img_of[t] == img_of[x] && t != y) img_of[t] = -2;      // the un-pooled tensor's names: nothing else may read them
+            im.h = g.pool_h; im.w = g.pool_w; im.ext_r = im.h; im.ext_c = im.w; im.tid = y;
+            img_of[y] = S.dst; kind_of[y] = sw ? SWAPPED : PLAIN;
+            continue;
+        }
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: op %u inside a residual graph", i, nd.op);
+    }
+    if (i >= m.n.size() || flat < 0 || G.st.empty() || m.n[i].in[0] != flat)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected a flattening RESHAPE and FULLY_CONNECTED after the residual steps");
+    cur = flat;
+    // the flattened tensor is the LAST step's output and nothing else reads it; every other tensor is read
+    if (G.final_img != G.st.back().dst || G.img[G.final_img].uses != 0)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "the flattened tensor is not the last step's output alone");
+    for (size_t k = 0; k < G.img.size(); ++k)
+        if ((int)k != G.final_img && G.img[k].uses == 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "the output of step %d is never read", G.img[k].producer);
+    if ((long)G.img[G.final_img].h * G.img[G.final_img].w * G.img[G.final_img].c > KWS_DENSE_IN_MAX)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "the residual steps flatten to %ld values: the dense stack takes at most %d inputs",
+                    (long)G.img[G.final_img].h * G.img[G.final_img].w * G.img[G.final_img].c, KWS_DENSE_IN_MAX);
+    // liveness: at step s the tensors made at or before s (the one being written included) that s or a later step reads
+    const int ns = (int)G.st.size();
+    int most = 0;
+    for (int s = 0; s < ns; ++s) {
+        int live = 0;
+        for (const HResImage &g : G.img) live += (g.producer <= s && (g.last_use >= s || g.producer == s)) ? 1 : 0;
+        most = std::max(most, live);
+    }
+    if (most > KWS_RES_SLOTS)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "the residual graph keeps %d tensors live at once (at most %d: a skip connection may span one block)", most, KWS_RES_SLOTS);
+    // images and slots: a slot is free for step s's output once its tensor's last reader is before s
+    int holder[KWS_RES_SLOTS] = { -1, -1, -1, -1 }, slot_bytes[KWS_RES_SLOTS] = { 0, 0, 0, 0 };
+    for (size_t k = 0; k < G.img.size(); ++k) {
+        HResImage &g = G.img[k];
+        if ((int)k == G.final_img) continue;
+        g.rows = g.mt + g.ext_r;
+        const int row = (g.ml + g.ext_c) * g.c;
+        g.pitch = is_float ? (row | 1) : 4 * (((row + 3) / 4) | 1);             // an odd number of dwords
+        const size_t bytes = ((size_t)g.rows * g.pitch * elem + 16 + 15) & ~(size_t)15;
+        if (bytes > (size_t)KWS_NNRES_LDS_I8)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "residual model needs %zu B of LDS for one %d x %d x %d image: it does not fit the kernel's LDS budget", bytes, g.h,
+                        g.w, g.c);
+        g.bytes = (int)bytes;
+        for (int s = 0; s < KWS_RES_SLOTS && g.slot < 0; ++s)
+            if (holder[s] < 0 || G.img[holder[s]].last_use < g.producer) { g.slot = s; holder[s] = (int)k; }
+        if (g.slot < 0) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "the residual graph keeps more than %d tensors live at once", KWS_RES_SLOTS);
+        slot_bytes[g.slot] = std::max(slot_bytes[g.slot], g.bytes);
+    }
+    int base[KWS_RES_SLOTS];
+    G.wave_bytes = 0;
+    for (int s = 0; s < KWS_RES_SLOTS; ++s) { base[s] = G.wave_bytes / elem; G.wave_bytes += slot_bytes[s]; }
+    for (HResImage &g : G.img) if (g.slot >= 0) g.base = base[g.slot];
+    for (HResStep &S : G.st) {
+        KwsResGeom &g = S.g;
+        const HResImage &A = G.img[S.a], &B = G.img[S.b];
+        g.a_base = A.base; g.a_pitch = A.pitch; g.a_off = (A.mt - S.pad_t) * A.pitch + (A.ml - S.pad_l) * A.c;
+        g.b_base = B.base; g.b_pitch = B.pitch; g.b_off = B.mt * B.pitch + B.ml * B.c;
+        const HResImage &D = G.img[S.dst];
+        if (S.dst == G.final_img) { g.d_base = -1; g.d_off = 0; g.d_pitch = g.pool_w * g.out_c; g.d_bytes = 0; }
+        else { g.d_base = D.base; g.d_off = D.mt * D.pitch + D.ml * D.c; g.d_pitch = D.pitch; g.d_bytes = D.bytes; }
+    }
+    return EI_IMPULSE_OK;
+}
+
+static EI_IMPULSE_ERROR build_nnres_i8(kws_handle *h, size_t &i, int &cur)
+{
+    const Model &m = h->model;
+    KwsResPlan &P = h->nnres;
+    memset(&P, 0, sizeof(P));
+    HResGraph G;
+    if (EI_IMPULSE_ERROR e = h_res_walk(m, i, cur, false, G)) return e;
+    const HResImage &in = G.img[0];
+    P.n_features = (int)m.nn_input_frame_size;
+    P.in_base = in.base; P.in_off = in.mt * in.pitch + in.ml * in.c; P.in_pitch = in.pitch; P.in_bytes = in.bytes; P.in_zp = m.t[in.tid].zero[0];
+    P.in_h = in.h; P.in_row = in.w * in.c;
+    P.wave_bytes = G.wave_bytes; P.n_adds = G.n_adds;
+    for (size_t s = 0; s < G.st.size(); s++) {
+        const HResStep &S = G.st[s];
+        const Node &nd = *S.nd;
+        KwsResStep &k = P.st[s];
+        k.g = S.g;
+        const KwsResGeom &g = k.g;
+        const Tensor &y = m.t[S.y_id];
+        k.out_zp = y.zero[0]; k.d_zp = y.zero[0];
+        h_act_range(S.act, y.scale[0], y.zero[0], &k.act_min, &k.act_max);
+        EI_IMPULSE_ERROR e;
+        if (g.kind == KWS_RES_CONV) {
+            // as build_nn2d_i8: weights -> [out_c][kh][krow4], bias_eff = bias + input_offset * sum(w)   (integer_ops/conv.h:64-113)
+            const Tensor &x = m.t[S.x_id], &w = m.t[nd.in[1]];
+            const Tensor *bias = (nd.in.size() > 2 && nd.in[2] >= 0) ? &m.t[nd.in[2]] : nullptr;
+            std::vector<int8_t> wp((size_t)g.out_c * g.kh * g.krow4, 0);
+            k.w_bytes = (int)wp.size();
+            std::vector<int32_t> rq((size_t)g.out_c * 4, 0);
+            const int8_t *wd = (const int8_t *)w.data.data();
+            const int32_t *bd = bias ? (const int32_t *)bias->data.data() : nullptr;
+            const int32_t in_off = -x.zero[0];
+            const bool per_channel = w.scale.size() > 1;
+            if (w.data.size() < (size_t)g.out_c * g.kh * g.krow || (bias && bias->data.size() < (size_t)g.out_c * 4))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu: constant data", s);
+            if (w.scale.empty() || (per_channel && ((int)w.scale.size() != g.out_c || w.qdim != 0)))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu: per-channel scale count", s);
+            for (int oc = 0; oc < g.out_c; oc++) {
+                int64_t wsum = 0, wabs = 0;
+                for (int fy = 0; fy < g.kh; fy++)
+                    for (int j = 0; j < g.krow; j++) {
+                        const int8_t v = wd[((size_t)oc * g.kh + fy) * g.krow + j];
+                        wp[((size_t)oc * g.kh + fy) * g.krow4 + j] = v;
+                        wsum += v; wabs += std::abs((int)v);
+                    }
+                rq[(size_t)oc * 4] = (int32_t)((bd ? bd[oc] : 0) + (int64_t)in_off * wsum);
+                const double eff = (double)x.scale[0] * (double)(per_channel ? w.scale[oc] : w.scale[0]) / (double)y.scale[0];
+                int32_t mult; int sh;
+                h_quantize_multiplier(eff, &mult, &sh);          // kernel_util_lite.cc:89-103
+                rq[(size_t)oc * 4 + 1] = mult; rq[(size_t)oc * 4 + 2] = sh;
+                if (mult < 0 || sh < -31) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu channel %d: requantisation multiplier", s, oc);
+                if (sh > 0 && h_left_shift_overflows(wabs, in_off, bd ? bd[oc] : 0, sh))
+                    return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu channel %d: requantisation shifts left by %d and (sum|w| * max|x| + |bias|) << %d "
+                                "can pass 2^31 - 1", s, oc, sh, sh);
+            }
+            if ((e = h->upload(wp, &k.w))) return e;
+            if ((e = h->upload(rq, &k.rq))) return e;
+        } else {
+            // CalculateOpData, add.cc:271-309; integer_ops/add.h:108-131 per operand value
+            const Tensor &t1 = m.t[nd.in[0]], &t2 = m.t[nd.in[1]];
+            const int left_shift = 20;
+            const double twice_max = 2 * (double)std::max(t1.scale[0], t2.scale[0]);
+            const double r1 = (double)t1.scale[0] / twice_max, r2 = (double)t2.scale[0] / twice_max;
+            const double ro = twice_max / ((double)(1 << left_shift) * (double)y.scale[0]);
+            int32_t m1, m2, mo; int s1, s2, so;
+            h_quantize_multiplier(r1, &m1, &s1);
+            h_quantize_multiplier(r2, &m2, &s2);
+            h_quantize_multiplier(ro, &mo, &so);
+            // QuantizeMultiplierSmallerThanOneExp asserts real < 1 and a shift <= 0 (a multiplier that rounds up to 2^31 is halved and shifts by one more)
+            if (!(r1 < 1.0) || !(r2 < 1.0) || s1 > 0 || s2 > 0)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "ADD %d: an input multiplier %g / %g is not below 1", (int)(S.nd - &m.n[0]), r1, r2);
+            if (!(ro < 1.0) || so > 0)
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "ADD %d: the output multiplier 2 max(s1, s2) / (2^20 s_out) = %g is not below 1 (the reference asserts there)",
+                            (int)(S.nd - &m.n[0]), ro);
+            std::vector<int32_t> tab(512);
+            for (int v = -128; v <= 127; v++) {
+                tab[v + 128] = h_rdivpot(h_srdhm((v - t1.zero[0]) * (1 << left_shift), m1), -s1);
+                tab[256 + v + 128] = h_rdivpot(h_srdhm((v - t2.zero[0]) * (1 << left_shift), m2), -s2);
+            }
+            k.add_mult = mo; k.add_shift = so;
+            if ((e = h->upload(tab, &k.rq))) return e;
+        }
+        P.tap_bytes += g.pool_h * g.pool_w * g.out_c;
+        P.n_steps++;
+    }
+    const KwsResGeom &lg = P.st[P.n_steps - 1].g;
+    P.out_n = lg.pool_h * lg.pool_w * lg.out_c;
+    if (kws_nnres_waves(P) == 0)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "int8 residual model needs %zu B of LDS at %d waves per workgroup (at most %d): it does not fit the kernel's LDS budget",
+                    kws_nnres_smem_bytes(P, KWS_NNRES_WAVES_MIN), KWS_NNRES_WAVES_MIN, KWS_NNRES_LDS_I8);
+    h->pooled_tap_bytes += P.tap_bytes;
+    h->n_res_adds = P.n_adds;
+    return EI_IMPULSE_OK;
+}
+
+// the float twin of build_nnres_i8: constants as they are, finite weights required (h_first_non_finite).  Filters are staged in LDS while the graph then
+// still fits at KWS_NNRES_WAVES_MIN waves; the largest ones stay in HBM otherwise.
+static EI_IMPULSE_ERROR build_nnres_f32(kws_handle *h, size_t &i, int &cur)
+{
+    const Model &m = h->model;
+    KwsResPlanF32 &P = h->nnresf;
+    memset(&P, 0, sizeof(P));
+    HResGraph G;
+    if (EI_IMPULSE_ERROR e = h_res_walk(m, i, cur, true, G)) return e;
+    const HResImage &in = G.img[0];
+    P.n_features = (int)m.nn_input_frame_size;
+    P.in_base = in.base; P.in_off = in.mt * in.pitch + in.ml * in.c; P.in_pitch = in.pitch; P.in_bytes = in.bytes; P.in_h = in.h; P.in_row = in.w * in.c;
+    P.wave_bytes = G.wave_bytes; P.n_adds = G.n_adds;
+    auto floats = [](const Tensor &t) { return std::vector<float>((const float *)t.data.data(), (const float *)t.data.data() + t.data.size() / 4); };
+    for (size_t s = 0; s < G.st.size(); s++) {
+        const HResStep &S = G.st[s];
+        const Node &nd = *S.nd;
+        KwsResStepF32 &k = P.st[s];
+        k.g = S.g;
+        const KwsResGeom &g = k.g;
+        h_act_range_f32(S.act, &k.act_min, &k.act_max);
+        h_act_range_f32(S.pool_act, &k.pool_min, &k.pool_max);
+        P.n_steps++;
+        if (g.kind != KWS_RES_CONV) continue;
+        const Tensor &w = m.t[nd.in[1]];
+        const Tensor *bias = (nd.in.size() > 2 && nd.in[2] >= 0) ? &m.t[nd.in[2]] : nullptr;
+        std::vector<float> wv = floats(w), bv((size_t)g.out_c, 0.0f);
+        if (wv.size() != (size_t)g.out_c * g.kh * g.krow) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu: filter size", s);
+        if (const long bad = h_first_non_finite(wv); bad >= 0)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu: weight tensor %d holds a non-finite value (element %ld): the float kernels need finite weights", s,
+                        nd.in[1], bad);
+        if (bias) { bv = floats(*bias); if (bv.size() != (size_t)g.out_c) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu: bias size", s); }
+        k.w_lds = 1;
+        EI_IMPULSE_ERROR e;
+        if ((e = h->upload(wv, &k.w))) return e;
+        if ((e = h->upload(bv, &k.bias))) return e;
+    }
+    const KwsResGeom &lg = P.st[P.n_steps - 1].g;
+    P.out_n = lg.pool_h * lg.pool_w * lg.out_c;
+    while (kws_nnres_f32_waves(P) == 0) {                 // the largest staged filter goes back to HBM
+        int big = -1;
+        for (int s = 0; s < P.n_steps; ++s)
+            if (P.st[s].g.kind == KWS_RES_CONV && P.st[s].w_lds &&
+                (big < 0 || P.st[s].g.out_c * P.st[s].g.kh * P.st[s].g.krow > P.st[big].g.out_c * P.st[big].g.kh * P.st[big].g.krow)) big = s;
+        if (big < 0)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "float residual model needs %zu B of LDS at %d waves per workgroup (at most %d): its images do not fit the kernel's "
+                        "LDS budget", kws_nnres_f32_smem_bytes(P, KWS_NNRES_WAVES_MIN), KWS_NNRES_WAVES_MIN, KWS_NNRES_LDS_F32);
+        P.st[big].w_lds = 0;
+    }
+    h->n_res_adds = P.n_adds;
+    return EI_IMPULSE_OK;
+}
+
 static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
 {
     const Model &m = h->model;
@@ -930,10 +1390,16 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
         while (i < m.n.size() && m.n[i].op == OP_RESHAPE && m.n[i].in[0] == cur) { cur = m.n[i].out[0]; i++; }
     };
     auto floats = [](const Tensor &t) { return std::vector<float>((const float *)t.data.data(), (const float *)t.data.data() + t.nbytes / 4); };
+    // a residual graph: its steps in a plan of their own (this one keeps n_blocks = 0), then the dense stack -- always
+    int inputs2d = 0;
+    const bool residual = h_is_residual(m);
+    if (residual) {
+        if (EI_IMPULSE_ERROR e = build_nnres_f32(h, i, cur)) return e;
+        inputs2d = h->nnresf.out_n;
+    }
     skip_reshapes();
     // a 2-D graph: its blocks in a plan of their own (this one keeps n_blocks = 0), then the dense stack -- always, a single FULLY_CONNECTED included
-    int inputs2d = 0;
-    if (h_is_2d(m, i, cur)) {
+    if (!residual && h_is_2d(m, i, cur)) {
         if (EI_IMPULSE_ERROR e = build_nn2d_f32(h, i, cur)) return e;
         if (i >= m.n.size() || m.n[i].op != OP_FULLY_CONNECTED) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "expected FULLY_CONNECTED after the conv blocks");
         inputs2d = h->nn2df.out_n;
@@ -1073,7 +1539,8 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
         N.fc_in = inputs; N.fc_out = 0;                  // the trunk form of kws_nn_f32_kernel sizes its output vector by fc_in; it has no head
         N.dense = &D; N.handoff = &h->handoff;
         handoff_init(h, sizeof(float) * (size_t)inputs);
-        if (inputs2d) h->handoff.trunk2d_f32 = &h->nn2df;
+        if (residual) h->handoff.trunkres_f32 = &h->nnresf;
+        else if (inputs2d) h->handoff.trunk2d_f32 = &h->nn2df;
         h->n_dense = D.n_layers;
         if (N.n_blocks > 0 && kws_nn_f32_smem_bytes(N, 4) > 150 * 1024) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "float model too large for the kernel's LDS budget");
         void *d = nullptr;

@@ -76,6 +76,19 @@ int kws_dense_layer_count(const kws_handle *h);          /* FULLY_CONNECTED laye
  * kernel serves the blocks: the trunk runs on v_dot4 (int8) / in-order float chains.  tap_pooled of kws_nn_batch_device holds every block's (pooled) output in NHWC
  * order, one after another, then the hidden dense outputs; kws_pooled_tap_bytes says how many. */
 int kws_conv2d_block_count(const kws_handle *h);         /* CONV_2D blocks of a 2-D graph; 0 for every other graph */
+/* Residual graphs: a graph in which at least one ADD sums two ACTIVATION tensors -- the identity and (strided) 1 x 1 projection shortcuts of
+ * TC-ResNet-style spotters and ResNet-ish Keras models, on [1][1][W][C] and on [1][H][W][C] images alike.  Between the input RESHAPE and the flatten the graph is
+ * a list of at most 16 steps in node order: CONV_2D (filter sides 1 .. 16, stride 1 .. 4 per axis, dilation 1, SAME / VALID, constant bias or none, fused activation
+ * 0 .. 3, at most 64 channels) or ADD(a, b) (identical 4-D dims, any scales and zero points, fused activation 0 .. 3; a and b any earlier tensors, the same one
+ * twice included), each optionally followed by a MAX_POOL_2D that is the only reader of its input.  RESHAPEs that keep the quantisation are renamings.  At most 4
+ * tensors are live at once.  A flatten, 1 .. 4 FULLY_CONNECTED layers and SOFTMAX follow.  Served bit-exactly (float32: logits bit for bit, scores within 1e-6) by
+ * kws_nnres_trunk_kernel / kws_nnres_f32_trunk_kernel in front of the dense kernels, through every entry point.  Refused with KWS_ERROR_UNSUPPORTED_MODEL
+ * (kws_last_error names the node and the reason): a broadcasting ADD, a constant ADD operand or DEPTHWISE_CONV_2D in such a graph, dilation other than 1, more
+ * than 16 steps or 4 live tensors, a pool that shares its input with another reader, an int8 pool with a fused activation, output dims that disagree with
+ * kernels/padding.h, non-finite float weights, left-shifting conv requantisation past the 1-D blocks' bound, an int8 ADD whose output multiplier
+ * 2 max(s1, s2) / (2^20 s_out) is not below 1, and a graph that does not fit the kernels' LDS budget at four waves per workgroup.  KWS_MODE_EXACT only, as a 2-D
+ * graph.  tap_pooled of kws_nn_batch_device holds every step's (pooled) output in step order, then the hidden dense outputs. */
+int kws_residual_add_count(const kws_handle *h);         /* tensor + tensor ADDs of a residual graph; 0 for every other graph (kws_conv2d_block_count stays 0 for a residual graph) */
 const char *kws_nn_kernel_name(const kws_handle *h);    /* which network kernel serves this model (diagnostics); "kws_nn_sd_kernel" / "kws_nn_f32_sd_kernel" (in front of a
                                                             dense stack: "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel", float32 likewise) for a graph with a strided or dilated block;
                                                             "kws_nn2d_trunk_kernel + kws_dense_i8_kernel" / "kws_nn2d_f32_trunk_kernel + kws_dense_f32_kernel" for a 2-D graph.

@@ -35,12 +35,21 @@ def dequantised_constants(tensors):
     return out
 
 
-def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
+def is_residual(tensors, nodes):
+    """an ADD of two activation tensors makes a graph residual"""
+    return any(nd["op"] == 2 and not tensors[nd["in"][0]]["const"] and not tensors[nd["in"][1]]["const"] for nd in nodes)
+
+
+def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None, four_d=None):
     """The graph's float32 twin evaluated in numpy for a batch x [n][features] -- the arithmetic of the reference's float kernels
     (TFL/kernels/internal/reference/conv.h:28-99, depthwiseconv_float.h:25, add.h:179-215, pooling.h:189-237, fully_connected.h:26-60)
     without their rounding order: used to CALIBRATE a synthetic head, never as a checker.  Activations are kept as [n][time][channel];
-    RESHAPE only renames axes in this graph family.  Returns {tensor id: value}; stops before the first node whose op is stop_before_op."""
-    act = {t_in: np.asarray(x, np.float64)}
+    RESHAPE only renames axes in this graph family.  Returns {tensor id: value}; stops before the first node whose op is stop_before_op.
+    A residual graph (is_residual; four_d says so for a slice of one) is a DAG: t_in may be a dict {tensor id: value} of the activations a slice of the
+    graph starts from, every 4-D tensor is kept as [n][H][W][C] (H = 1 included), and ADD sums two activations."""
+    act = {k: np.asarray(v, np.float64) for k, v in t_in.items()} if isinstance(t_in, dict) else {t_in: np.asarray(x, np.float64)}
+    if four_d is None:
+        four_d = is_residual(tensors, nodes)
 
     def fused(v, a):                                    # TfLiteFusedActivation: 0 none, 1 relu, 2 relu_n1_to_1, 3 relu6
         return v if a == 0 else np.maximum(v, 0.0) if a == 1 else np.clip(v, -1.0, 1.0) if a == 2 else np.clip(v, 0.0, 6.0)
@@ -72,7 +81,7 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
         a = act.get(nd["in"][0])
         if nd["op"] == 0:                               # RESHAPE
             n = a.shape[0]
-            if len(dims) == 4 and dims[1] > 1 and dims[2] > 1:          # a 2-D image [n][H][W][C] (blocks2d=)
+            if len(dims) == 4 and ((dims[1] > 1 and dims[2] > 1) or four_d):          # a 2-D image [n][H][W][C] (blocks2d=, residual=)
                 act[o] = a.reshape(n, dims[1], dims[2], dims[3])
             else:
                 act[o] = a.reshape(n, -1) if len(dims) == 2 else a.reshape(n, -1, dims[-1])
@@ -111,6 +120,8 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None):
                 mult = p[6]
                 v = np.einsum("nwto,to->nwo", np.repeat(g, mult, axis=3), w[0, 0]) + b
             act[o] = fused(v, p[3])
+        elif nd["op"] == 2 and nd["in"][1] in act:      # ADD of two activations (a residual graph)
+            act[o] = fused(a + act[nd["in"][1]], p[0])
         elif nd["op"] == 2:                             # ADD of a per-channel constant
             act[o] = fused(a + const[nd["in"][1]], p[0])
         elif nd["op"] == 3:                             # MAX_POOL_2D over time
@@ -160,13 +171,53 @@ def calibrate_ranges(tensors, nodes, t_in, x):
         tensors[tb]["scale"] = new_scale
         tensors[tb]["data"] = np.round(old / np.float64(new_scale)).astype(np.int32).tobytes()
 
+    # a node's inputs come from the activations so far, not from "the previous output": the graph may be a DAG (residual=)
     act = {t_in: np.asarray(x, np.float64)}
+    four_d = is_residual(tensors, nodes)
     for nd in nodes:
         before(nd)
-        sub = float_forward(tensors, [nd], nd["in"][0], act[nd["in"][0]], on_output=on_output) if nd["op"] != 5 else None
-        if sub is None:
+        if nd["op"] == 5:
             break
+        sub = float_forward(tensors, [nd], {k: act[k] for k in nd["in"] if k in act}, None, on_output=on_output, four_d=four_d)
         act[nd["out"][0]] = sub[nd["out"][0]]
+
+
+def calibrate_residual(tensors, nodes, t_in, x, lift=0.5, lifts=None, per_tensor=False):
+    """The convolutions of a residual graph (synth_model_blob's residual=), in node order on the calibration set x.  As drawn, a ReLU parks about half of a
+    convolution's outputs on its bound and the drawn output scales saturate the rest, so that every ADD sums two clamped tensors.  Per convolution: a
+    ReLU_N1_TO_1 / ReLU6 one gets weight scales that make its pre-activations' deviation 0.5 / 1.5; the int32 bias is set per channel so that the float
+    twin's pre-activation has mean lift x its own deviation under ReLU / ReLU6 (about 0.5: a third of the outputs below zero) and mean 0 otherwise
+    (lifts: {node index: lift} overrides that for a node, whatever its activation).  Then every activation range is settled (calibrate_ranges)."""
+    four_d = True
+    for idx, nd in enumerate(nodes):
+        if nd["op"] != 1:
+            continue
+        calibrate_ranges(tensors, nodes[:idx], t_in, x)
+        a = float_forward(tensors, nodes[:idx], t_in, x, four_d=four_d)[nd["in"][0]]
+        tw, tb = tensors[nd["in"][1]], tensors[nd["in"][2]]
+        if per_tensor:
+            tw["scale"], tw["zero"] = [float(np.float32(np.mean(tw["scale"])))], [0]
+        act = nd["p"][3]
+        nd["p"][3] = 0                                   # the pre-activation: this node without its clamp and bias
+        tb["data"] = bytes(len(tb["data"]))
+
+        def pre():
+            v = float_forward(tensors, [nd], {nd["in"][0]: a}, None, four_d=four_d)[nd["out"][0]]
+            return v.reshape(-1, v.shape[-1])
+        if act in (2, 3):
+            sd = pre().std()
+            tw["scale"] = [float(np.float32(s_ * (1.5 if act == 3 else 0.5) / sd)) for s_ in tw["scale"]]
+        v = pre()
+        nd["p"][3] = act
+        in_scale = tensors[nd["in"][0]]["scale"][0]
+        tb["scale"] = [float(np.float32(in_scale) * np.float32(s_)) for s_ in tw["scale"]]
+        tb["zero"] = [0] * len(tb["scale"])
+        k = (lifts or {}).get(idx, lift if act in (1, 3) else 0.0)
+        bias = np.round((k * v.std(axis=0) - v.mean(axis=0)) / np.float64(tb["scale"]))
+        assert np.abs(bias).max() < 2 ** 31
+        tb["data"] = bias.astype(np.int32).tobytes()
+    fc = [i for i, nd in enumerate(nodes) if nd["op"] == 4][0]
+    calibrate_ranges(tensors, nodes[:fc], t_in, x)
 
 
 def calibrate_hidden(tensors, nodes, t_in, hidden, x, lift=0.7):
@@ -219,7 +270,7 @@ def calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, logit_std, seed, n_cal=2
 def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((30, 7, 7), (10, 7, 7)), n_labels=4,
                      conv_bias=False, add_bias=True, num_filters=32, raw_samples=16000, fft_length=256, frame_length=0.02,
                      frame_stride=0.02, pre_cof=0.98, dsp_block="mfcc", logit_std=None, quantize_filterbank=False, edit=None, dense=None,
-                     calib=None, conv_valid=(), conv_stride=None, conv_dilation=None, blocks2d=None):
+                     calib=None, conv_valid=(), conv_stride=None, conv_dilation=None, blocks2d=None, residual=None, two_d=False, residual_opts=None):
     """blocks: sequence of
          (out_channels, taps, pool)              CONV_2D 1xK (+ optional int32 bias) -> ADD(int8 per-channel)+ReLU -> MAX_POOL
          ("dw", depth_mult, taps, pool, act)     DEPTHWISE_CONV_2D 1xK with int32 bias and fused activation -> MAX_POOL
@@ -247,6 +298,15 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
        int32 bias and fused ReLU, then MAX_POOL_2D pool x pool at stride pool, SAME padding (pool 0 / 1: no pooling node).  options (a dict): stride=(h, w),
        valid=True (VALID convolution), act=0 .. 3, bias=False (no bias tensor), pool=(h, w) window, pool_stride=(h, w), pool_valid=True.  A flatten, dense=,
        the head and softmax follow as ever.  It draws nothing when blocks2d is None: every blob is the one the same arguments gave before.
+       residual: None, or the steps of a residual graph, which then REPLACE blocks: the features are reshaped to [1][1][frames][columns] (two_d:
+       [1][frames][columns][1]) -- the tensor named "in" -- and every step names its output:
+         (name, "conv", src, out_c, kh, kw, (sh, sw), valid, act[, lift])   CONV_2D kh x kw on tensor src with int32 bias and fused activation act
+         (name, "add", a, b, act)                                           ADD of tensors a and b (the same name twice is allowed)
+         (name, "pool", src, (ph, pw), (psh, psw), valid[, keras])           MAX_POOL_2D; keras: through the [1][W][1][C] renaming of Keras' Conv1D exports
+       The last step's output is flattened; dense=, the head and softmax follow as ever.  Such a graph is always calibrated (calibrate_residual on
+       standardised random feature matrices or calib: the bias of an activated convolution lifts its pre-activations by 0.5 deviations -- a step's own lift
+       overrides that --, every step output gets the range its float twin shows; then calibrate_hidden / calibrate_head).  residual_opts: dict(per_tensor=True)
+       gives every filter ONE scale.  It draws nothing when residual is None: every blob is the one the same arguments gave before.
        edit: a callable edit(tensors, nodes) run on the finished graph just before it is serialised -- the way to any quantisation
        parameter, constant or node option outside the drawn bands (tests/kws_testlib.py QUANT_EDGES).  It draws nothing from the
        model's generator: with edit=None every blob is the one the same arguments gave before."""
@@ -279,10 +339,79 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
     def rscale(lo, hi):
         return float(np.float32(np.exp(rng.uniform(np.log(lo), np.log(hi)))))
 
+    residual_lift = {}                                  # residual=: node index -> a convolution's own lift
     in_scale, in_zp = rscale(0.03, 0.06), int(rng.integers(-20, 5))
     t_in = T(9, [1, F], scale=[in_scale], zero=[in_zp])
     cur, cur_scale, cur_zp, w, c = t_in, in_scale, in_zp, n_frames, ncep
-    if blocks2d is not None:
+    if residual is not None:
+        blocks = ()
+        hh, ww, cc = (n_frames, ncep, 1) if two_d else (1, n_frames, ncep)
+        t = T(9, [1, hh, ww, cc], scale=[cur_scale], zero=[cur_zp])
+        node(0, [cur, shape_const([1, hh, ww, cc])], [t])
+        named = {"in": (t, hh, ww, cc)}                                 # name -> (tensor id, H, W, C)
+
+        def drawn_output(act):
+            return rscale(0.03, 0.12), int(rng.integers(-128, -90)) if act in (1, 3) else int(rng.integers(-30, 40))
+
+        for ent in residual:
+            name, kind = ent[0], ent[1]
+            assert name not in named, name
+            if kind == "conv":
+                src, oc, kh, kw, (sh, sw), valid, act = ent[2:9]
+                ts, h_, w_, c_ = named[src]
+                wq = rng.integers(-127, 128, (oc, kh, kw, c_)).astype(np.int8)
+                wscales = [rscale(0.001, 0.005) for _ in range(oc)]
+                tw = T(9, [oc, kh, kw, c_], True, wscales, [0] * oc, wq.tobytes())
+                bias = rng.integers(-300, 300, oc).astype(np.int32)
+                tb = T(2, [oc], True, [tensors[ts]["scale"][0] * s_ for s_ in wscales], [0] * oc, bias.tobytes())
+                out_scale, out_zp = drawn_output(act)
+                if valid:                                               # ComputeOutSize (kernels/padding.h)
+                    assert h_ >= kh and w_ >= kw
+                    h_, w_ = (h_ - kh) // sh + 1, (w_ - kw) // sw + 1
+                else:
+                    h_, w_ = (h_ + sh - 1) // sh, (w_ + sw - 1) // sw
+                tc = T(9, [1, h_, w_, oc], scale=[out_scale], zero=[out_zp])
+                node(1, [ts, tw, tb], [tc], [2 if valid else 1, sw, sh, act, 1, 1])
+                if len(ent) > 9:
+                    residual_lift[len(nodes) - 1] = ent[9]
+                named[name] = (tc, h_, w_, oc)
+            elif kind == "add":
+                a_, b_, act = ent[2:5]
+                (ta, h_, w_, c_), (tb_, hb, wb, cb) = named[a_], named[b_]
+                assert (h_, w_, c_) == (hb, wb, cb), (name, named[a_], named[b_])
+                out_scale, out_zp = drawn_output(act)
+                to = T(9, [1, h_, w_, c_], scale=[out_scale], zero=[out_zp])
+                node(2, [ta, tb_], [to], [act])
+                named[name] = (to, h_, w_, c_)
+            elif kind == "pool":
+                src, (ph, pw), (psh, psw), valid = ent[2:6]
+                keras = len(ent) > 6 and ent[6]                         # through the [1][W][1][C] renaming of Keras' Conv1D exports (1-D graphs)
+                ts, h_, w_, c_ = named[src]
+                q = dict(scale=list(tensors[ts]["scale"]), zero=list(tensors[ts]["zero"]))
+                if valid:
+                    assert h_ >= ph and w_ >= pw
+                    h2, w2, pad = (h_ - ph) // psh + 1, (w_ - pw) // psw + 1, 2
+                else:
+                    h2, w2, pad = (h_ + psh - 1) // psh, (w_ + psw - 1) // psw, 1
+                if keras:
+                    assert h_ == 1 and ph == 1 and psh == 1
+                    t4 = T(9, [1, w_, 1, c_], **q)
+                    node(0, [ts, shape_const([1, w_, 1, c_])], [t4])
+                    tp = T(9, [1, w2, 1, c_], **q)
+                    node(3, [t4], [tp], [pad, 1, psw, 1, pw, 0])
+                    t5 = T(9, [1, 1, w2, c_], **q)
+                    node(0, [tp, shape_const([1, 1, w2, c_])], [t5])
+                    tp = t5
+                else:
+                    tp = T(9, [1, h2, w2, c_], **q)
+                    node(3, [ts], [tp], [pad, psw, psh, pw, ph, 0])
+                named[name] = (tp, h2, w2, c_)
+            else:
+                raise ValueError("residual step kind %r" % (kind,))
+        cur, hh, ww, c = named[residual[-1][0]]
+        cur_scale, cur_zp = tensors[cur]["scale"][0], tensors[cur]["zero"][0]
+        w = hh * ww                                                     # the flatten below: NHWC order
+    elif blocks2d is not None:
         blocks = ()
         hh, w, c = n_frames, ncep, 1
         t = T(9, [1, hh, w, 1], scale=[cur_scale], zero=[cur_zp])
@@ -439,7 +568,12 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
     node(4, [tf, tfw, tfb], [tfo], [0])
     tso = T(9, [1, n_labels], scale=[0.00390625], zero=[-128])
     node(5, [tfo], [tso], beta=1.0)
-    if hidden:
+    if residual is not None:
+        xc = np.random.default_rng(200000 + seed).standard_normal((256, F)) if calib is None else np.asarray(calib, np.float64)
+        calibrate_residual(tensors, nodes, t_in, xc, lifts=residual_lift, per_tensor=bool((residual_opts or {}).get("per_tensor")))
+        calibrate_hidden(tensors, nodes, t_in, hidden, xc)
+        calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, 1.5 if logit_std is None else float(logit_std), seed, x=xc)
+    elif hidden:
         xc = np.random.default_rng(200000 + seed).standard_normal((256, F)) if calib is None else np.asarray(calib, np.float64)
         calibrate_hidden(tensors, nodes, t_in, hidden, xc)
         calibrate_head(tensors, nodes, t_in, tfw, tfb, tfo, 1.5 if logit_std is None else float(logit_std), seed, x=xc)
@@ -474,6 +608,10 @@ def main():
     ap.add_argument("--conv-valid", default="", help="convolutions with VALID padding: block;block")
     ap.add_argument("--blocks2d", default="", help="a 2-D convolutional graph instead of --blocks: out_channels,kh,kw,pool per block, e.g. \"8,3,3,2;16,3,3,2\"; "
                     "options after a colon, k=v pairs: stride=HxW valid=1 act=N bias=0 pool=HxW pool_stride=HxW pool_valid=1")
+    ap.add_argument("--residual", default="", help="a residual graph instead of --blocks: steps name,conv,src,out_c,kh,kw,SHxSW,valid,act[,lift] | name,add,a,b,act | "
+                    "name,pool,src,PHxPW,SHxSW,valid[,keras], separated by ';' (src \"in\": the reshaped input), e.g. "
+                    "\"c0,conv,in,16,1,3,1x1,0,1;m1,conv,c0,16,1,9,1x1,0,0;sum,add,c0,m1,1\"")
+    ap.add_argument("--two-d", action="store_true", help="with --residual: the input is [1][frames][columns][1], not [1][1][frames][columns]")
     a = ap.parse_args()
     blocks = tuple(tuple(v if v in ("dw", "pw") else int(v) for v in b.split(",")) for b in a.blocks.split(";") if b)      # --blocks "": dense only
     dense = tuple(tuple(int(v) for v in d.split(",")) for d in a.dense.split(";") if d) or None
@@ -485,7 +623,17 @@ def main():
             opt[k] = tuple(int(x) for x in v.split("x")) if k in ("stride", "pool", "pool_stride") else bool(int(v)) if k in ("valid", "bias", "pool_valid") else int(v)
         return tuple(int(v) for v in head.split(",")) + ((opt,) if opt else ())
     blocks2d = tuple(block2d(b) for b in a.blocks2d.split(";") if b) or None
-    blob = synth_model_blob(a.seed, blocks2d=blocks2d, ncep=a.ncep, win_size=a.win_size, low=a.low, high=a.high, blocks=blocks,
+
+    def res_step(text):
+        v = text.split(",")
+        pair = lambda s: tuple(int(x) for x in s.split("x"))
+        if v[1] == "conv":
+            return (v[0], "conv", v[2], int(v[3]), int(v[4]), int(v[5]), pair(v[6]), bool(int(v[7])), int(v[8])) + ((float(v[9]),) if len(v) > 9 else ())
+        if v[1] == "add":
+            return (v[0], "add", v[2], v[3], int(v[4]))
+        return (v[0], "pool", v[2], pair(v[3]), pair(v[4]), bool(int(v[5]))) + ((bool(int(v[6])),) if len(v) > 6 else ())
+    residual = tuple(res_step(s_) for s_ in a.residual.split(";") if s_) or None
+    blob = synth_model_blob(a.seed, blocks2d=blocks2d, residual=residual, two_d=a.two_d, ncep=a.ncep, win_size=a.win_size, low=a.low, high=a.high, blocks=blocks,
                             n_labels=a.labels, num_filters=a.num_filters, logit_std=a.logit_std, dense=dense,
                             conv_valid=tuple(int(v) for v in a.conv_valid.split(";") if v),
                             conv_stride={int(v.split(":")[0]): int(v.split(":")[1]) for v in a.conv_stride.split(";") if v} or None,
