@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "run_moving_average_filter", "ei_run_impulse_check_canceled", "ei_sleep", "ei_read_timer_ms",
     "ei_read_timer_us", "ei_printf", "ei_printf_float",
     "kws_create", "kws_create_from_file", "kws_destroy", "kws_last_error", "kws_label_count", "kws_label",
-    "kws_feature_count", "kws_clip_samples", "kws_frame_count", "kws_pooled_tap_bytes", "kws_dense_layer_count", "kws_conv2d_block_count", "kws_residual_add_count", "kws_model_is_float",
+    "kws_feature_count", "kws_clip_samples", "kws_frame_count", "kws_pooled_tap_bytes", "kws_dense_layer_count", "kws_conv2d_block_count", "kws_residual_add_count", "kws_depthwise_step_count", "kws_model_is_float",
     "kws_nn_f32_batch_device", "kws_nn_kernel_name", "kws_mfcc_kernel_name", "kws_mfe_batch_device", "kws_filter_count", "kws_set_default_model",
     "kws_default_model", "kws_run_classifier_batch_device", "kws_run_classifier_batch",
     "kws_extract_mfcc_batch_device", "kws_run_inference_batch_device", "kws_mfcc_batch_device",
@@ -121,6 +121,8 @@ def lib():
             L.kws_conv2d_block_count.argtypes = [vp]
         if hasattr(L, "kws_residual_add_count"):
             L.kws_residual_add_count.argtypes = [vp]
+        if hasattr(L, "kws_depthwise_step_count"):
+            L.kws_depthwise_step_count.argtypes = [vp]
         L.kws_label.restype = C.c_char_p
         L.kws_comm_unique_id.argtypes = [vp, sz]
         L.kws_comm_create.argtypes = [vp, sz, i32, i32, i32, C.POINTER(vp)]
@@ -284,6 +286,7 @@ class Model:
         self.dense_layer_count = self.L.kws_dense_layer_count(h) if hasattr(self.L, "kws_dense_layer_count") else 1
         self.conv2d_block_count = self.L.kws_conv2d_block_count(h) if hasattr(self.L, "kws_conv2d_block_count") else 0     # CONV_2D blocks of a 2-D graph, else 0
         self.residual_add_count = self.L.kws_residual_add_count(h) if hasattr(self.L, "kws_residual_add_count") else 0     # tensor + tensor ADDs of a residual graph, else 0
+        self.depthwise_step_count = self.L.kws_depthwise_step_count(h) if hasattr(self.L, "kws_depthwise_step_count") else 0     # depthwise steps on the step trunks, else 0
         self.is_float = bool(self.L.kws_model_is_float(h))
         self.nn_kernel = self.L.kws_nn_kernel_name(h).decode()
         self.mfcc_kernel = self.L.kws_mfcc_kernel_name(h).decode()

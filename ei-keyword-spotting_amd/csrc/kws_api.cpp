@@ -87,6 +87,7 @@ int kws_pooled_tap_bytes(const kws_handle *h) { return h->pooled_tap_bytes; }
 int kws_dense_layer_count(const kws_handle *h) { return h ? h->n_dense : 0; }
 int kws_conv2d_block_count(const kws_handle *h) { return h ? h->n_conv2d : 0; }
 int kws_residual_add_count(const kws_handle *h) { return h ? h->n_res_adds : 0; }
+int kws_depthwise_step_count(const kws_handle *h) { return h ? h->n_res_dw : 0; }
 int kws_model_is_float(const kws_handle *h) { return h->is_float ? 1 : 0; }
 // (the tuned kernel of the int16 batch paths; float samples -- the SDK's signal_t callback -- run kws_mfcc_kernel, the same arithmetic on
 // the older lane layout)
@@ -101,8 +102,8 @@ const char *kws_nn_kernel_name(const kws_handle *h)
 {
     // a 2-D graph: the 2-D trunk, then the dense kernel
     if (h->n_conv2d) return h->is_float ? "kws_nn2d_f32_trunk_kernel + kws_dense_f32_kernel" : "kws_nn2d_trunk_kernel + kws_dense_i8_kernel";
-    // a residual graph: the residual trunk, then the dense kernel
-    if (h->n_res_adds) return h->is_float ? "kws_nnres_f32_trunk_kernel + kws_dense_f32_kernel" : "kws_nnres_trunk_kernel + kws_dense_i8_kernel";
+    // a residual graph or a 2-D graph with depthwise steps: the step trunk, then the dense kernel
+    if (h->res_trunk) return h->is_float ? "kws_nnres_f32_trunk_kernel + kws_dense_f32_kernel" : "kws_nnres_trunk_kernel + kws_dense_i8_kernel";
     // a strided or dilated block in front of a dense stack: the strided form of the trunk, then the dense kernel
     if (h->is_float ? kws_nnf_dense(h->nnf) && kws_nnf_strided(h->nnf) : kws_nn_dense(h->nn) && kws_nn_strided(h->nn))
         return h->is_float ? "kws_nn_f32_sd_trunk_kernel + kws_dense_f32_kernel" : "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel";
@@ -130,6 +131,8 @@ EI_IMPULSE_ERROR kws_set_mode(kws_handle *h, int mode)
     if (!h || (mode != KWS_MODE_EXACT && mode != KWS_MODE_FAST)) return fail(KWS_ERROR_BAD_ARGUMENT, "kws_set_mode: bad argument");
     if (mode == KWS_MODE_FAST && h->n_res_adds)
         return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a residual graph keeps the exact kernels (no fused plan, no calibrated logit gain)");
+    if (mode == KWS_MODE_FAST && h->res_trunk)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a 2-D depthwise-separable graph keeps the exact kernels (no fused plan, no calibrated logit gain)");
     if (mode == KWS_MODE_FAST && h->n_conv2d)
         return fail(KWS_ERROR_UNSUPPORTED_MODEL, "fast mode: a 2-D convolutional graph keeps the exact kernels (no fused plan, no calibrated logit gain)");
     if (mode == KWS_MODE_FAST && h->is_float && kws_nnf_dense(h->nnf))

@@ -739,6 +739,12 @@ EI_IMPULSE_ERROR build_fast_plans(kws_handle *h)
         h->fast_why = "fast mode: a residual graph keeps the exact kernels";
         return EI_IMPULSE_OK;
     }
+    // a 2-D graph with depthwise steps likewise
+    if (h->res_trunk) {
+        h->fast_plain_ok = h->fast_fused_ok = h->fast_q_ok = false;
+        h->fast_why = "fast mode: a 2-D depthwise-separable graph keeps the exact kernels";
+        return EI_IMPULSE_OK;
+    }
     // float32 graphs of the tuned DSP shapes: the guard needs the graph's logit gain (kws_gain.cpp), ~50 ms of host work per model
     if (h->is_float && !h->dsp.generic && !kws_nnf_dense(h->nnf) && h->nnf.n_blocks > 0 && h->nnf.blk[0].in_w == h->dsp.n_frames && h->nnf.blk[0].in_c == h->dsp.n_cepstral)
         kws_calibrate_gain(h);

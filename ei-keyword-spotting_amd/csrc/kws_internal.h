@@ -189,6 +189,9 @@ struct kws_handle {
     KwsResPlan nnres{};
     KwsResPlanF32 nnresf{};
     int n_res_adds = 0;
+    // the step trunks serve the graph (a residual graph, or a 2-D graph with a DEPTHWISE_CONV_2D), and its depthwise steps
+    bool res_trunk = false;
+    int n_res_dw = 0;
     std::vector<void *> dev_allocs;
     // kws_spectral_lds_kernel's frames per chunk, measured per handle on its own first large calls (kws_api.cpp generic_chunk_begin / _end)
     struct GenericTune { int choice = 0, phase = 0, armed = 0; size_t clips = 0; hipEvent_t ev[2] = { nullptr, nullptr }; double ms_per_clip[2] = { 0.0, 0.0 };

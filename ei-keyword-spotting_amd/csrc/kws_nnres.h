@@ -4,9 +4,11 @@
 #include <hip/hip_runtime.h>
 #include "kws_plan.h"
 
-// waves per workgroup: the most that fit the LDS budget, from 16 down to 4 (the 2-D trunks' bounds and budgets); the waves of a workgroup share one copy of
-// the weights, requantisation constants and ADD tables
-#define KWS_NNRES_WAVES_MIN 4
+// waves per workgroup: the most that fit the LDS budget, from 16 down to 2 (the 2-D trunks' budgets); the waves of a workgroup share one copy of the
+// weights, requantisation constants and ADD tables.  Below KWS_NNRES_WAVES_STAGE (the floor of DESIGN 4.17) only what would be refused otherwise runs: a
+// float inverted residual's expanded image; the float plan stages filters in LDS only while the graph still fits at KWS_NNRES_WAVES_STAGE.
+#define KWS_NNRES_WAVES_MIN 2
+#define KWS_NNRES_WAVES_STAGE 4
 #define KWS_NNRES_WAVES_MAX 16
 #define KWS_NNRES_LDS_I8 (158 * 1024)
 #define KWS_NNRES_LDS_F32 (150 * 1024)

@@ -1,6 +1,6 @@
-// kws_nnres_f32.hip -- kws_nnres_f32_trunk_kernel: the steps of a float32 residual graph -- CONV_2D [+ MAX_POOL_2D] and ADD(tensor, tensor)
-// [+ MAX_POOL_2D] -- in front of kws_dense_f32_kernel.  Replays reference/conv.h:28-99, reference/add.h and reference/pooling.h:189-237 in the reference's
-// own order.
+// kws_nnres_f32.hip -- kws_nnres_f32_trunk_kernel: the steps of a float32 residual graph or depthwise-separable 2-D graph --
+// CONV_2D, DEPTHWISE_CONV_2D and ADD(tensor, tensor), each [+ MAX_POOL_2D] -- in front of kws_dense_f32_kernel.  Replays reference/conv.h:28-99,
+// reference/depthwiseconv_float.h:25-97, reference/add.h and reference/pooling.h:189-237 in the reference's own order.
 //
 // The execution model and the image layout of kws_nnres_trunk_kernel (kws_nnres_int8.hip): one wave per clip, persistent workgroups, every tensor once in
 // the slot the plan gave it, behind the largest margin its consumers need; padding is +0.0f.  The convolution is kws_nn2d_f32_trunk_kernel's: every output
@@ -8,6 +8,9 @@
 // switches contraction off), then + bias, then the clamp; a padded tap adds 0 * w = +-0 to a chain that started at +0, which changes nothing for a FINITE w
 // (the plan refuses a non-finite weight).  The filters of the steps the plan marks (w_lds) are staged once per workgroup in LDS; a float twin's filters can
 // exceed the LDS, and the plan leaves the largest ones in HBM, where the lanes read them through the caches.
+// Depthwise convolution: output channel oc is one chain over fy, then fx, of input channel oc / depth_multiplier times filter [fy][fx][oc] (the tensor's own
+// [kh][kw][out_c] order, in LDS or HBM as a convolution's), then + bias (+ 0.0f where the node has none: the plan uploads zeros), then the fused
+// activation's clamp, which the float op honours (depthwise_conv.cc:582-603).
 // ADD: clamp(a + b), one rounded add; whatever the operands hold (+-0, subnormals, +-inf, NaN) meets the same instruction as in the reference.
 // MAX_POOL_2D behind either: std::max over the window's in-image RESULTS in the reference's order (max = max < v ? v : max from lowest(): a NaN never wins),
 // then the pool's own clamp.
@@ -33,7 +36,7 @@ __global__ __launch_bounds__(KWS_WAVE * KWS_NNRES_WAVES_MAX) void kws_nnres_f32_
     float *sp = (float *)smem_raw;
     for (int s = 0; s < N.n_steps; ++s) {
         const KwsResStepF32 &k = N.st[s];
-        if (k.g.kind != KWS_RES_CONV) continue;
+        if (k.g.kind == KWS_RES_ADD) continue;
         if (k.w_lds) {
             const int nw = k.g.out_c * k.g.kh * k.g.krow;
             for (int i = threadIdx.x; i < nw; i += blockDim.x) sp[i] = k.w[i];
@@ -100,6 +103,39 @@ __global__ __launch_bounds__(KWS_WAVE * KWS_NNRES_WAVES_MAX) void kws_nnres_f32_
                                 }
                                 xr += g.a_pitch;
                                 wr += krow;
+                            }
+                            v = nnres_clamp(total + bv, k.act_min, k.act_max);
+                            mx = mx < v ? v : mx;                               // std::max(mx, v)
+                        }
+                    dbase[py * dpitch + px * out_c + oc] = g.has_pool ? nnres_clamp(mx, k.pool_min, k.pool_max) : v;
+                }
+            } else if (g.kind == KWS_RES_DW) {
+                const float *wb = k.w;                                // HBM, unless staged
+                if (k.w_lds) { wb = bp; bp += (out_c * g.kh * g.krow + 3) & ~3; }
+                const float *bias = bp;
+                bp += (out_c + 3) & ~3;
+                const float *cur = wbase + g.a_base + g.a_off;
+                const int in_c = g.in_c, xstep = g.sw * in_c, ystep = g.sh * g.a_pitch, wrow = g.kw * out_c;
+                for (int item = lane; item < n_items; item += 64) {
+                    const int pos = item / out_c, oc = item - pos * out_c;
+                    const int py = pos / g.pool_w, px = pos - py * g.pool_w;
+                    const int cy0 = py * g.psh - g.ppt, cx0 = px * g.psw - g.ppl;
+                    const int wy0 = max(0, -cy0), wy1 = min(g.ph, g.out_h - cy0), wx0 = max(0, -cx0), wx1 = min(g.pw, g.out_w - cx0);
+                    const int ic = g.dm == 1 ? oc : oc / g.dm;
+                    const float bv = bias[oc];
+                    float mx = -FLT_MAX, v = 0.0f;
+                    for (int wy = wy0; wy < wy1; ++wy)
+                        for (int wx = wx0; wx < wx1; ++wx) {
+                            const float *xr = cur + (cy0 + wy) * ystep + (cx0 + wx) * xstep + ic;
+                            const float *wr = wb + oc;
+                            float total = 0.0f;
+                            for (int fy = 0; fy < g.kh; ++fy) {
+                                for (int fx = 0; fx < g.kw; ++fx) {
+                                    const float prod = xr[fx * in_c] * wr[fx * out_c];
+                                    total += prod;
+                                }
+                                xr += g.a_pitch;
+                                wr += wrow;
                             }
                             v = nnres_clamp(total + bv, k.act_min, k.act_max);
                             mx = mx < v ? v : mx;                               // std::max(mx, v)

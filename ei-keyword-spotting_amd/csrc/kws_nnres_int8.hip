@@ -1,6 +1,6 @@
-// kws_nnres_int8.hip -- kws_nnres_trunk_kernel: the steps of an int8 residual graph -- CONV_2D [+ MAX_POOL_2D] and ADD(tensor, tensor)
-// [+ MAX_POOL_2D] over H x W x C images, H >= 1 -- in front of kws_dense_i8_kernel.  Replays integer_ops/conv.h:64-116, integer_ops/add.h and
-// integer_ops/pooling.h:82-137.
+// kws_nnres_int8.hip -- kws_nnres_trunk_kernel: the steps of an int8 residual graph or depthwise-separable 2-D graph -- CONV_2D,
+// DEPTHWISE_CONV_2D and ADD(tensor, tensor), each [+ MAX_POOL_2D], over H x W x C images, H >= 1 -- in front of kws_dense_i8_kernel.  Replays
+// integer_ops/conv.h:64-116, integer_ops/depthwise_conv.h:22-120, integer_ops/add.h and integer_ops/pooling.h:82-137.
 //
 // The execution model of kws_nn2d_trunk_kernel (kws_nn2d_int8.hip): one wave per clip, persistent workgroups; per workgroup, once, every step's constants
 // in LDS -- a convolution's weights ([out_c][kh][krow4]) and requantisation constants, an ADD's two operand tables.  Per wave: KWS_RES_SLOTS image buffers.
@@ -11,6 +11,11 @@
 // Convolution: kws_nn2d_trunk_kernel's arithmetic -- a lane owns one pooled output (py, px, oc), a filter row is a run of v_dot4 over operand words
 // assembled with v_alignbyte from aligned LDS words, the window's largest raw accumulator is requantised once (max commutes with the non-decreasing
 // requantisation; the plan refuses what would break that).
+// Depthwise convolution: output channel oc reads input channel oc / depth_multiplier alone; the filter stays in the tensor's own [kh][kw][out_c] order, so
+// at one tap the lanes of a position read neighbouring weight bytes and (depth multiplier 1) neighbouring image bytes -- one byte per lane, no two lanes on
+// different dwords of a bank before 64 bytes are covered.  The same bias folding (a padding byte is the zero point and adds 0), the same single
+// requantisation of the window's largest accumulator; the clamp is the int8 range whatever the node's fused activation says (depthwise_conv.cc:618-620:
+// the plan sets act_min / act_max so).
 // ADD: o = clamp(MBQM(q1[a] + q2[b], mo, so) + z_out), q1 / q2 the operands' 256-entry tables (the host built them with the reference's arithmetic:
 // (x - z) << 20 through the operand's multiplier).  ADD is not monotone in the pair, so a pool behind it takes the maximum of the RESULTS at the positions
 // of its window.
@@ -28,7 +33,7 @@ __global__ __launch_bounds__(KWS_WAVE * KWS_NNRES_WAVES_MAX) void kws_nnres_trun
     unsigned char *sp = smem_raw;
     for (int s = 0; s < N.n_steps; ++s) {
         const KwsResStep &k = N.st[s];
-        if (k.g.kind == KWS_RES_CONV) {
+        if (k.g.kind != KWS_RES_ADD) {
             for (int i = threadIdx.x * 4; i < k.w_bytes; i += blockDim.x * 4) *(int *)(sp + i) = *(const int *)(k.w + i);
             sp += (k.w_bytes + 15) & ~15;
             for (int i = threadIdx.x; i < k.g.out_c * 4; i += blockDim.x) ((int *)sp)[i] = k.rq[i];
@@ -104,6 +109,36 @@ __global__ __launch_bounds__(KWS_WAVE * KWS_NNRES_WAVES_MAX) void kws_nnres_trun
                                     lo = hi;
                                 }
                                 xr += g.a_pitch >> 2;
+                            }
+                            m = max(m, acc);
+                        }
+                    const int r = nn_requant(m, nn_rq_of(rqt, oc), k.out_zp, k.act_min, k.act_max);
+                    dbase[py * dpitch + px * out_c + oc] = (int8_t)r;
+                    if (tp) tp[item] = (int8_t)r;
+                }
+            } else if (g.kind == KWS_RES_DW) {
+                const int8_t *wb = (const int8_t *)bp;
+                bp += (k.w_bytes + 15) & ~15;
+                const int4 *rqt = (const int4 *)bp;
+                bp += out_c * 16;
+                const int8_t *cur = wbase + g.a_base + g.a_off;
+                const int in_c = g.in_c, xstep = g.sw * in_c, ystep = g.sh * g.a_pitch, wrow = g.kw * out_c;
+                for (int item = lane; item < n_items; item += 64) {
+                    const int pos = item / out_c, oc = item - pos * out_c;
+                    const int py = pos / g.pool_w, px = pos - py * g.pool_w;
+                    const int cy0 = py * g.psh - g.ppt, cx0 = px * g.psw - g.ppl;
+                    const int wy0 = max(0, -cy0), wy1 = min(g.ph, g.out_h - cy0), wx0 = max(0, -cx0), wx1 = min(g.pw, g.out_w - cx0);
+                    const int ic = g.dm == 1 ? oc : oc / g.dm;
+                    int m = (int)0x80000000;
+                    for (int wy = wy0; wy < wy1; ++wy)
+                        for (int wx = wx0; wx < wx1; ++wx) {
+                            const int8_t *xr = cur + (cy0 + wy) * ystep + (cx0 + wx) * xstep + ic;
+                            const int8_t *wr = wb + oc;
+                            int acc = 0;
+                            for (int fy = 0; fy < g.kh; ++fy) {
+                                for (int fx = 0; fx < g.kw; ++fx) acc += (int)wr[fx * out_c] * (int)xr[fx * in_c];
+                                xr += g.a_pitch;
+                                wr += wrow;
                             }
                             m = max(m, acc);
                         }

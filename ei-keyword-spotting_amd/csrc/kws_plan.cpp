@@ -597,6 +597,7 @@ static EI_IMPULSE_ERROR build_nn2d_i8(kws_handle *h, size_t &i, int &cur)
 
 // residual graphs (below, behind the float helpers)
 static bool h_is_residual(const Model &m);
+static bool h_is_dw2d(const Model &m);
 static EI_IMPULSE_ERROR build_nnres_i8(kws_handle *h, size_t &i, int &cur);
 
 // Recognise the Edge Impulse 1-D CNN family and fold its per-model constants.
@@ -628,8 +629,9 @@ EI_IMPULSE_ERROR build_nn_plan(kws_handle *h)
         }
         return true;
     };
-    if (h_is_residual(m)) {
-        // a residual graph: its steps in a plan of their own, then the dense stack -- always, as for a 2-D graph
+    if (h_is_residual(m) || h_is_dw2d(m)) {
+        // a residual graph or a 2-D graph with depthwise steps: its steps in a plan of their own, then the dense stack -- always,
+        // as for a 2-D graph
         if (EI_IMPULSE_ERROR e = build_nnres_i8(h, i, cur)) return e;
         if (EI_IMPULSE_ERROR e = build_dense_i8(h, i, cur, h->nnres.out_n)) return e;
         h->handoff.trunkres = &h->nnres;
@@ -928,6 +930,22 @@ static bool h_is_residual(const Model &m)
         if (nd.op == OP_ADD && !m.t[nd.in[0]].is_const && !m.t[nd.in[1]].is_const) return true;
     return false;
 }
+// A 2-D graph -- the tensor flowing into its first convolution is [1][H][W][C] with H > 1 and W > 1 (h_is_2d's rule) -- that holds a DEPTHWISE_CONV_2D takes
+// the step trunks too, ADD or not.  A 1-D graph with depthwise blocks and no tensor + tensor ADD keeps the block kernels.
+static bool h_is_dw2d(const Model &m)
+{
+    bool any_dw = false, first = true, two_d = false;
+    for (const Node &nd : m.n) {
+        if (nd.op != OP_CONV_2D && nd.op != OP_DEPTHWISE_CONV_2D) continue;
+        if (first) {
+            const Tensor &x = m.t[nd.in[0]];
+            two_d = x.dims.size() == 4 && x.dims[0] == 1 && x.dims[1] > 1 && x.dims[2] > 1;
+            first = false;
+        }
+        any_dw = any_dw || nd.op == OP_DEPTHWISE_CONV_2D;
+    }
+    return two_d && any_dw;
+}
 
 // LDS of the residual trunks at n_waves waves per workgroup, laid out as kws_nnres_trunk_kernel / kws_nnres_f32_trunk_kernel walk it -- per workgroup every
 // step's constants, per wave the KWS_RES_SLOTS image slots -- and the wave count their launchers pick (kws_nnres.h)
@@ -935,7 +953,7 @@ size_t kws_nnres_smem_bytes(const KwsResPlan &N, int n_waves)
 {
     size_t s = 0;
     for (int k = 0; k < N.n_steps; ++k)
-        s += N.st[k].g.kind == KWS_RES_CONV ? (((size_t)N.st[k].w_bytes + 15) & ~(size_t)15) + (size_t)N.st[k].g.out_c * 16 : (size_t)KWS_NNRES_ADD_TAB_BYTES;
+        s += N.st[k].g.kind != KWS_RES_ADD ? (((size_t)N.st[k].w_bytes + 15) & ~(size_t)15) + (size_t)N.st[k].g.out_c * 16 : (size_t)KWS_NNRES_ADD_TAB_BYTES;
     return s + (size_t)n_waves * (size_t)N.wave_bytes;
 }
 int kws_nnres_waves(const KwsResPlan &N)
@@ -949,7 +967,7 @@ size_t kws_nnres_f32_smem_bytes(const KwsResPlanF32 &N, int n_waves)
     size_t s = 0;
     for (int k = 0; k < N.n_steps; ++k) {
         const KwsResGeom &g = N.st[k].g;
-        if (g.kind != KWS_RES_CONV) continue;
+        if (g.kind == KWS_RES_ADD) continue;
         s += sizeof(float) * (size_t)((N.st[k].w_lds ? (g.out_c * g.kh * g.krow + 3) & ~3 : 0) + ((g.out_c + 3) & ~3));
     }
     return s + (size_t)n_waves * (size_t)N.wave_bytes;
@@ -969,7 +987,7 @@ struct HResImage {
     int slot = -1, rows = 0, pitch = 0, bytes = 0, base = 0;
 };
 struct HResStep { KwsResGeom g; const Node *nd; int a, b, dst, x_id, y_id, act, pool_act, pad_t, pad_l; };
-struct HResGraph { std::vector<HResImage> img; std::vector<HResStep> st; int final_img = -1, wave_bytes = 0, n_adds = 0; };
+struct HResGraph { std::vector<HResImage> img; std::vector<HResStep> st; int final_img = -1, wave_bytes = 0, n_adds = 0, n_dw = 0; };
 
 // The steps of a residual graph: every node up to the first FULLY_CONNECTED, in node order.  RESHAPEs that keep the quantisation are renamings: a tensor id
 // maps to an image and to how its dims spell that image -- as they are ([1][H][W][C]), with H and W exchanged (one of them 1: the same bytes, what Keras'
@@ -1055,9 +1073,8 @@ static EI_IMPULSE_ERROR h_res_walk(const Model &m, size_t &i, int &cur, bool is_
         }
         if ((int)G.st.size() >= KWS_RES_STEPS_MAX && nd.op != OP_MAX_POOL_2D)
             return fail(KWS_ERROR_UNSUPPORTED_MODEL, "node %zu: more than %d steps (CONV_2D / ADD) in a residual graph", i, KWS_RES_STEPS_MAX);
-        if (nd.op == OP_DEPTHWISE_CONV_2D)
-            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: DEPTHWISE_CONV_2D inside a residual graph is not served (the family is CONV_2D, ADD and MAX_POOL_2D)", i);
-        if (nd.op == OP_CONV_2D) {
+        if (nd.op == OP_CONV_2D || nd.op == OP_DEPTHWISE_CONV_2D) {
+            const bool dw = nd.op == OP_DEPTHWISE_CONV_2D;
             if (EI_IMPULSE_ERROR e = readable(i, x, "conv input")) return e;
             if (kind_of[x] != PLAIN) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: its input is a renamed tensor (only MAX_POOL_2D and ADD read those)", i);
             if (EI_IMPULSE_ERROR e = produce(i, y)) return e;
@@ -1068,9 +1085,17 @@ static EI_IMPULSE_ERROR h_res_walk(const Model &m, size_t &i, int &cur, bool is_
                 return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: filter and output must be 4-D tensors of the graph's type, one batch", i);
             HResStep S{};
             KwsResGeom &g = S.g;
-            g.kind = KWS_RES_CONV;
-            g.in_c = src.c; g.out_c = w.dims[0]; g.kh = w.dims[1]; g.kw = w.dims[2];
-            if (g.out_c > 64 || g.kh > KWS_RES_K_MAX || g.kw > KWS_RES_K_MAX || w.dims[3] != g.in_c)
+            g.kind = dw ? KWS_RES_DW : KWS_RES_CONV;
+            g.in_c = src.c; g.out_c = w.dims[dw ? 3 : 0]; g.kh = w.dims[1]; g.kw = w.dims[2]; g.dm = 1;
+            if (dw) {
+                // the filter is [1][kh][kw][in_c * depth_multiplier]; every bound before any product (in_c <= 64: the images' bound)
+                g.dm = nd.p[6];
+                if (w.dims[0] != 1 || g.dm < 1 || g.dm > 64 || g.out_c < 1 || g.out_c > 64 || g.out_c != g.in_c * g.dm || g.kh < 1 || g.kh > KWS_RES_K_MAX || g.kw < 1 ||
+                    g.kw > KWS_RES_K_MAX)
+                    return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: DEPTHWISE_CONV_2D with a [%d][%d][%d][%d] filter and depth multiplier %d over %d channels is not "
+                                "served (the filter must be [1][kh][kw][channels x multiplier], multiplier >= 1, sides 1 .. %d, at most 64 output channels)", i,
+                                w.dims[0], w.dims[1], w.dims[2], w.dims[3], nd.p[6], g.in_c, KWS_RES_K_MAX);
+            } else if (g.out_c > 64 || g.kh > KWS_RES_K_MAX || g.kw > KWS_RES_K_MAX || w.dims[3] != g.in_c)
                 return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: a %d x %d filter over %d (filter: %d) -> %d channels is outside the residual kernels' limits (filter "
                             "sides 1 .. %d, at most 64 channels)", i, g.kh, g.kw, g.in_c, w.dims[3], g.out_c, KWS_RES_K_MAX);
             if (!w.is_const || (bias && (!bias->is_const || bias->type != (is_float ? TYPE_F32 : TYPE_I32) || (long)bias->nbytes != 4l * g.out_c)))
@@ -1080,7 +1105,8 @@ static EI_IMPULSE_ERROR h_res_walk(const Model &m, size_t &i, int &cur, bool is_
             if (g.sh < 1 || g.sh > KWS_NN2D_STRIDE_MAX || g.sw < 1 || g.sw > KWS_NN2D_STRIDE_MAX)
                 return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: stride %d x %d is outside 1 .. %d", i, g.sh, g.sw, KWS_NN2D_STRIDE_MAX);
             if (nd.p[4] != 1 || nd.p[5] != 1)
-                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: dilation %d x %d: a residual graph's convolutions are not dilated", i, nd.p[5], nd.p[4]);
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: %sdilation %d x %d: a residual graph's convolutions are not dilated", i,
+                            dw ? "DEPTHWISE_CONV_2D with " : "", nd.p[5], nd.p[4]);
             if ((padding != 1 && padding != 2) || S.act < 0 || S.act > 3)
                 return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu: padding %d / fused activation %d", i, padding, S.act);
             g.out_h = h_out_size(padding, src.h, g.kh, g.sh, 1); g.out_w = h_out_size(padding, src.w, g.kw, g.sw, 1);
@@ -1088,7 +1114,8 @@ static EI_IMPULSE_ERROR h_res_walk(const Model &m, size_t &i, int &cur, bool is_
                 return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %zu output shape: the tensor is %d x %d x %d, kernels/padding.h gives %d x %d x %d", i, yt.dims[1], yt.dims[2],
                             yt.dims[3], g.out_h, g.out_w, g.out_c);
             S.pad_t = h_pad_amount(g.sh, 1, src.h, g.kh, g.out_h); S.pad_l = h_pad_amount(g.sw, 1, src.w, g.kw, g.out_w);
-            g.krow = g.kw * g.in_c; g.krow4 = (g.krow + 3) & ~3;
+            g.krow = dw ? g.kw : g.kw * g.in_c; g.krow4 = (g.krow + 3) & ~3;
+            G.n_dw += dw ? 1 : 0;
             src.mt = std::max(src.mt, S.pad_t); src.ml = std::max(src.ml, S.pad_l);
             src.ext_r = std::max(src.ext_r, (g.out_h - 1) * g.sh + g.kh - S.pad_t);
             src.ext_c = std::max(src.ext_c, (g.out_w - 1) * g.sw + g.kw - S.pad_l);
@@ -1232,7 +1259,7 @@ static EI_IMPULSE_ERROR build_nnres_i8(kws_handle *h, size_t &i, int &cur)
     P.n_features = (int)m.nn_input_frame_size;
     P.in_base = in.base; P.in_off = in.mt * in.pitch + in.ml * in.c; P.in_pitch = in.pitch; P.in_bytes = in.bytes; P.in_zp = m.t[in.tid].zero[0];
     P.in_h = in.h; P.in_row = in.w * in.c;
-    P.wave_bytes = G.wave_bytes; P.n_adds = G.n_adds;
+    P.wave_bytes = G.wave_bytes; P.n_adds = G.n_adds; P.n_dw = G.n_dw;
     for (size_t s = 0; s < G.st.size(); s++) {
         const HResStep &S = G.st[s];
         const Node &nd = *S.nd;
@@ -1243,7 +1270,43 @@ static EI_IMPULSE_ERROR build_nnres_i8(kws_handle *h, size_t &i, int &cur)
         k.out_zp = y.zero[0]; k.d_zp = y.zero[0];
         h_act_range(S.act, y.scale[0], y.zero[0], &k.act_min, &k.act_max);
         EI_IMPULSE_ERROR e;
-        if (g.kind == KWS_RES_CONV) {
+        if (g.kind == KWS_RES_DW) {
+            // integer_ops/depthwise_conv.h:22-120: weights stay [kh][kw][out_c], bias_eff = bias + input_offset * sum(w[.][.][oc]); the int8 depthwise op clamps
+            // to the int8 range and IGNORES its fused activation (depthwise_conv.cc:618-620), as the 1-D kernels do
+            const int node_i = (int)(S.nd - &m.n[0]);
+            const Tensor &x = m.t[S.x_id], &w = m.t[nd.in[1]];
+            const Tensor *bias = (nd.in.size() > 2 && nd.in[2] >= 0) ? &m.t[nd.in[2]] : nullptr;
+            const size_t nw = (size_t)g.kh * g.kw * g.out_c;
+            std::vector<int8_t> wp((nw + 3) & ~(size_t)3, 0);
+            k.w_bytes = (int)wp.size();
+            k.act_min = -128; k.act_max = 127;
+            std::vector<int32_t> rq((size_t)g.out_c * 4, 0);
+            const int32_t *bd = bias ? (const int32_t *)bias->data.data() : nullptr;
+            const int32_t in_off = -x.zero[0];
+            const bool per_channel = w.scale.size() > 1;
+            if (w.data.size() < nw || (bias && bias->data.size() < (size_t)g.out_c * 4))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %d: DEPTHWISE_CONV_2D constant data", node_i);
+            if (w.scale.empty() || (per_channel && ((int)w.scale.size() != g.out_c || w.qdim != 3)))
+                return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %d: DEPTHWISE_CONV_2D per-channel scale count (one scale, or one per output channel along dimension 3)",
+                            node_i);
+            memcpy(wp.data(), w.data.data(), nw);
+            for (int oc = 0; oc < g.out_c; oc++) {
+                int64_t wsum = 0, wabs = 0;
+                for (int t = 0; t < g.kh * g.kw; t++) { const int v = wp[(size_t)t * g.out_c + oc]; wsum += v; wabs += std::abs(v); }
+                rq[(size_t)oc * 4] = (int32_t)((bd ? bd[oc] : 0) + (int64_t)in_off * wsum);
+                const double eff = (double)x.scale[0] * (double)(per_channel ? w.scale[oc] : w.scale[0]) / (double)y.scale[0];
+                int32_t mult; int sh;
+                h_quantize_multiplier(eff, &mult, &sh);          // kernel_util_lite.cc:89-103
+                rq[(size_t)oc * 4 + 1] = mult; rq[(size_t)oc * 4 + 2] = sh;
+                if (mult < 0 || sh < -31)
+                    return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %d: DEPTHWISE_CONV_2D channel %d: requantisation multiplier", node_i, oc);
+                if (sh > 0 && h_left_shift_overflows(wabs, in_off, bd ? bd[oc] : 0, sh))
+                    return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %d: DEPTHWISE_CONV_2D channel %d: requantisation shifts left by %d and (sum|w| * max|x| + |bias|) "
+                                "<< %d can pass 2^31 - 1", node_i, oc, sh, sh);
+            }
+            if ((e = h->upload(wp, &k.w))) return e;
+            if ((e = h->upload(rq, &k.rq))) return e;
+        } else if (g.kind == KWS_RES_CONV) {
             // as build_nn2d_i8: weights -> [out_c][kh][krow4], bias_eff = bias + input_offset * sum(w)   (integer_ops/conv.h:64-113)
             const Tensor &x = m.t[S.x_id], &w = m.t[nd.in[1]];
             const Tensor *bias = (nd.in.size() > 2 && nd.in[2] >= 0) ? &m.t[nd.in[2]] : nullptr;
@@ -1313,11 +1376,13 @@ static EI_IMPULSE_ERROR build_nnres_i8(kws_handle *h, size_t &i, int &cur)
                     kws_nnres_smem_bytes(P, KWS_NNRES_WAVES_MIN), KWS_NNRES_WAVES_MIN, KWS_NNRES_LDS_I8);
     h->pooled_tap_bytes += P.tap_bytes;
     h->n_res_adds = P.n_adds;
+    h->n_res_dw = P.n_dw;
+    h->res_trunk = true;
     return EI_IMPULSE_OK;
 }
 
 // the float twin of build_nnres_i8: constants as they are, finite weights required (h_first_non_finite).  Filters are staged in LDS while the graph then
-// still fits at KWS_NNRES_WAVES_MIN waves; the largest ones stay in HBM otherwise.
+// still fits at KWS_NNRES_WAVES_STAGE waves; the largest ones stay in HBM otherwise.
 static EI_IMPULSE_ERROR build_nnres_f32(kws_handle *h, size_t &i, int &cur)
 {
     const Model &m = h->model;
@@ -1328,7 +1393,7 @@ static EI_IMPULSE_ERROR build_nnres_f32(kws_handle *h, size_t &i, int &cur)
     const HResImage &in = G.img[0];
     P.n_features = (int)m.nn_input_frame_size;
     P.in_base = in.base; P.in_off = in.mt * in.pitch + in.ml * in.c; P.in_pitch = in.pitch; P.in_bytes = in.bytes; P.in_h = in.h; P.in_row = in.w * in.c;
-    P.wave_bytes = G.wave_bytes; P.n_adds = G.n_adds;
+    P.wave_bytes = G.wave_bytes; P.n_adds = G.n_adds; P.n_dw = G.n_dw;
     auto floats = [](const Tensor &t) { return std::vector<float>((const float *)t.data.data(), (const float *)t.data.data() + t.data.size() / 4); };
     for (size_t s = 0; s < G.st.size(); s++) {
         const HResStep &S = G.st[s];
@@ -1339,12 +1404,16 @@ static EI_IMPULSE_ERROR build_nnres_f32(kws_handle *h, size_t &i, int &cur)
         h_act_range_f32(S.act, &k.act_min, &k.act_max);
         h_act_range_f32(S.pool_act, &k.pool_min, &k.pool_max);
         P.n_steps++;
-        if (g.kind != KWS_RES_CONV) continue;
+        if (g.kind == KWS_RES_ADD) continue;
+        // (a depthwise filter [1][kh][kw][out_c] goes as it is too: krow = kw, the same out_c * kh * krow values)
         const Tensor &w = m.t[nd.in[1]];
         const Tensor *bias = (nd.in.size() > 2 && nd.in[2] >= 0) ? &m.t[nd.in[2]] : nullptr;
         std::vector<float> wv = floats(w), bv((size_t)g.out_c, 0.0f);
         if (wv.size() != (size_t)g.out_c * g.kh * g.krow) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu: filter size", s);
-        if (const long bad = h_first_non_finite(wv); bad >= 0)
+        if (const long bad = h_first_non_finite(wv); bad >= 0 && g.kind == KWS_RES_DW)
+            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv %d: DEPTHWISE_CONV_2D weight tensor %d holds a non-finite value (element %ld): the float kernels need "
+                        "finite weights", (int)(S.nd - &m.n[0]), nd.in[1], bad);
+        else if (bad >= 0)
             return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu: weight tensor %d holds a non-finite value (element %ld): the float kernels need finite weights", s,
                         nd.in[1], bad);
         if (bias) { bv = floats(*bias); if (bv.size() != (size_t)g.out_c) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "conv step %zu: bias size", s); }
@@ -1355,17 +1424,20 @@ static EI_IMPULSE_ERROR build_nnres_f32(kws_handle *h, size_t &i, int &cur)
     }
     const KwsResGeom &lg = P.st[P.n_steps - 1].g;
     P.out_n = lg.pool_h * lg.pool_w * lg.out_c;
-    while (kws_nnres_f32_waves(P) == 0) {                 // the largest staged filter goes back to HBM
+    while (kws_nnres_f32_smem_bytes(P, KWS_NNRES_WAVES_STAGE) > KWS_NNRES_LDS_F32) {                 // the largest staged filter goes back to HBM
         int big = -1;
         for (int s = 0; s < P.n_steps; ++s)
-            if (P.st[s].g.kind == KWS_RES_CONV && P.st[s].w_lds &&
+            if (P.st[s].g.kind != KWS_RES_ADD && P.st[s].w_lds &&
                 (big < 0 || P.st[s].g.out_c * P.st[s].g.kh * P.st[s].g.krow > P.st[big].g.out_c * P.st[big].g.kh * P.st[big].g.krow)) big = s;
-        if (big < 0)
-            return fail(KWS_ERROR_UNSUPPORTED_MODEL, "float residual model needs %zu B of LDS at %d waves per workgroup (at most %d): its images do not fit the kernel's "
-                        "LDS budget", kws_nnres_f32_smem_bytes(P, KWS_NNRES_WAVES_MIN), KWS_NNRES_WAVES_MIN, KWS_NNRES_LDS_F32);
+        if (big < 0) break;                               // (the images alone: fewer waves, down to KWS_NNRES_WAVES_MIN)
         P.st[big].w_lds = 0;
     }
+    if (kws_nnres_f32_waves(P) == 0)
+        return fail(KWS_ERROR_UNSUPPORTED_MODEL, "float residual model needs %zu B of LDS at %d waves per workgroup (at most %d): its images do not fit the kernel's "
+                    "LDS budget", kws_nnres_f32_smem_bytes(P, KWS_NNRES_WAVES_MIN), KWS_NNRES_WAVES_MIN, KWS_NNRES_LDS_F32);
     h->n_res_adds = P.n_adds;
+    h->n_res_dw = P.n_dw;
+    h->res_trunk = true;
     return EI_IMPULSE_OK;
 }
 
@@ -1392,7 +1464,7 @@ static EI_IMPULSE_ERROR build_nn_plan_f32(kws_handle *h)
     auto floats = [](const Tensor &t) { return std::vector<float>((const float *)t.data.data(), (const float *)t.data.data() + t.nbytes / 4); };
     // a residual graph: its steps in a plan of their own (this one keeps n_blocks = 0), then the dense stack -- always
     int inputs2d = 0;
-    const bool residual = h_is_residual(m);
+    const bool residual = h_is_residual(m) || h_is_dw2d(m);        // (a 2-D graph with depthwise steps takes the step trunks too)
     if (residual) {
         if (EI_IMPULSE_ERROR e = build_nnres_f32(h, i, cur)) return e;
         inputs2d = h->nnresf.out_n;

@@ -247,8 +247,8 @@ struct KwsNn2dPlanF32 {
 // bytes of image b's LDS buffer: the padded image plus 16 bytes the last filter row's zero-weight tail may read (int8), rounded to 16
 __host__ __device__ static inline int kws_nn2d_img_bytes(const KwsConv2dGeom &g, int elem) { return (g.img_rows * g.img_pitch * elem + 16 + 15) & ~15; }
 
-// ---- residual graphs: a list of steps -- CONV_2D [-> MAX_POOL_2D] or ADD(tensor, tensor) [-> MAX_POOL_2D] -- over H x W x C images (H >= 1)
-//      in front of a dense stack.  Plans of their own again, read by kws_nnres_trunk_kernel (kws_nnres_int8.hip) / kws_nnres_f32_trunk_kernel
+// ---- residual graphs and depthwise-separable 2-D graphs: a list of steps -- CONV_2D, DEPTHWISE_CONV_2D or ADD(tensor, tensor),
+//      each [-> MAX_POOL_2D] -- over H x W x C images (H >= 1) in front of a dense stack.  Plans of their own again, read by kws_nnres_trunk_kernel (kws_nnres_int8.hip) / kws_nnres_f32_trunk_kernel
 //      (kws_nnres_f32.hip) alone and reached through the hand-off (KwsHandoff::trunkres / trunkres_f32).
 //      Every tensor lives ONCE in LDS, in one of KWS_RES_SLOTS per-wave buffers the plan's liveness analysis assigns, behind a margin that is the largest
 //      top / left padding any of its consumers needs; a consumer with less padding starts reading further in (a_off / b_off).
@@ -257,13 +257,15 @@ __host__ __device__ static inline int kws_nn2d_img_bytes(const KwsConv2dGeom &g,
 #define KWS_RES_K_MAX 16                   // filter side (the 1-D family's tap bound); pool windows keep KWS_NN2D_K_MAX
 #define KWS_RES_CONV 0
 #define KWS_RES_ADD 1
+#define KWS_RES_DW 2
 struct KwsResGeom {
-    int kind;                              // KWS_RES_CONV / KWS_RES_ADD
+    int kind;                              // KWS_RES_CONV / KWS_RES_ADD / KWS_RES_DW
     int in_c, out_c, kh, kw, sh, sw;       // ADD: in_c = out_c, 1 x 1, stride 1
+    int dm;                                // depthwise: the depth multiplier, out_c = in_c * dm and output channel oc reads input channel oc / dm (else 1)
     int out_h, out_w;                      // the step's own output (before the pool)
     int ph, pw, psh, psw, ppt, ppl;        // pool window, stride, padding above / left (no pooling node: 1, 1, 1, 1, 0, 0)
     int pool_h, pool_w, has_pool;
-    int krow, krow4;                       // conv: operands of one filter row, kw * in_c, and rounded up to a multiple of 4
+    int krow, krow4;                       // conv: operands of one filter row, kw * in_c, and rounded up to a multiple of 4; depthwise: kw (per channel)
     // sources: where the tensor's slot starts in the wave's LDS region (elements; a multiple of 16 bytes), element offset of the first element the step's
     // output (0, 0) reads (the tensor's margin minus this step's own padding), elements per image row.  ADD: a and b (they may be the same tensor); conv: a
     int a_base, a_off, a_pitch, b_base, b_off, b_pitch;
@@ -277,14 +279,14 @@ struct KwsResStep {
     int out_zp, act_min, act_max;
     int add_mult, add_shift;               // ADD: the output multiplier (< 1: add_shift <= 0)
     int w_bytes;
-    const int8_t *w;                       // conv: [out_c][kh][krow4], zero padded
-    const int32_t *rq;                     // conv: [out_c] x (bias_eff, multiplier, shift, 0); ADD: two 256-entry tables, q1 of operand a and q2 of operand b
+    const int8_t *w;                       // conv: [out_c][kh][krow4], zero padded; depthwise: [kh][kw][out_c], the tensor's own order (w_bytes rounded up to 4)
+    const int32_t *rq;                     // conv / depthwise: [out_c] x (bias_eff, multiplier, shift, 0); ADD: two 256-entry tables, q1 of operand a and q2 of operand b
                                            // by value + 128 (integer_ops/add.h: the operand shifted left by 20, through its own multiplier)
 };
 struct KwsResPlan {
     int n_steps, n_features, out_n;        // out_n: the last step's (pooled) output, flattened NHWC (= the dense stack's inputs)
     int tap_bytes;                         // of every step's (pooled) output, one after another
-    int n_adds;
+    int n_adds, n_dw;
     int in_base, in_off, in_pitch, in_bytes, in_zp, in_h, in_row;     // the reshaped input tensor's image: in_h rows of in_row values
     int wave_bytes;                        // LDS per wave: the KWS_RES_SLOTS slots, each a multiple of 16 bytes
     KwsResStep st[KWS_RES_STEPS_MAX];
@@ -294,11 +296,11 @@ struct KwsResStepF32 {
     float act_min, act_max, pool_min, pool_max;     // the convolution's / the ADD's clamp, the pool's
     int w_lds;                             // conv: the filter is staged in LDS (else the lanes read it from HBM through the caches: a float twin's filters can
                                            // exceed the LDS -- the plan spills the largest ones)
-    const float *w;                        // [out_c][kh][krow]
+    const float *w;                        // [out_c][kh][krow]; depthwise: [kh][kw][out_c] (either way the filter tensor as it is, out_c * kh * krow values)
     const float *bias;                     // [out_c]
 };
 struct KwsResPlanF32 {
-    int n_steps, n_features, out_n, n_adds;
+    int n_steps, n_features, out_n, n_adds, n_dw;
     int in_base, in_off, in_pitch, in_bytes, in_h, in_row;
     int wave_bytes;
     KwsResStepF32 st[KWS_RES_STEPS_MAX];

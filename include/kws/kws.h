@@ -83,12 +83,22 @@ int kws_conv2d_block_count(const kws_handle *h);         /* CONV_2D blocks of a 
  * twice included), each optionally followed by a MAX_POOL_2D that is the only reader of its input.  RESHAPEs that keep the quantisation are renamings.  At most 4
  * tensors are live at once.  A flatten, 1 .. 4 FULLY_CONNECTED layers and SOFTMAX follow.  Served bit-exactly (float32: logits bit for bit, scores within 1e-6) by
  * kws_nnres_trunk_kernel / kws_nnres_f32_trunk_kernel in front of the dense kernels, through every entry point.  Refused with KWS_ERROR_UNSUPPORTED_MODEL
- * (kws_last_error names the node and the reason): a broadcasting ADD, a constant ADD operand or DEPTHWISE_CONV_2D in such a graph, dilation other than 1, more
+ * (kws_last_error names the node and the reason): a broadcasting ADD, a constant ADD operand in such a graph, dilation other than 1, more
  * than 16 steps or 4 live tensors, a pool that shares its input with another reader, an int8 pool with a fused activation, output dims that disagree with
  * kernels/padding.h, non-finite float weights, left-shifting conv requantisation past the 1-D blocks' bound, an int8 ADD whose output multiplier
- * 2 max(s1, s2) / (2^20 s_out) is not below 1, and a graph that does not fit the kernels' LDS budget at four waves per workgroup.  KWS_MODE_EXACT only, as a 2-D
+ * 2 max(s1, s2) / (2^20 s_out) is not below 1, and a graph that does not fit the kernels' LDS budget at two waves per workgroup (four before DESIGN 4.18).  KWS_MODE_EXACT only, as a 2-D
  * graph.  tap_pooled of kws_nn_batch_device holds every step's (pooled) output in step order, then the hidden dense outputs. */
 int kws_residual_add_count(const kws_handle *h);         /* tensor + tensor ADDs of a residual graph; 0 for every other graph (kws_conv2d_block_count stays 0 for a residual graph) */
+/* Depthwise-separable 2-D graphs and depthwise steps next to a skip connection: the step list above takes a third kind, DEPTHWISE_CONV_2D
+ * (filter [1][kh][kw][channels x depth_multiplier], multiplier >= 1, at most 64 output channels, sides 1 .. 16, stride 1 .. 4 per axis, dilation 1, SAME / VALID,
+ * constant bias or none, per-channel scales along dimension 3 or one scale), and the same kernels serve a graph when it has a tensor + tensor ADD (as before) OR
+ * it is a 2-D graph ([1][H][W][C] input image, H > 1 and W > 1) that holds a DEPTHWISE_CONV_2D -- Hello-Edge DS-CNN, MobileNet-style trunks, MobileNetV2 inverted
+ * residuals, MatchboxNet-style separable blocks with a shortcut.  int8 depthwise steps clamp to the int8 range whatever their fused activation says, as the
+ * reference's kernel does; float32 ones honour it.  A 1-D graph with depthwise blocks and no tensor + tensor ADD keeps the block kernels (and the fast mode).
+ * Refused (the message names the node as "conv N:" and says DEPTHWISE_CONV_2D): a filter of other dims, a multiplier < 1 or one that disagrees with the tensors,
+ * more than 64 output channels, dilation, left-shifting requantisation past the 1-D blocks' bound, non-finite float weights.  KWS_MODE_EXACT only. */
+int kws_depthwise_step_count(const kws_handle *h);       /* DEPTHWISE_CONV_2D steps of a graph the step trunks serve; 0 for every other graph (a 1-D depthwise chain on the
+                                                            block kernels included).  kws_residual_add_count is 0 for a 2-D depthwise graph without ADDs */
 const char *kws_nn_kernel_name(const kws_handle *h);    /* which network kernel serves this model (diagnostics); "kws_nn_sd_kernel" / "kws_nn_f32_sd_kernel" (in front of a
                                                             dense stack: "kws_nn_sd_trunk_kernel + kws_dense_i8_kernel", float32 likewise) for a graph with a strided or dilated block;
                                                             "kws_nn2d_trunk_kernel + kws_dense_i8_kernel" / "kws_nn2d_f32_trunk_kernel + kws_dense_f32_kernel" for a 2-D graph.

@@ -103,9 +103,20 @@ def float_forward(tensors, nodes, t_in, x, stop_before_op=None, on_output=None, 
                 for fx in range(pw):
                     v = np.maximum(v, ap[:, fy:fy + (oh - 1) * sh + 1:sh, fx:fx + (ow - 1) * sw + 1:sw])
             act[o] = fused(v, p[5])
+        elif nd["op"] == 6 and a.ndim == 4:             # DEPTHWISE_CONV_2D over both axes: filter [1][KH][KW][C * p[6]], stride (p[2], p[1]), no dilation
+            w = const[nd["in"][1]]
+            b = const[nd["in"][2]] if len(nd["in"]) > 2 and nd["in"][2] >= 0 else 0.0
+            kh, kw, sh, sw = w.shape[1], w.shape[2], p[2], p[1]
+            ap, oh, ow = padded2d(a, kh, kw, sh, sw, p[0], 0.0)
+            ap = np.repeat(ap, p[6], axis=3)             # output channel oc reads input channel oc // multiplier
+            v = np.zeros((a.shape[0], oh, ow, w.shape[3]))
+            for fy in range(kh):
+                for fx in range(kw):
+                    v += ap[:, fy:fy + (oh - 1) * sh + 1:sh, fx:fx + (ow - 1) * sw + 1:sw] * w[0, fy, fx]
+            act[o] = fused(v + b, p[3])
         elif nd["op"] in (1, 6):                        # CONV_2D / DEPTHWISE_CONV_2D, 1 x K, stride p[1] and dilation p[4] along time
             w = const[nd["in"][1]]
-            b = const[nd["in"][2]]
+            b = const[nd["in"][2]] if len(nd["in"]) > 2 and nd["in"][2] >= 0 else 0.0
             n, in_w, in_c = a.shape
             taps = w.shape[2]
             stride, dil = p[1], p[4]
@@ -190,11 +201,13 @@ def calibrate_residual(tensors, nodes, t_in, x, lift=0.5, lifts=None, per_tensor
     (lifts: {node index: lift} overrides that for a node, whatever its activation).  Then every activation range is settled (calibrate_ranges)."""
     four_d = True
     for idx, nd in enumerate(nodes):
-        if nd["op"] != 1:
+        if nd["op"] not in (1, 6):
             continue
         calibrate_ranges(tensors, nodes[:idx], t_in, x)
         a = float_forward(tensors, nodes[:idx], t_in, x, four_d=four_d)[nd["in"][0]]
-        tw, tb = tensors[nd["in"][1]], tensors[nd["in"][2]]
+        tw = tensors[nd["in"][1]]
+        has_bias = len(nd["in"]) > 2 and nd["in"][2] >= 0
+        tb = tensors[nd["in"][2]] if has_bias else {"data": b""}               # (a depthwise step without a bias tensor: only its weight scales are set)
         if per_tensor:
             tw["scale"], tw["zero"] = [float(np.float32(np.mean(tw["scale"])))], [0]
         act = nd["p"][3]
@@ -209,6 +222,8 @@ def calibrate_residual(tensors, nodes, t_in, x, lift=0.5, lifts=None, per_tensor
             tw["scale"] = [float(np.float32(s_ * (1.5 if act == 3 else 0.5) / sd)) for s_ in tw["scale"]]
         v = pre()
         nd["p"][3] = act
+        if not has_bias:
+            continue
         in_scale = tensors[nd["in"][0]]["scale"][0]
         tb["scale"] = [float(np.float32(in_scale) * np.float32(s_)) for s_ in tw["scale"]]
         tb["zero"] = [0] * len(tb["scale"])
@@ -301,12 +316,16 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
        residual: None, or the steps of a residual graph, which then REPLACE blocks: the features are reshaped to [1][1][frames][columns] (two_d:
        [1][frames][columns][1]) -- the tensor named "in" -- and every step names its output:
          (name, "conv", src, out_c, kh, kw, (sh, sw), valid, act[, lift])   CONV_2D kh x kw on tensor src with int32 bias and fused activation act
+         (name, "dw", src, depth_multiplier, kh, kw, (sh, sw), valid, act[, lift])   DEPTHWISE_CONV_2D kh x kw on tensor src: filter
+                                                                            [1][kh][kw][channels x depth_multiplier], per-channel scales along dimension 3
          (name, "add", a, b, act)                                           ADD of tensors a and b (the same name twice is allowed)
          (name, "pool", src, (ph, pw), (psh, psw), valid[, keras])           MAX_POOL_2D; keras: through the [1][W][1][C] renaming of Keras' Conv1D exports
        The last step's output is flattened; dense=, the head and softmax follow as ever.  Such a graph is always calibrated (calibrate_residual on
        standardised random feature matrices or calib: the bias of an activated convolution lifts its pre-activations by 0.5 deviations -- a step's own lift
        overrides that --, every step output gets the range its float twin shows; then calibrate_hidden / calibrate_head).  residual_opts: dict(per_tensor=True)
-       gives every filter ONE scale.  It draws nothing when residual is None: every blob is the one the same arguments gave before.
+       gives every filter ONE scale; dict(no_bias=(names)) leaves the named depthwise steps without a bias tensor.  With two_d=True and a "dw" step no ADD is
+       needed: the step trunks serve such a graph too.  A "dw" step draws only its own constants: every spec without one gives the blob it gave before.
+       It draws nothing when residual is None: every blob is the one the same arguments gave before.
        edit: a callable edit(tensors, nodes) run on the finished graph just before it is serialised -- the way to any quantisation
        parameter, constant or node option outside the drawn bands (tests/kws_testlib.py QUANT_EDGES).  It draws nothing from the
        model's generator: with edit=None every blob is the one the same arguments gave before."""
@@ -349,6 +368,7 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
         t = T(9, [1, hh, ww, cc], scale=[cur_scale], zero=[cur_zp])
         node(0, [cur, shape_const([1, hh, ww, cc])], [t])
         named = {"in": (t, hh, ww, cc)}                                 # name -> (tensor id, H, W, C)
+        no_bias = tuple((residual_opts or {}).get("no_bias", ()))       # names of the depthwise steps without a bias tensor (a two-input node)
 
         def drawn_output(act):
             return rscale(0.03, 0.12), int(rng.integers(-128, -90)) if act in (1, 3) else int(rng.integers(-30, 40))
@@ -372,6 +392,28 @@ def synth_model_blob(seed, ncep=13, win_size=101, low=300, high=4000, blocks=((3
                     h_, w_ = (h_ + sh - 1) // sh, (w_ + sw - 1) // sw
                 tc = T(9, [1, h_, w_, oc], scale=[out_scale], zero=[out_zp])
                 node(1, [ts, tw, tb], [tc], [2 if valid else 1, sw, sh, act, 1, 1])
+                if len(ent) > 9:
+                    residual_lift[len(nodes) - 1] = ent[9]
+                named[name] = (tc, h_, w_, oc)
+            elif kind == "dw":
+                src, mult, kh, kw, (sh, sw), valid, act = ent[2:9]
+                ts, h_, w_, c_ = named[src]
+                oc = c_ * mult
+                wq = rng.integers(-127, 128, (1, kh, kw, oc)).astype(np.int8)
+                wscales = [rscale(0.002, 0.02) for _ in range(oc)]
+                tw = T(9, [1, kh, kw, oc], True, wscales, [0] * oc, wq.tobytes(), qdim=3)
+                bias = rng.integers(-300, 300, oc).astype(np.int32)
+                ins = [ts, tw]
+                if name not in no_bias:
+                    ins.append(T(2, [oc], True, [tensors[ts]["scale"][0] * s_ for s_ in wscales], [0] * oc, bias.tobytes()))
+                out_scale, out_zp = drawn_output(act)
+                if valid:                                               # ComputeOutSize (kernels/padding.h)
+                    assert h_ >= kh and w_ >= kw
+                    h_, w_ = (h_ - kh) // sh + 1, (w_ - kw) // sw + 1
+                else:
+                    h_, w_ = (h_ + sh - 1) // sh, (w_ + sw - 1) // sw
+                tc = T(9, [1, h_, w_, oc], scale=[out_scale], zero=[out_zp])
+                node(6, ins, [tc], [2 if valid else 1, sw, sh, act, 1, 1, mult])
                 if len(ent) > 9:
                     residual_lift[len(nodes) - 1] = ent[9]
                 named[name] = (tc, h_, w_, oc)
@@ -608,7 +650,7 @@ def main():
     ap.add_argument("--conv-valid", default="", help="convolutions with VALID padding: block;block")
     ap.add_argument("--blocks2d", default="", help="a 2-D convolutional graph instead of --blocks: out_channels,kh,kw,pool per block, e.g. \"8,3,3,2;16,3,3,2\"; "
                     "options after a colon, k=v pairs: stride=HxW valid=1 act=N bias=0 pool=HxW pool_stride=HxW pool_valid=1")
-    ap.add_argument("--residual", default="", help="a residual graph instead of --blocks: steps name,conv,src,out_c,kh,kw,SHxSW,valid,act[,lift] | name,add,a,b,act | "
+    ap.add_argument("--residual", default="", help="a residual graph instead of --blocks: steps name,conv,src,out_c,kh,kw,SHxSW,valid,act[,lift] | name,dw,src,depth_mult,kh,kw,SHxSW,valid,act[,lift] | name,add,a,b,act | "
                     "name,pool,src,PHxPW,SHxSW,valid[,keras], separated by ';' (src \"in\": the reshaped input), e.g. "
                     "\"c0,conv,in,16,1,3,1x1,0,1;m1,conv,c0,16,1,9,1x1,0,0;sum,add,c0,m1,1\"")
     ap.add_argument("--two-d", action="store_true", help="with --residual: the input is [1][frames][columns][1], not [1][1][frames][columns]")
@@ -627,8 +669,8 @@ def main():
     def res_step(text):
         v = text.split(",")
         pair = lambda s: tuple(int(x) for x in s.split("x"))
-        if v[1] == "conv":
-            return (v[0], "conv", v[2], int(v[3]), int(v[4]), int(v[5]), pair(v[6]), bool(int(v[7])), int(v[8])) + ((float(v[9]),) if len(v) > 9 else ())
+        if v[1] in ("conv", "dw"):
+            return (v[0], v[1], v[2], int(v[3]), int(v[4]), int(v[5]), pair(v[6]), bool(int(v[7])), int(v[8])) + ((float(v[9]),) if len(v) > 9 else ())
         if v[1] == "add":
             return (v[0], "add", v[2], v[3], int(v[4]))
         return (v[0], "pool", v[2], pair(v[3]), pair(v[4]), bool(int(v[5]))) + ((bool(int(v[6])),) if len(v) > 6 else ())
