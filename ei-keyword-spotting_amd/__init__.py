@@ -46,6 +46,10 @@ EXPORTED_SYMBOLS = [
     "kws_frame_stride_samples", "kws_slide_window_count", "kws_slide_plan", "kws_slide_recordings_device",
     "kws_bank_create", "kws_bank_destroy", "kws_bank_size", "kws_bank_member", "kws_bank_run_classifier_batch_device",
     "kws_bank_cmvn_inference_batch_device", "kws_bank_slide_recordings_device",
+    "kws_bank_scan_recordings_device", "kws_bank_run_classifier_ragged_device",
+    "kws_bank_live_create", "kws_bank_live_destroy", "kws_bank_live_reset", "kws_bank_live_window_count", "kws_bank_live_push_device",
+    "kws_bank_slide_live_create", "kws_bank_slide_live_destroy", "kws_bank_slide_live_path", "kws_bank_slide_live_reset",
+    "kws_bank_slide_live_window_count", "kws_bank_slide_live_push_device",
     "kws_window_frame_count", "kws_run_classifier_ragged_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_slide_live_create", "kws_slide_live_destroy", "kws_slide_live_path", "kws_slide_live_reset", "kws_slide_live_window_count",
@@ -217,6 +221,22 @@ def lib():
             L.kws_slide_live_reset.argtypes = [vp, vp, sz]
             L.kws_slide_live_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
             L.kws_slide_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "kws_bank_live_push_device"):
+            L.kws_bank_scan_recordings_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+            L.kws_bank_run_classifier_ragged_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp]
+            L.kws_bank_live_create.argtypes = [vp, sz, sz, C.POINTER(vp)]
+            L.kws_bank_live_destroy.argtypes = [vp]
+            L.kws_bank_live_destroy.restype = None
+            L.kws_bank_live_reset.argtypes = [vp, vp, sz]
+            L.kws_bank_live_window_count.argtypes = [vp, sz, sz, C.c_int, C.POINTER(sz)]
+            L.kws_bank_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.kws_bank_slide_live_create.argtypes = [vp, sz, sz, i32, C.POINTER(vp)]
+            L.kws_bank_slide_live_destroy.argtypes = [vp]
+            L.kws_bank_slide_live_destroy.restype = None
+            L.kws_bank_slide_live_path.argtypes = [vp]
+            L.kws_bank_slide_live_reset.argtypes = [vp, vp, sz]
+            L.kws_bank_slide_live_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
+            L.kws_bank_slide_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         L.kws_device_malloc.argtypes = [C.POINTER(vp), sz]
         L.kws_device_free.argtypes = [vp]
         L.kws_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -512,6 +532,31 @@ class Bank:
         _check(self.L.kws_bank_slide_recordings_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, hop_samples, flags, self._scores(scores_ptrs),
                                                        features_ptr, stream))
 
+    def scan_recordings_device(self, pcm_ptr, offsets, lengths, scores_ptrs, raw_scores_ptrs=None, slice_samples=None, stream=None):
+        """Model.scan_recordings_device for every member: window counts are any member's.  raw_scores_ptrs: one device pointer (or None) per
+        member, or None for no raw scores at all."""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        raw = None if raw_scores_ptrs is None else self._scores(raw_scores_ptrs)
+        _check(self.L.kws_bank_scan_recordings_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, slice_samples or self._models[0].clip_samples // 4,
+                                                      self._scores(scores_ptrs), raw, stream))
+
+    def run_classifier_ragged_device(self, pcm_ptr, offsets, lengths, scores_ptrs, features_ptr=None, stream=None):
+        """Model.run_classifier_ragged_device for every member: the DSP route once, features (optional) shared"""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        _check(self.L.kws_bank_run_classifier_ragged_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, self._scores(scores_ptrs), features_ptr, stream))
+
+    def live_streams(self, n_streams, slice_samples=None):
+        """a live session of n_streams streams in continuous mode for every member (kws_bank_live_*): see BankLiveStreams"""
+        return BankLiveStreams(self, n_streams, slice_samples)
+
+    def slide_streams(self, n_streams, hop_samples, flags=SLIDE_AUTO):
+        """a live session of n_streams streams of one-shot windows for every member (kws_bank_slide_live_*): see BankSlideStreams"""
+        return BankSlideStreams(self, n_streams, hop_samples, flags)
+
     def close(self):
         if getattr(self, "b", None):
             self.L.kws_bank_destroy(self.b)
@@ -640,6 +685,104 @@ class SlideStreams:
     def close(self):
         if getattr(self, "sl", None):
             self.L.kws_slide_live_destroy(self.sl)
+            self.sl = None
+
+
+class BankLiveStreams:
+    """LiveStreams for every member of a bank (kws_bank_live; the contract is in include/kws/kws.h): one session, one copy of every stream's
+    carried samples and retained rows, one moving-average state per member.  Close the session before its bank."""
+
+    def __init__(self, bank, n_streams, slice_samples=None):
+        self.bank = bank
+        self.L = bank.L
+        self.slice_samples = slice_samples or bank.members[0].clip_samples // 4
+        lv = C.c_void_p()
+        _check(self.L.kws_bank_live_create(bank.b, n_streams, self.slice_samples, C.byref(lv)))
+        self.lv = lv
+        self.n_streams = n_streams
+
+    def window_count(self, stream, n_new, finish=False):
+        """windows a push of n_new samples to `stream` (finishing it if finish) would return now"""
+        n = C.c_size_t()
+        _check(self.L.kws_bank_live_window_count(self.lv, stream, n_new, 1 if finish else 0, C.byref(n)))
+        return n.value
+
+    def push_device(self, pcm_ptr, streams, offsets, lengths, scores_ptrs, raw_scores_ptrs=None, finish=None, stream=None):
+        """LiveStreams.push_device for every member: scores_ptrs (and raw_scores_ptrs) hold one device pointer per member, [sum][that
+        member's n_labels]; no member can be skipped (its filter must see every window).  Returns n_windows per entry (numpy uint64)."""
+        st = np.ascontiguousarray(streams, np.uint64)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert st.shape == off.shape == ln.shape and st.ndim == 1
+        fin = None if finish is None else np.ascontiguousarray(finish, np.int32)
+        assert fin is None or fin.shape == st.shape
+        nw = np.zeros(st.size, np.uint64)
+        raw = None if raw_scores_ptrs is None else self.bank._scores(raw_scores_ptrs)
+        _check(self.L.kws_bank_live_push_device(self.lv, st.size, _p(st), pcm_ptr, _p(off), _p(ln), None if fin is None else _p(fin),
+                                                self.bank._scores(scores_ptrs), raw, _p(nw), stream))
+        return nw
+
+    def reset(self, streams=None):
+        """streams (host sequence; None: all) back to fresh state"""
+        if streams is None:
+            _check(self.L.kws_bank_live_reset(self.lv, None, 0))
+            return
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_bank_live_reset(self.lv, _p(st), st.size))
+
+    def close(self):
+        if getattr(self, "lv", None):
+            self.L.kws_bank_live_destroy(self.lv)
+            self.lv = None
+
+
+class BankSlideStreams:
+    """SlideStreams for every member of a bank (kws_bank_slide_live; the contract is in include/kws/kws.h): one session, one copy of every
+    stream's carried samples and retained rows.  Close the session before its bank."""
+
+    def __init__(self, bank, n_streams, hop_samples, flags=SLIDE_AUTO):
+        self.bank = bank
+        self.L = bank.L
+        self.hop_samples = hop_samples
+        sl = C.c_void_p()
+        _check(self.L.kws_bank_slide_live_create(bank.b, n_streams, hop_samples, flags, C.byref(sl)))
+        self.sl = sl
+        self.n_streams = n_streams
+
+    @property
+    def path(self):
+        """SLIDE_DIRECT or SLIDE_SHARED: what the session's pushes run"""
+        return int(self.L.kws_bank_slide_live_path(self.sl))
+
+    def window_count(self, stream, n_new):
+        """windows a push of n_new samples to `stream` would return now"""
+        n = C.c_size_t()
+        _check(self.L.kws_bank_slide_live_window_count(self.sl, stream, n_new, C.byref(n)))
+        return n.value
+
+    def push_device(self, pcm_ptr, streams, offsets, lengths, scores_ptrs, features_ptr=None, stream=None):
+        """SlideStreams.push_device for every member: scores_ptrs holds one device pointer per member (None: skipped in this push),
+        features (optional) are shared.  Returns n_windows per entry (numpy uint64)."""
+        st = np.ascontiguousarray(streams, np.uint64)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert st.shape == off.shape == ln.shape and st.ndim == 1
+        nw = np.zeros(st.size, np.uint64)
+        _check(self.L.kws_bank_slide_live_push_device(self.sl, st.size, _p(st), pcm_ptr, _p(off), _p(ln), self.bank._scores(scores_ptrs), features_ptr,
+                                                      _p(nw), stream))
+        return nw
+
+    def reset(self, streams=None):
+        """streams (host sequence; None: all) back to fresh state"""
+        if streams is None:
+            _check(self.L.kws_bank_slide_live_reset(self.sl, None, 0))
+            return
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_bank_slide_live_reset(self.sl, _p(st), st.size))
+
+    def close(self):
+        if getattr(self, "sl", None):
+            self.L.kws_bank_slide_live_destroy(self.sl)
             self.sl = None
 
 

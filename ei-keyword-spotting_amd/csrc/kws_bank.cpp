@@ -13,39 +13,6 @@
 #include "kws_bank.h"
 
 #include <algorithm>
-#include <memory>
-
-struct kws_bank {
-    std::vector<kws_handle *> m;           // members, in the caller's order
-    std::vector<kws_handle *> by_addr;     // the same, in the order their locks are taken
-    int device = 0;
-    KwsBankRec *d_rec = nullptr;           // [K] (int8 members' entries are filled)
-    float *feat = nullptr;                 // the shared feature matrix of calls without `features`
-    size_t feat_cap = 0;
-    hipEvent_t ev = nullptr;               // end of the last call's work
-    bool ev_used = false;
-    std::mutex mu;
-};
-
-// every member's lock in one order whatever the order of the members (two banks over the same handles cannot deadlock), and every
-// member's scratch bracket: the call is a call on each of them (kws.h: streams and concurrency)
-struct BankUse {
-    std::unique_lock<std::mutex> own;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    std::vector<std::unique_ptr<ScratchUse>> uses;        // released before the locks (declared after them)
-    kws_bank *b;
-    hipStream_t s;
-    // skip_first: the slide brackets the first member itself (kws_slide_run)
-    BankUse(kws_bank *b_, hipStream_t s_, bool skip_first) : own(b_->mu), b(b_), s(s_)
-    {
-        for (kws_handle *h : b->by_addr) locks.emplace_back(h->mu);
-        for (size_t k = skip_first ? 1 : 0; k < b->m.size(); ++k) uses.emplace_back(new ScratchUse(b->m[k], s));
-    }
-    ~BankUse()
-    {
-        if (b->ev && hipEventRecord(b->ev, s) == hipSuccess) b->ev_used = true;
-    }
-};
 
 #define DIFFER(field, fmt, a, b_)                                                                                                      \
     return fail(KWS_ERROR_BAD_ARGUMENT, "bank member %zu differs from member 0 in " field ": " fmt " against " fmt, k, a, b_)
@@ -77,7 +44,7 @@ static EI_IMPULSE_ERROR bank_same_front_end(const kws_handle *a, const kws_handl
 }
 
 // every member's network from the feature matrix feat [B][F] (device); scores[k] + row0 * labels of member k is where its rows go
-static EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, hipStream_t s)
+EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, hipStream_t s)
 {
     const size_t K = b->m.size(), F = b->m[0]->model.nn_input_frame_size;
     KwsBankOut o16{}, o64{};
@@ -108,23 +75,19 @@ static EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, 
     return EI_IMPULSE_OK;
 }
 
-static bool bank_wants_nothing(const kws_bank *b, float *const *scores, const float *features)
+bool bank_wants_nothing(const kws_bank *b, float *const *scores, const float *features)
 {
     if (features) return false;
     for (size_t k = 0; k < b->m.size(); ++k) if (scores[k]) return false;
     return true;
 }
 
-// the slide's finishing step for a bank: cmvnw (the MFE normalisation) once through the first member, then every member
-struct BankSlide {
-    kws_bank *b;
-    float *const *scores;
-    float *features;
-};
-static EI_IMPULSE_ERROR bank_slide_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
+// the finishing step of a chunk of gathered windows for a bank (the slide's, and the window pipelines' of kws_bank_windows.cpp): cmvnw (the MFE
+// normalisation) once through the first member, then every member
+EI_IMPULSE_ERROR bank_window_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
 {
     if (n == 0) return EI_IMPULSE_OK;
-    BankSlide &c = *(BankSlide *)ctx;
+    BankWindows &c = *(BankWindows *)ctx;
     kws_bank *b = c.b;
     kws_handle *h0 = b->m[0];
     const size_t F = h0->model.nn_input_frame_size;
@@ -250,8 +213,8 @@ EI_IMPULSE_ERROR kws_bank_slide_recordings_device(kws_bank *b, const int16_t *pc
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     BankUse use(b, s, true);
-    BankSlide ctx{ b, scores, features };
-    return kws_slide_run(b->m[0], pcm, offsets, lengths, R, hop_samples, flags, 0, bank_slide_finish, &ctx, s);
+    BankWindows ctx{ b, scores, features };
+    return kws_slide_run(b->m[0], pcm, offsets, lengths, R, hop_samples, flags, 0, bank_window_finish, &ctx, s);
 }
 
 #pragma GCC visibility pop

@@ -388,6 +388,29 @@ typedef EI_IMPULSE_ERROR (*kws_slide_finish_fn)(void *ctx, float *win, size_t n,
 KWS_INTERNAL EI_IMPULSE_ERROR kws_slide_run(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R, size_t hop_samples,
                                             int flags, int take_lock, kws_slide_finish_fn finish, void *ctx, hipStream_t s);
 
+// The other window pipelines as runners of the same shape (kws_scan.cpp, kws_live.cpp, kws_slide_live.cpp, kws_ragged.cpp): the entry point's
+// body with what follows the gathering as callables, for the entry point itself and for a bank (kws_bank_windows.cpp).
+//   finish(ctx, win, n, first, s)   as above; the two live runners call it with n == 0 BEFORE any launch when a push returns no window
+//                                   (finish_idle: also when no entry has device work), and after the last chunk otherwise
+//   maf(ctx, meta, n, s)            the moving-average step of the continuous pipelines over the raw scores finish() wrote: the scan hands its
+//                                   window prefix wbase [n + 1] of the n recordings with windows, a live push its per-entry tables of n entries
+//   labels                          the most labels any reader of the windows has (the bound on windows x labels)
+// take_lock == 0: the caller holds h->mu.  The ragged runner ends the DSP route in f [B][feature_count] (and the int8 tensor q) and calls
+// finish(ctx, f, B, 0, s) once; net: the finishing step is the handle's own network, so the handle's scratch stands in for an output the
+// caller did not ask for; net == 0: only `features` is written.
+typedef EI_IMPULSE_ERROR (*kws_window_maf_fn)(void *ctx, const long long *meta, int n, hipStream_t s);
+KWS_INTERNAL EI_IMPULSE_ERROR kws_scan_run(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R, size_t slice_samples,
+                                           size_t labels, int take_lock, kws_slide_finish_fn finish, kws_window_maf_fn maf, void *ctx, hipStream_t s);
+KWS_INTERNAL EI_IMPULSE_ERROR kws_live_open(kws_handle *h, size_t S, size_t slice_samples, int with_maf, kws_live **out);
+KWS_INTERNAL EI_IMPULSE_ERROR kws_live_run(kws_live *lv, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets, const size_t *lengths,
+                                           const int *finish_flags, const void *out, size_t *n_windows, size_t labels, int take_lock, int finish_idle,
+                                           kws_slide_finish_fn finish, kws_window_maf_fn maf, void *ctx, hipStream_t s);
+KWS_INTERNAL EI_IMPULSE_ERROR kws_slide_live_run(kws_slide_live *sl, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets,
+                                                 const size_t *lengths, const void *out, size_t *n_windows, size_t labels, int take_lock, int finish_idle,
+                                                 kws_slide_finish_fn finish, void *ctx, hipStream_t s);
+KWS_INTERNAL EI_IMPULSE_ERROR kws_ragged_run(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B, float *features,
+                                             int8_t *q_in, int net, int take_lock, kws_slide_finish_fn finish, void *ctx, hipStream_t s);
+
 // grows the device buffer *p to at least n elements (synchronising the device first: the old buffer may still be in use by enqueued work);
 // the per-call scratch of the window pipelines (kws_windows.h), of kws_bank.cpp and of kws_ragged.cpp
 template <typename T>

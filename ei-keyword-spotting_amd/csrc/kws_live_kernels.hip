@@ -18,18 +18,7 @@
 
 #define KWS_LIVE_TAPS (EI_CLASSIFIER_SLICES_PER_MODEL_WINDOW >> 1)
 
-// The per-entry tables of one push, n_act entries (the entries of the call that have work), each a device array:
-struct KwsLiveMeta {
-    const long long *off;      // the entry's chunk: pcm + off
-    const long long *n0;       // samples the stream had before the push
-    const long long *len;      // samples pushed
-    const long long *stream;   // stream index
-    const long long *k0, *k1;  // finished slices before / after the push
-    const long long *fin;      // 1: the push finishes the stream (its state is not committed)
-    const long long *fbase;    // [n_act + 1] prefix: slice-0 items of the entries before
-    const long long *ibase;    // [n_act + 1] prefix: slice k >= 1 items of the entries before
-    const long long *wbase;    // [n_act + 1] prefix: windows of the entries before
-};
+// (KwsLiveMeta, the per-entry tables of one push, and live_meta: kws_window_kernels.h)
 
 // first = 1: item g is the slice 0 of the entry with fbase[a] <= g < fbase[a + 1]; first = 0: item g is a slice k >= 1, counted over the
 // entries in order from each entry's first new slice max(k0, 1).  One block per item.
@@ -146,14 +135,6 @@ __global__ void kws_live_maf_kernel(const float *raw, float *scores, KwsLiveMeta
 #pragma unroll
     for (int i = 0; i < KWS_LIVE_TAPS; ++i) st[i] = buf[i];
     st[KWS_LIVE_TAPS] = rs;
-}
-
-static KwsLiveMeta live_meta(const long long *d, int n_act)
-{
-    KwsLiveMeta m;
-    m.off = d; m.n0 = d + n_act; m.len = d + 2 * n_act; m.stream = d + 3 * n_act; m.k0 = d + 4 * n_act; m.k1 = d + 5 * n_act; m.fin = d + 6 * n_act;
-    m.fbase = d + 7 * n_act; m.ibase = m.fbase + n_act + 1; m.wbase = m.ibase + n_act + 1;
-    return m;
 }
 
 int kws_launch_live_stage(const int16_t *pcm, const int16_t *carry, const long long *meta, int n_act, long long item0, int n_items, int first, int slice,

@@ -8,8 +8,9 @@
 //   MFE block, general-shape plans   the grouped route: clips are bucketed by frame count; each bucket is gathered into slots of one stride
 //                                    (with its wrap samples), run through the existing fixed-length launches with kws_plan_for_length's
 //                                    plan, and its packed rows are scattered into the full-stride rows (kws_ragged_scatter_kernel).
-// and the network is the existing launches on the [B][feature_count] matrix / int8 tensor.  These are the launches of KWS_MODE_EXACT: nothing
-// here reads the handle's mode, its fast counters or its logits tap.
+// and the network is the existing launches on the [B][feature_count] matrix / int8 tensor -- a callable behind the DSP route (kws_ragged_run): a
+// bank runs the route once with the network skipped, then every member's network on the feature rows (kws_bank_windows.cpp).
+// These are the launches of KWS_MODE_EXACT: nothing here reads the handle's mode, its fast counters or its logits tap.
 #include "kws_internal.h"
 #include "kws_ragged.h"
 
@@ -143,14 +144,30 @@ static EI_IMPULSE_ERROR ragged_grouped(kws_handle *h, KwsRaggedScratch &S, const
     return EI_IMPULSE_OK;
 }
 
-#pragma GCC visibility push(default)
-EI_IMPULSE_ERROR kws_run_classifier_ragged_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B,
-                                                  float *scores, float *features, int8_t *q_in, void *stream)
+// The network step of kws_run_classifier_ragged_device itself: the existing launches on the matrix / the int8 tensor the DSP route wrote
+struct RaggedOwn {
+    kws_handle *h;
+    float *scores;
+    int8_t *q_in;
+};
+static EI_IMPULSE_ERROR ragged_own_finish(void *ctx, float *f, size_t B, size_t, hipStream_t s)
+{
+    RaggedOwn &o = *(RaggedOwn *)ctx;
+    kws_handle *h = o.h;
+    if (!o.scores) return EI_IMPULSE_OK;
+    const int8_t *q = h->is_float ? nullptr : o.q_in ? o.q_in : h->s_q;        // (the tensor kws_ragged_run had the DSP route write)
+    return network_device(h, f, q, B, o.scores, nullptr, nullptr, nullptr, nullptr, nullptr, s);
+}
+
+// The ragged call up to the network: argument checks, then the DSP route into f [B][feature_count] and the int8 tensor q, then
+// finish(ctx, f, B, 0, s) once (kws_internal.h has the contract; `me` names the public call in messages).
+EI_IMPULSE_ERROR kws_ragged_run(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B, float *features, int8_t *q_in,
+                                int net, int take_lock, kws_slide_finish_fn finish, void *ctx, hipStream_t s)
 {
     static const char *const me = "kws_run_classifier_ragged_device";
     if (!h) return fail(KWS_ERROR_BAD_ARGUMENT, "%s: null handle", me);
     if (B >= ((size_t)1 << 31)) return fail(KWS_ERROR_BAD_ARGUMENT, "%s: batch too large (%zu clips)", me, B);
-    if (!scores && !features && !q_in) return fail(KWS_ERROR_BAD_ARGUMENT, "%s: no output requested (scores, features and q_in are all NULL)", me);
+    if (!net && !features && !q_in) return fail(KWS_ERROR_BAD_ARGUMENT, "%s: no output requested (scores, features and q_in are all NULL)", me);
     if (h->is_float && q_in) return fail(KWS_ERROR_UNSUPPORTED_MODEL, "int8 input tensor requested from a float32 model");
     if (B == 0) return EI_IMPULSE_OK;
     if (!pcm || !offsets || !lengths) return fail(KWS_ERROR_BAD_ARGUMENT, "%s: null %s", me, !pcm ? "pcm" : !offsets ? "offsets" : "lengths");
@@ -161,19 +178,27 @@ EI_IMPULSE_ERROR kws_run_classifier_ragged_device(kws_handle *h, const int16_t *
                         lengths[i], nfr, h->dsp.n_frames);
     }
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(h->mu);
+    std::unique_lock<std::mutex> lk(h->mu, std::defer_lock);
+    if (take_lock) lk.lock();
     if (!h->ragged) { h->ragged = new KwsRaggedScratch(); h->ragged_release = ragged_release; }
     KwsRaggedScratch &S = *h->ragged;
     EI_IMPULSE_ERROR e = ensure_scratch(h, B);
     if (e) return e;
     ScratchUse use(h, s);
-    // what the network reads when the caller does not ask for it: the handle's scratch
-    float *f = (features || !(scores && h->is_float)) ? features : h->s_mfcc;
-    int8_t *q = h->is_float ? nullptr : (q_in || !scores) ? q_in : h->s_q;
+    // what the handle's network reads when the caller does not ask for it: the handle's scratch
+    float *f = (features || !(net && h->is_float)) ? features : h->s_mfcc;
+    int8_t *q = h->is_float ? nullptr : (q_in || !net) ? q_in : h->s_q;
     const bool tuned = h->model.dsp.block == DSP_BLOCK_MFCC && kws_mfcc_ragged_serves(h->dsp);
     e = tuned ? ragged_tuned(h, S, pcm, offsets, lengths, B, f, q, s) : ragged_grouped(h, S, pcm, offsets, lengths, B, f, q, s);
-    if (e || !scores) return e;
-    return network_device(h, f, q, B, scores, nullptr, nullptr, nullptr, nullptr, nullptr, s);
+    if (e) return e;
+    return finish(ctx, f, B, 0, s);
+}
+
+#pragma GCC visibility push(default)
+EI_IMPULSE_ERROR kws_run_classifier_ragged_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B,
+                                                  float *scores, float *features, int8_t *q_in, void *stream)
+{
+    RaggedOwn own{ h, scores, q_in };
+    return kws_ragged_run(h, pcm, offsets, lengths, B, features, q_in, scores != nullptr, 1, ragged_own_finish, &own, (hipStream_t)stream);
 }
 #pragma GCC visibility pop

@@ -11,6 +11,8 @@
 //      cmvn_nn_fast_device in KWS_MODE_FAST), which write each window's raw scores in place;
 //   3. the moving average per (recording, label) over its windows in order (kws_scan_maf_kernel).
 // A = the recordings of the call that produce at least one window; the others need no work.
+// Steps 2 and 3 end in callables (kws_scan_run: the finishing hook per chunk, the moving-average hook): what is written above is what
+// kws_scan_recordings_device passes; a bank passes cmvnw once + every member's network and one filter launch for all (kws_bank_windows.cpp).
 // Scratch and its bounds, the table upload, the finishing step of a chunk and the fast counters: the window pipelines' core, kws_windows.h.
 #include "kws_internal.h"
 #include "kws_windows.h"
@@ -64,24 +66,39 @@ EI_IMPULSE_ERROR scan_layout(const kws_handle *h, size_t slice_samples, ScanLayo
     return EI_IMPULSE_OK;
 }
 
-extern "C" {
-#pragma GCC visibility push(default)
-
-EI_IMPULSE_ERROR kws_scan_window_count(const kws_handle *h, size_t n_samples, size_t slice_samples, size_t *n_windows)
+// The finishing and moving-average steps of kws_scan_recordings_device itself: cmvnw + the handle's network in the handle's mode, chunk by
+// chunk, raw scores where the moving average reads them; then one fresh filter per recording (h->mu held)
+struct ScanOwn {
+    float *scores, *raw;
+    KwsChunkCounts counts;
+    bool started = false;
+};
+static EI_IMPULSE_ERROR scan_own_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t st)
 {
-    if (!h || !n_windows) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    *n_windows = 0;
-    ScanLayout L;
-    EI_IMPULSE_ERROR e = scan_layout(h, slice_samples, &L);
-    if (e) return e;
-    *n_windows = L.windows(n_samples / slice_samples);
+    ScanOwn &o = *(ScanOwn *)ctx;
+    kws_handle *h = o.counts.h;
+    EI_IMPULSE_ERROR e;
+    if (!o.started) {
+        o.started = true;
+        o.counts = KwsChunkCounts(h);                              // (the handle's mode, read under its lock)
+        if ((e = o.counts.begin(h->scan->acc, n, st))) return e;
+    }
+    if (n == 0) return o.counts.end(st);                           // after the last chunk
+    if ((e = kws_finish_window_chunk(h, win, n, o.raw + g0 * h->model.labels.size(), nullptr, o.counts.fast, st))) return e;
+    return o.counts.chunk(st);
+}
+static EI_IMPULSE_ERROR scan_own_maf(void *ctx, const long long *wbase, int n_rec, hipStream_t st)
+{
+    ScanOwn &o = *(ScanOwn *)ctx;
+    KWS_LAUNCH_TRY("scan moving-average kernel", kws_launch_scan_maf(o.raw, o.scores, wbase, n_rec, (int)o.counts.h->model.labels.size(), st));
     return EI_IMPULSE_OK;
 }
 
-EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
-                                            size_t slice_samples, float *scores, float *raw_scores, void *stream)
+// The scan: argument checks, staging and cepstral rows, windows gathered in chunks; every chunk (win [n][F] cepstra before cmvnw, the call's
+// windows g0 .. g0 + n - 1) goes to finish(), which is called once more with n == 0 after the last chunk; then maf() (kws_internal.h).
+EI_IMPULSE_ERROR kws_scan_run(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R, size_t slice_samples, size_t labels,
+                              int take_lock, kws_slide_finish_fn finish, kws_window_maf_fn maf, void *ctx, hipStream_t st)
 {
-    if (!h || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (R > 0 && (!pcm || !offsets || !lengths)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (R > 0x3fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "too many recordings");
     ScanLayout L;
@@ -101,12 +118,12 @@ EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, c
     if (A == 0) return EI_IMPULSE_OK;
     const size_t n_win = (size_t)wbase.back(), n_slots = (size_t)ibase.back();
     const Model &m = h->model;
-    const size_t F = m.nn_input_frame_size, C = m.labels.size();
+    const size_t F = m.nn_input_frame_size, C = labels;
     const int ncols = h->dsp.n_cepstral, rows = (int)(F / (size_t)ncols);
     if (n_win * C > (size_t)1 << 40) return fail(KWS_ERROR_BAD_ARGUMENT, "too many windows");
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(h->mu);
+    std::unique_lock<std::mutex> lk(h->mu, std::defer_lock);
+    if (take_lock) lk.lock();
     if (!h->scan) { h->scan = new KwsWindowScratch(); h->scan_release = scan_release; }
     KwsWindowScratch &S = *h->scan;
     const size_t item_cap = kws_window_item_cap(slice_samples), win_chunk = kws_window_chunk(F, n_win);
@@ -133,19 +150,37 @@ EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, c
         KWS_LAUNCH_TRY("scan staging kernel", kws_launch_scan_stage(pcm, d_off, d_len, d_ibase, A, (long long)g0, n, 0, slice, L.grow, S.stage, S.wrap, st));
         if ((e = spectral_device(h, P1, S.stage, 0, n, slot_rows + g0 * L.nf1 * ncols, S.wrap, st, L.nf1 * ncols))) return e;
     }
-    // 2. windows in chunks through the stream API's cmvnw + network; raw scores land where the moving average reads them
-    float *raw = raw_scores ? raw_scores : scores;
-    KwsChunkCounts cnt(h);
-    if ((e = cnt.begin(S.acc, n_win, st))) return e;
+    // 2. windows in chunks through the finishing step (the stream API's cmvnw + network); raw scores land where the moving average reads them
     for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
         const int n = (int)std::min(win_chunk, n_win - g0);
         KWS_LAUNCH_TRY("scan gather kernel", kws_launch_scan_gather(first_rows, slot_rows, d_wbase, d_ibase, A, (long long)g0, n, L.nf0, L.nf1, L.ring_rows, rows, ncols, S.win, st));
-        if ((e = kws_finish_window_chunk(h, S.win, n, raw + g0 * C, nullptr, cnt.fast, st)) || (e = cnt.chunk(st))) return e;
+        if ((e = finish(ctx, S.win, (size_t)n, g0, st))) return e;
     }
-    if ((e = cnt.end(st))) return e;
+    if ((e = finish(ctx, S.win, 0, n_win, st))) return e;
     // 3. the moving average, one fresh filter per recording
-    KWS_LAUNCH_TRY("scan moving-average kernel", kws_launch_scan_maf(raw, scores, d_wbase, A, (int)C, st));
+    return maf(ctx, d_wbase, A, st);
+}
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+EI_IMPULSE_ERROR kws_scan_window_count(const kws_handle *h, size_t n_samples, size_t slice_samples, size_t *n_windows)
+{
+    if (!h || !n_windows) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    *n_windows = 0;
+    ScanLayout L;
+    EI_IMPULSE_ERROR e = scan_layout(h, slice_samples, &L);
+    if (e) return e;
+    *n_windows = L.windows(n_samples / slice_samples);
     return EI_IMPULSE_OK;
+}
+
+EI_IMPULSE_ERROR kws_scan_recordings_device(kws_handle *h, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                            size_t slice_samples, float *scores, float *raw_scores, void *stream)
+{
+    if (!h || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    ScanOwn own{ scores, raw_scores ? raw_scores : scores, KwsChunkCounts(h) };
+    return kws_scan_run(h, pcm, offsets, lengths, R, slice_samples, h->model.labels.size(), 1, scan_own_finish, scan_own_maf, &own, (hipStream_t)stream);
 }
 
 #pragma GCC visibility pop

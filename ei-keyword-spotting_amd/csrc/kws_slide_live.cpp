@@ -20,6 +20,8 @@
 //   direct path:  per chunk, kws_slide_live_stage_clips_kernel (carry + chunk -> aligned clips) and the handle's own plan into [chunk][F];
 //   both:         the finishing step per chunk (cmvn_nn_device, or cmvn_nn_fast_device and the count kernel in KWS_MODE_FAST), then
 //                 kws_slide_live_commit_kernel: each entry's new carry and retained rows, after every read of the old ones.
+// The finishing step is a callable (kws_slide_live_run): the above is what kws_slide_live_push_device passes; a bank passes cmvnw once + every
+// member's network (kws_bank_windows.cpp).
 // Reset touches no device memory: a stream's carry and rows are only read in the ranges its host counts say were written.
 // Scratch, table upload, finishing step, fast counters, the session skeleton and the slide's geometry (SlideGeom): kws_windows.h.
 #include "kws_internal.h"
@@ -44,6 +46,131 @@ struct kws_slide_live : KwsLiveSession {
 
     unsigned long long positions(size_t W) const { return path == KWS_SLIDE_SHARED && W ? (unsigned long long)(W - 1) * hs + (unsigned long long)G.run : 0; }
 };
+
+// The finishing step of kws_slide_live_push_device itself: cmvnw + the handle's network in the handle's mode, chunk by chunk (h->mu held)
+struct SlideLiveOwn {
+    kws_slide_live *sl;
+    float *scores, *features;
+    KwsChunkCounts counts;
+    bool started = false;
+};
+static EI_IMPULSE_ERROR slide_live_own_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t st)
+{
+    SlideLiveOwn &o = *(SlideLiveOwn *)ctx;
+    kws_handle *h = o.sl->h;
+    const size_t F = h->model.nn_input_frame_size, C = h->model.labels.size();
+    EI_IMPULSE_ERROR e;
+    if (!o.started) {
+        // a push without a window: the fast counters describe it
+        if (n == 0) return KwsChunkCounts::wanted(h) ? KwsChunkCounts::none(h, st) : EI_IMPULSE_OK;
+        o.started = true;
+        if ((e = o.counts.begin(o.sl->scratch.acc, n, st))) return e;
+    }
+    if (n == 0) return o.counts.end(st);                           // after the last chunk
+    if ((e = kws_finish_window_chunk(h, win, n, o.scores + g0 * C, o.features ? o.features + g0 * F : nullptr, o.counts.fast, st))) return e;
+    return o.counts.chunk(st);
+}
+
+// The push: argument checks, every count, the rows or clips of the completed windows, windows gathered in chunks through finish(), the
+// commit of carry and retained rows, and the mirrors (kws_internal.h has the hook's contract).
+EI_IMPULSE_ERROR kws_slide_live_run(kws_slide_live *sl, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets, const size_t *lengths,
+                                    const void *out, size_t *n_windows, size_t labels, int take_lock, int finish_idle, kws_slide_finish_fn finish, void *ctx,
+                                    hipStream_t st)
+{
+    kws_handle *h = sl->h;
+    const SlideGeom &G = sl->G;
+    const bool shared = sl->path == KWS_SLIDE_SHARED;
+    std::unique_lock<std::mutex> lk(h->mu, std::defer_lock);
+    if (take_lock) lk.lock();
+    // argument checks and every count of the push, before any state changes
+    EI_IMPULSE_ERROR e = sl->check_push(n, streams, pcm, offsets, lengths, n_windows, (const float *)out);
+    if (e) return e;
+    // the entries with device work (A of them): windows, or new samples to carry
+    std::vector<size_t> counts(n, 0);
+    std::vector<long long> off, n0, len, sid, w0, pc0, np, rbase(1, 0), wbase(1, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t s = streams[i];
+        if (!lengths[i]) continue;
+        const size_t a0 = G.windows(sl->n[s]), a1 = G.windows(sl->n[s] + lengths[i]);
+        counts[i] = a1 - a0;
+        const unsigned long long p0 = sl->pc[s], p1 = sl->positions(a1);
+        off.push_back((long long)offsets[i]);
+        n0.push_back((long long)sl->n[s]);
+        len.push_back((long long)lengths[i]);
+        sid.push_back((long long)s);
+        w0.push_back((long long)a0);
+        pc0.push_back((long long)p0);
+        np.push_back((long long)(p1 - p0));
+        rbase.push_back(rbase.back() + (shared ? (long long)(p1 - p0) + (long long)(G.pre ? a1 - a0 : 0) : 0));
+        wbase.push_back(wbase.back() + (long long)(a1 - a0));
+    }
+    const int A = (int)off.size();
+    const size_t n_frames = (size_t)rbase.back(), n_win = (size_t)wbase.back();
+    const Model &m = h->model;
+    const size_t F = m.nn_input_frame_size, C = labels;
+    const int ncols = G.ncols, nfi = G.nfi;
+    if (n_win > (size_t)1 << 40 || n_win * C > (size_t)1 << 40) return fail(KWS_ERROR_BAD_ARGUMENT, "too many windows");
+    for (size_t i = 0; i < n; ++i) n_windows[i] = counts[i];
+    auto commit_mirrors = [&]() {
+        for (size_t i = 0; i < n; ++i) {
+            const size_t s = streams[i];
+            sl->n[s] += lengths[i];
+            sl->pc[s] = sl->positions(G.windows(sl->n[s]));
+        }
+    };
+    if (A == 0 && !finish_idle) {
+        commit_mirrors();
+        return EI_IMPULSE_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    KwsWindowScratch &S = sl->scratch;
+    // staged items: a rows item is nfi frames of S1 samples; a direct item is a window
+    const size_t item_len = (size_t)nfi * G.S1, n_items = (n_frames + nfi - 1) / nfi;
+    const size_t item_cap = kws_window_item_cap(item_len), clip_cap = kws_window_item_cap(G.clip), win_chunk = kws_window_chunk(F, n_win);
+    const size_t stage_need = shared ? std::min(item_cap, std::max<size_t>(n_items, 1)) * item_len : std::min(clip_cap, win_chunk) * G.clip;
+    const size_t wrap_need = shared ? std::min(item_cap, std::max<size_t>(n_items, 1)) : 1;
+    if ((e = S.reserve(h, stage_need, wrap_need, win_chunk * F, std::max<size_t>(n_items * nfi * ncols, 1), 7 * (size_t)A + 2 * ((size_t)A + 1), win_chunk)))
+        return e;
+    ScratchUse use(h, st);
+    if (n_win == 0) {
+        if ((e = finish(ctx, nullptr, 0, 0, st))) return e;
+        if (A == 0) {
+            commit_mirrors();
+            return EI_IMPULSE_OK;
+        }
+    }
+    // per-entry tables (kws_slide_live_kernels.hip KwsSlideLiveMeta)
+    if ((e = kws_upload_tables(S, { &off, &n0, &len, &sid, &w0, &pc0, &np, &rbase, &wbase }, st))) return e;
+    if (shared && n_items) {
+        // 1. the rows this push needs: nfi independent frames per item, S1 samples apart, each with its predecessor in the sample before it
+        const KwsDspPlan PF = G.first_plan(h);
+        for (size_t g0 = 0; g0 < n_items; g0 += item_cap) {
+            const int c = (int)std::min(item_cap, n_items - g0);
+            KWS_LAUNCH_TRY("slide live staging kernel", kws_launch_slide_live_stage_rows(pcm, sl->carry, S.meta, A, (long long)g0, c, (long long)n_frames, nfi, (int)G.S1, G.used, G.stride,
+                                                                                         (long long)G.hop, (int)G.clip, G.pre, S.stage, S.wrap, st));
+            if ((e = spectral_device(h, PF, S.stage, 0, c, S.rows + g0 * nfi * ncols, S.wrap, st, nfi * ncols))) return e;
+        }
+    }
+    // 2. windows in chunks through the finishing step (cmvnw + the network)
+    for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
+        const int c = (int)std::min(win_chunk, n_win - g0);
+        if (shared) {
+            KWS_LAUNCH_TRY("slide live gather kernel", kws_launch_slide_live_gather(S.rows, sl->kept, S.meta, A, (long long)g0, c, (long long)sl->hs, G.run, G.pre, ncols, S.win, st));
+        } else {
+            for (size_t i0 = 0; i0 < (size_t)c; i0 += clip_cap) {
+                const int nw = (int)std::min(clip_cap, (size_t)c - i0);
+                KWS_LAUNCH_TRY("slide live staging kernel", kws_launch_slide_live_stage_clips(pcm, sl->carry, S.meta, A, (long long)(g0 + i0), nw, (long long)G.hop, (int)G.clip, S.stage, st));
+                if ((e = spectral_device(h, h->dsp, S.stage, 0, nw, S.win + i0 * F, nullptr, st, 0))) return e;
+            }
+        }
+        if ((e = finish(ctx, S.win, (size_t)c, g0, st))) return e;
+    }
+    if (n_win && (e = finish(ctx, S.win, 0, n_win, st))) return e;
+    // 3. the new carry and retained rows (after every read of the old ones above)
+    KWS_LAUNCH_TRY("slide live commit kernel", kws_launch_slide_live_commit(pcm, S.rows, S.meta, A, (long long)G.hop, (int)G.clip, shared ? G.run : 0, ncols, sl->carry, sl->kept, st));
+    commit_mirrors();
+    return EI_IMPULSE_OK;
+}
 
 extern "C" {
 #pragma GCC visibility push(default)
@@ -108,103 +235,10 @@ EI_IMPULSE_ERROR kws_slide_live_push_device(kws_slide_live *sl, size_t n, const 
 {
     if (!sl) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     kws_handle *h = sl->h;
-    const SlideGeom &G = sl->G;
-    const bool shared = sl->path == KWS_SLIDE_SHARED;
     std::lock_guard<std::mutex> lk(h->mu);
-    // argument checks and every count of the push, before any state changes
-    EI_IMPULSE_ERROR e = sl->check_push(n, streams, pcm, offsets, lengths, n_windows, scores);
-    if (e) return e;
-    // the entries with device work (A of them): windows, or new samples to carry
-    std::vector<size_t> counts(n, 0);
-    std::vector<long long> off, n0, len, sid, w0, pc0, np, rbase(1, 0), wbase(1, 0);
-    for (size_t i = 0; i < n; ++i) {
-        const size_t s = streams[i];
-        if (!lengths[i]) continue;
-        const size_t a0 = G.windows(sl->n[s]), a1 = G.windows(sl->n[s] + lengths[i]);
-        counts[i] = a1 - a0;
-        const unsigned long long p0 = sl->pc[s], p1 = sl->positions(a1);
-        off.push_back((long long)offsets[i]);
-        n0.push_back((long long)sl->n[s]);
-        len.push_back((long long)lengths[i]);
-        sid.push_back((long long)s);
-        w0.push_back((long long)a0);
-        pc0.push_back((long long)p0);
-        np.push_back((long long)(p1 - p0));
-        rbase.push_back(rbase.back() + (shared ? (long long)(p1 - p0) + (long long)(G.pre ? a1 - a0 : 0) : 0));
-        wbase.push_back(wbase.back() + (long long)(a1 - a0));
-    }
-    const int A = (int)off.size();
-    const size_t n_frames = (size_t)rbase.back(), n_win = (size_t)wbase.back();
-    const Model &m = h->model;
-    const size_t F = m.nn_input_frame_size, C = m.labels.size();
-    const int ncols = G.ncols, nfi = G.nfi;
-    if (n_win > (size_t)1 << 40 || n_win * C > (size_t)1 << 40) return fail(KWS_ERROR_BAD_ARGUMENT, "too many windows");
-    for (size_t i = 0; i < n; ++i) n_windows[i] = counts[i];
-    const bool count = KwsChunkCounts::wanted(h);
-    auto commit_mirrors = [&]() {
-        for (size_t i = 0; i < n; ++i) {
-            const size_t s = streams[i];
-            sl->n[s] += lengths[i];
-            sl->pc[s] = sl->positions(G.windows(sl->n[s]));
-        }
-    };
-    if (A == 0 && !(count && h->d_flags)) {
-        commit_mirrors();
-        return EI_IMPULSE_OK;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    KwsWindowScratch &S = sl->scratch;
-    // staged items: a rows item is nfi frames of S1 samples; a direct item is a window
-    const size_t item_len = (size_t)nfi * G.S1, n_items = (n_frames + nfi - 1) / nfi;
-    const size_t item_cap = kws_window_item_cap(item_len), clip_cap = kws_window_item_cap(G.clip), win_chunk = kws_window_chunk(F, n_win);
-    const size_t stage_need = shared ? std::min(item_cap, std::max<size_t>(n_items, 1)) * item_len : std::min(clip_cap, win_chunk) * G.clip;
-    const size_t wrap_need = shared ? std::min(item_cap, std::max<size_t>(n_items, 1)) : 1;
-    if ((e = S.reserve(h, stage_need, wrap_need, win_chunk * F, std::max<size_t>(n_items * nfi * ncols, 1), 7 * (size_t)A + 2 * ((size_t)A + 1), win_chunk)))
-        return e;
-    ScratchUse use(h, st);
-    if (count && n_win == 0) {
-        if ((e = KwsChunkCounts::none(h, st))) return e;
-        if (A == 0) {
-            commit_mirrors();
-            return EI_IMPULSE_OK;
-        }
-    }
-    // per-entry tables (kws_slide_live_kernels.hip KwsSlideLiveMeta)
-    if ((e = kws_upload_tables(S, { &off, &n0, &len, &sid, &w0, &pc0, &np, &rbase, &wbase }, st))) return e;
-    if (shared && n_items) {
-        // 1. the rows this push needs: nfi independent frames per item, S1 samples apart, each with its predecessor in the sample before it
-        const KwsDspPlan PF = G.first_plan(h);
-        for (size_t g0 = 0; g0 < n_items; g0 += item_cap) {
-            const int c = (int)std::min(item_cap, n_items - g0);
-            KWS_LAUNCH_TRY("slide live staging kernel", kws_launch_slide_live_stage_rows(pcm, sl->carry, S.meta, A, (long long)g0, c, (long long)n_frames, nfi, (int)G.S1, G.used, G.stride,
-                                                                                         (long long)G.hop, (int)G.clip, G.pre, S.stage, S.wrap, st));
-            if ((e = spectral_device(h, PF, S.stage, 0, c, S.rows + g0 * nfi * ncols, S.wrap, st, nfi * ncols))) return e;
-        }
-    }
-    // 2. windows in chunks through the finishing step (cmvnw + the network)
-    KwsChunkCounts cnt(h);
-    if ((e = cnt.begin(S.acc, n_win, st))) return e;
-    for (size_t g0 = 0; g0 < n_win; g0 += win_chunk) {
-        const int c = (int)std::min(win_chunk, n_win - g0);
-        if (shared) {
-            KWS_LAUNCH_TRY("slide live gather kernel", kws_launch_slide_live_gather(S.rows, sl->kept, S.meta, A, (long long)g0, c, (long long)sl->hs, G.run, G.pre, ncols, S.win, st));
-        } else {
-            for (size_t i0 = 0; i0 < (size_t)c; i0 += clip_cap) {
-                const int nw = (int)std::min(clip_cap, (size_t)c - i0);
-                KWS_LAUNCH_TRY("slide live staging kernel", kws_launch_slide_live_stage_clips(pcm, sl->carry, S.meta, A, (long long)(g0 + i0), nw, (long long)G.hop, (int)G.clip, S.stage, st));
-                if ((e = spectral_device(h, h->dsp, S.stage, 0, nw, S.win + i0 * F, nullptr, st, 0))) return e;
-            }
-        }
-        if ((e = kws_finish_window_chunk(h, S.win, (size_t)c, scores + g0 * C, features ? features + g0 * F : nullptr, cnt.fast, st)) ||
-            (e = cnt.chunk(st)))
-            return e;
-    }
-    if ((e = cnt.end(st))) return e;
-    // 3. the new carry and retained rows (after every read of the old ones above)
-    KWS_LAUNCH_TRY("slide live commit kernel", kws_launch_slide_live_commit(pcm, S.rows, S.meta, A, (long long)G.hop, (int)G.clip, shared ? G.run : 0, ncols, sl->carry, sl->kept, st));
-    commit_mirrors();
-    return EI_IMPULSE_OK;
+    SlideLiveOwn own{ sl, scores, features, KwsChunkCounts(h) };
+    return kws_slide_live_run(sl, n, streams, pcm, offsets, lengths, scores, n_windows, h->model.labels.size(), 0, KwsChunkCounts::wanted(h) && h->d_flags,
+                              slide_live_own_finish, &own, (hipStream_t)stream);
 }
 
 #pragma GCC visibility pop

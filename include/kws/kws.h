@@ -570,6 +570,65 @@ EI_IMPULSE_ERROR kws_slide_live_window_count(const kws_slide_live *sl, size_t st
 EI_IMPULSE_ERROR kws_slide_live_push_device(kws_slide_live *sl, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets,
                                             const size_t *lengths, float *scores, float *features, size_t *n_windows, void *stream);
 
+/* ---- banks over recording scans, live streams and clips of their own lengths --------------------------------------------------------
+ * The bank forms of kws_scan_recordings_device, kws_live_*, kws_slide_live_* and kws_run_classifier_ragged_device: with these every entry
+ * point that takes int16 audio has one.  Staging, the spectral kernels, gathering, cmvnw and -- in a live session -- every stream's
+ * carried samples and retained rows exist ONCE, through the first member; each member adds its network, and in continuous mode its
+ * moving-average filters, which one kernel launch serves for all members.
+ *   scores, raw_scores   HOST arrays of K DEVICE pointers, as in the bank calls above; scores[k] is [rows][kws_label_count(member k)] float
+ *   features             [rows][feature_count] float, device, optional (NULL): the shared feature matrix (live slide, ragged)
+ *   rows, n_windows      window counts are any member's (kws_scan_window_count, kws_*_live_window_count); the ragged call: rows = B
+ *   other arguments as in the single-model entry point of the same name
+ * Parity contract.  Member k's rows are bit-identical to what that member's own entry point writes in KWS_MODE_EXACT on the same input --
+ * kws_scan_recordings_device, kws_live_push_device, kws_slide_live_push_device, kws_run_classifier_ragged_device; for a live session: the
+ * same sequence of pushes on a session of its own at the same slicing or hop.  That holds for scores and raw_scores, for int8 and float32
+ * members alike, and `features` is bit-identical to any member's own; through those entry points' contracts the rows match the reference
+ * (int8 bit-exact, float32 scores within 1e-6), and the live slide's DIRECT and SHARED paths stay bit-identical to each other.
+ * Mode.  These calls always run the exact kernels.  They neither read nor change any member's kws_set_mode state, fast counters
+ * (kws_fast_fallback_count / kws_fast_exact_count) or logits tap, and they write no tap.
+ * Skipping a member.  scores[k] == NULL skips member k in the scan, the live slide push and the ragged call, which keep nothing per
+ * member.  raw_scores == NULL, or a NULL entry of it, means no raw scores for that member (its scores are filtered in place).
+ * kws_bank_live_push_device is stricter: a member's moving-average filter must see every window, so a NULL scores[k] is
+ * KWS_ERROR_BAD_ARGUMENT and no state changes.  For fewer members make a smaller bank: a handle may be a member of several banks.
+ * Empty and refused calls.  Every scores[k] NULL (and features NULL where there is one): KWS_ERROR_BAD_ARGUMENT.  No window, or no clip:
+ * EI_IMPULSE_OK, nothing written.  Whatever the single-model entry point refuses is refused with its code before anything is enqueued -- a
+ * slicing the stream API refuses, a bad hop or flags, a ragged length outside 1 .. kws_frame_count frames, a stream named twice -- and
+ * kws_last_error is set as that entry point sets it.
+ * Ordering and locks.  A call or push counts as a call on EVERY member: it takes the members' locks in the bank's fixed order (by address)
+ * and brackets every member's scratch, as the bank calls above.  Calls on one bank, its sessions' pushes, resets and counts included, are
+ * serialised.
+ * Lifetimes.  Destroy sessions before their bank, and banks before their members; a session's destroy waits for its enqueued work.
+ * Device memory.  Per live stream ONE carry ring and ONE retained-row ring (kws_live_create's / kws_slide_live_create's) serve all
+ * members; the continuous session adds sum_k labels_k x (taps + 1) floats of filter state per stream.  Per-push scratch is the
+ * single-model session's, plus the bank's shared feature matrix for one chunk (at most 64 MiB; the ragged call without `features`:
+ * B x feature_count floats).  The scan and the ragged call use the FIRST member's scan / ragged scratch with the single-model bounds;
+ * no session keeps anything in a member's own scratch between pushes. */
+/* kws_scan_recordings_device for K models */
+EI_IMPULSE_ERROR kws_bank_scan_recordings_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                 size_t slice_samples, float *const *scores, float *const *raw_scores, void *stream);
+/* kws_live_* for K models: one session, one copy of every stream's carry and retained rows, one moving-average state per member */
+typedef struct kws_bank_live kws_bank_live;
+EI_IMPULSE_ERROR kws_bank_live_create(kws_bank *b, size_t S, size_t slice_samples, kws_bank_live **out);
+void kws_bank_live_destroy(kws_bank_live *lv);
+EI_IMPULSE_ERROR kws_bank_live_reset(kws_bank_live *lv, const size_t *streams, size_t n);
+EI_IMPULSE_ERROR kws_bank_live_window_count(const kws_bank_live *lv, size_t stream, size_t n_new, int finish, size_t *n_windows);
+EI_IMPULSE_ERROR kws_bank_live_push_device(kws_bank_live *lv, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets,
+                                           const size_t *lengths, const int *finish, float *const *scores, float *const *raw_scores,
+                                           size_t *n_windows, void *stream);
+/* kws_slide_live_* for K models */
+typedef struct kws_bank_slide_live kws_bank_slide_live;
+EI_IMPULSE_ERROR kws_bank_slide_live_create(kws_bank *b, size_t S, size_t hop_samples, int flags, kws_bank_slide_live **out);
+void kws_bank_slide_live_destroy(kws_bank_slide_live *sl);
+int kws_bank_slide_live_path(const kws_bank_slide_live *sl);
+EI_IMPULSE_ERROR kws_bank_slide_live_reset(kws_bank_slide_live *sl, const size_t *streams, size_t n);
+EI_IMPULSE_ERROR kws_bank_slide_live_window_count(const kws_bank_slide_live *sl, size_t stream, size_t n_new, size_t *n_windows);
+EI_IMPULSE_ERROR kws_bank_slide_live_push_device(kws_bank_slide_live *sl, size_t n, const size_t *streams, const int16_t *pcm,
+                                                 const size_t *offsets, const size_t *lengths, float *const *scores, float *features,
+                                                 size_t *n_windows, void *stream);
+/* kws_run_classifier_ragged_device for K models: the first member's DSP route once, then every member's network on the full-stride rows */
+EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B,
+                                                       float *const *scores, float *features, void *stream);
+
 /* ---- multi-GPU: clips shard contiguously over the GPUs of one node (rank r owns clips [r*B, (r+1)*B)), tables are
  * replicated, nothing is exchanged inside the pipeline; the one collective is the all-gather of the per-clip scores over xGMI.
  * It goes through RCCL's C API (librccl is opened on first use: single-GPU applications do not need it).  One process per GPU:
