@@ -1053,6 +1053,24 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
 
 // PROF: development aid -- shader-clock totals per phase of wave 0 of workgroup 0 (tools/gpu_fast_phase_profile.py)
 #define KWS_FAST_NPHASE 20       // 0..8 phases, 9..11 detail of block 0, 12 + b: block b >= 1 on its own
+// the three-wave build's pass loop (each can be switched off on the compiler's command line, to be measured apart): a second copy of the mel phase for passes
+// of eight live frames, sample requests as scalar base + 32-bit lane offset, the frame energies' log once per clip
+#ifndef KWS_FAST_FULL_PASS
+#define KWS_FAST_FULL_PASS (KWS_FAST_WPS >= 3)
+#endif
+#ifndef KWS_FAST_SOFS
+#define KWS_FAST_SOFS (KWS_FAST_WPS >= 3)
+#endif
+#ifndef KWS_FAST_LATE_ELOG
+#define KWS_FAST_LATE_ELOG (KWS_FAST_WPS >= 3)
+#endif
+// what a pass parks as a frame's energy: three waves per SIMD the reduced, scaled sum itself -- its zero handling and log are taken once per clip, in front of
+// the DCT, for all frames at once --, otherwise the log
+#if KWS_FAST_LATE_ELOG
+#define KWS_FAST_ELOG(e) (e)
+#else
+#define KWS_FAST_ELOG(e) fast_log((e) == 0.0f ? FLT_EPSILON : (e))
+#endif
 #define FPH(i) do { if (PROF) { const long long now_ = clock64(); ph[i] += now_ - tlast; tlast = now_; } } while (0)
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1267,8 +1285,34 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         } else {
         const int16_t *xbase = pcm + (size_t)clip * n_samples;
         const int wrap_prev = (int)xbase[n_samples - 1];                 // x[-1] is the window's last sample (processing.hpp:68, 104-106)
+#if KWS_FAST_SOFS
+        // (three waves per SIMD) The sample requests as the clip's base -- wave-uniform: scalar registers -- plus a 32-bit byte offset per lane.  A lane's
+        // offset advances by eight frames per pass, and the clamp of the frame index to the last frame is one minimum against the lane's offset in that frame,
+        // formed once per clip.  sofs0 is four bytes ahead of the lane's first sample (the x[-2], x[-1] in front of frame 0 would make it negative): the
+        // requests carry the -4 in their constant offsets.
+        const char *const xb = (const char *)xbase;
+        const int pass_bytes = 2 * KWS_FAST_MEL_CHUNK * frame_stride;
+        const int sofs0 = 2 * (min(fg, nfr - 1) * frame_stride + 2 * nbA), sofs_last = 2 * ((nfr - 1) * frame_stride + 2 * nbA);
+        auto sofs = [&](int q) { return min(sofs0 + q * pass_bytes, sofs_last); };
+        const int tch_d = 64 * fl - 4 * nbA;                               // the touch's segment of a frame against the lane's samples (>= 0)
+        auto fetch_at = [&](auto first_c, int so, fast_i2 (&raw)[2][8]) {
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    // only the clip's first request can lie in front of the PCM buffer (frame 0's x[-2], x[-1]: clamped to the window's start)
+                    const unsigned o = (decltype(first_c)::value && blk == 0 && i == 0) ? (unsigned)max(so, 4) : (unsigned)so;
+                    raw[blk][i] = *(const fast_i2 *)(xb + o + (2 * (4 * blk + 32 * (i >> 1) + 128 * (i & 1)) - 4));
+                }
+        };
+        // (the profiling forms spill two and three more registers with them and keep the addresses below)
+        constexpr bool SOFS = !PROF;
+#endif
         // a point's four samples x[2n - 2 .. 2n + 1] of frame f, requested one pass ahead
         auto fetch = [&](int q, fast_i2 (&raw)[2][8]) {
+#if KWS_FAST_SOFS
+            if constexpr (SOFS) { fetch_at(std::false_type(), sofs(q), raw); return; }
+#endif
             const int f = min(KWS_FAST_MEL_CHUNK * q + fg, nfr - 1);
             const int16_t *xf = xbase + (f * frame_stride + 2 * nbA - 2);
 #pragma unroll
@@ -1284,18 +1328,57 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         // those find their lines in the cache (a pass is shorter than an HBM round trip under load); the value is only handed to
         // an empty asm statement a pass later, which is what keeps its register reserved until the data has arrived
         auto touch = [&](int q) {
+#if KWS_FAST_SOFS
+            if constexpr (SOFS) return *(const int *)(xb + (unsigned)(sofs(q) + tch_d));
+#endif
             const int f = min(KWS_FAST_MEL_CHUNK * q + fg, nfr - 1);
             return *(const int *)(xbase + (f * frame_stride + 32 * fl));
         };
         // ---- mel filterbank for the frames of a pass: dot_by_row as a register-tap gather, zero handling, log.  pairs = pairs of
         //      frame slots a lane half walks (2: slots 4 h .. 4 h + 3 of an eight-frame pass; 1: the tail pass, slots 0, 1)
         // adj1: added to the image offset of frame slot 1's stores (the tail pass parks the NEXT clip's last frame in the stash)
-        auto mel_phase = [&](int fbase, int nfc, int pairs, int adj1) {
+        // full_c (three waves per SIMD): a pass whose eight frame slots are all live -- every lane passes `slot < nfc`, and a lane index is below NF for
+        // filters 0..31 and below 8 for the rest --: the power rows are requested as one batch, the logs sit in one block and the stores carry no predicate
+        auto mel_phase = [&](auto full_c, int fbase, int nfc, int pairs, int adj1) {
             WAVE_SYNC();
             // filters 0..31: lane half h takes frame slots 4 h .. 4 h + 3; filters 32..39 (40 filters only): one frame slot each
             const int j2 = 32 + (lane_c & 7), sl2 = lane_c >> 3;
             const float *p1 = pw + 4 * half * pstride + start1, *p2 = pw + sl2 * pstride + start2;
             float macc[5] = { 1.0f, 1.0f, 1.0f, 1.0f, 1.0f };
+            if constexpr (decltype(full_c)::value) {
+                float xv[4][NZ], xv2[NZ2];
+                if (DG > 4) {
+#pragma unroll
+                    for (int n = 0; n < NZ2; ++n) xv2[n] = p2[n];
+                }
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int n = 0; n < NZ; ++n) xv[s][n] = p1[s * pstride + n];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int n = 0; n < NZ; ++n) acc = __fmaf_rn(xv[s][n], w1[n], acc);
+                    macc[s] = acc;
+                }
+                float acc2 = 0.0f;
+                if (DG > 4) {
+#pragma unroll
+                    for (int n = 0; n < NZ2; ++n) acc2 = __fmaf_rn(xv2[n], w2[n], acc2);
+                }
+                macc[4] = acc2;
+#pragma unroll
+                for (int s = 0; s < 5; ++s) {
+                    const float a = macc[s] == 0.0f ? FLT_EPSILON : macc[s];                           // functions.hpp:63-69
+                    macc[s] = MFE ? a : fast_log(a);
+                }
+                float *const d1 = img + (fbase + 4 * half) * fs + t;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) d1[s * fs] = macc[s];
+                if (DG > 4) img[(fbase + sl2) * fs + j2] = macc[4];
+                return;
+            }
 #pragma unroll
             for (int s2 = 0; s2 < 4; s2 += 2) {
                 if (s2 >= 2 * pairs) break;
@@ -1334,6 +1417,10 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
             if (DG > 4 && sl2 < nfc && j2 < NF) img[(fbase + sl2) * fs + j2 + (sl2 == 1 ? adj1 : 0)] = macc[4];
         };
         fast_i2 nxt[2][8];
+#if KWS_FAST_SOFS
+        if constexpr (SOFS) fetch_at(std::true_type(), sofs0, nxt);
+        else
+#endif
         fetch(0, nxt);
         int touched = touch(1);
 #if KWS_FAST_WPS >= 3
@@ -1346,7 +1433,14 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         int touched_tail = 0;
         const int16_t *const xnext = pcm + (size_t)max(next_clip, 0) * n_samples;
         if (pair_tail && lane_c < 8) touched_tail = *(const int *)(xnext + (nfr - 1) * frame_stride + 32 * lane_c);
+        // one eight-frame pass.  (Three waves per SIMD its body is a lambda: the same statements as the loop's body, but the form from which the headline form's
+        // registers are allocated at 168 with one spilled register -- as the loop's own body, with the addresses and the second mel copy above, it
+        // spills 37.  The two-wave build keeps the loop, and with it its listing.)
+#if KWS_FAST_WPS >= 3
+        auto pass_body = [&](int q) {
+#else
         for (int q = 0; q < n_pass; ++q) {
+#endif
             const int fbase = KWS_FAST_MEL_CHUNK * q;
             const int f = fbase + fg;
             const bool live = f < nfr;
@@ -1468,14 +1562,28 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                 }
                 // frame energy (feature.hpp:289-298): its log is parked until the DCT has run
                 esum = oct_sum(esum) * pscale;                       // the power rows are unscaled: the energy takes the scale once
-                if (fl == 0 && live) elog[f] = fast_log(esum == 0.0f ? FLT_EPSILON : esum);
+                if (fl == 0 && live) elog[f] = KWS_FAST_ELOG(esum);
             }
             FPH(2);
 
-            mel_phase(fbase, min(KWS_FAST_MEL_CHUNK, nfr - fbase), 2, 0);
+#if KWS_FAST_FULL_PASS
+            // The mel phase is compiled twice: a pass whose eight frame slots are all live (every pass of the usual 49 frames: six passes and a tail) takes the
+            // copy without frame predicates.  The test is wave-uniform, a scalar compare of the frames left: one per pass rather than one per clip on
+            // `n_tail != 0 || n_frames % 8 == 0` -- it picks the same copy wherever that test holds, and the full copy for the leading passes of every other
+            // frame count.  (The whole pass compiled twice, a loop per copy picked once per clip, spilled 30 registers of the headline form;
+            // profiles/full_pass.md.)
+            if (nfr - fbase >= KWS_FAST_MEL_CHUNK) mel_phase(std::true_type(), fbase, KWS_FAST_MEL_CHUNK, 2, 0);
+            else
+#endif
+            mel_phase(std::false_type(), fbase, min(KWS_FAST_MEL_CHUNK, nfr - fbase), 2, 0);
             WAVE_SYNC();
             FPH(3);
+#if KWS_FAST_WPS >= 3
+        };
+        for (int q = 0; q < n_pass; ++q) pass_body(q);
+#else
         }
+#endif
 
         asm volatile("" : : "v"(touched_tail));
         if (n_tail == 1 && have_stash) {
@@ -1582,10 +1690,10 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                     prow[0] = pdc;
                 }
                 esum = half_wave_sum(esum) * pscale;
-                if (t == 0 && live_t) *((pair_tail && half == 1) ? stash + 47 : elog + ft) = fast_log(esum == 0.0f ? FLT_EPSILON : esum);
+                if (t == 0 && live_t) *((pair_tail && half == 1) ? stash + 47 : elog + ft) = KWS_FAST_ELOG(esum);
             }
             // frame slot 1 of a paired pass belongs to the next clip: its row goes to the stash instead of image row n_frames
-            mel_phase(KWS_FAST_MEL_CHUNK * n_pass, pair_tail ? 2 : n_tail, 1, pair_tail ? (int)(stash - img) - nfr * fs : 0);
+            mel_phase(std::false_type(), KWS_FAST_MEL_CHUNK * n_pass, pair_tail ? 2 : n_tail, 1, pair_tail ? (int)(stash - img) - nfr * fs : 0);
             have_stash = pair_tail;
             WAVE_SYNC();
         }
@@ -1606,7 +1714,12 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                     for (int nt = 0; nt < 2; ++nt) dB[g][i][nt] = dct_frag[((g * 2 + i) * 2 + nt) * KWS_WAVE + lane_l];
             const float *arow = img + lm * fs + 2 * lq;
             float e0 = 0.0f;
+#if KWS_FAST_LATE_ELOG
+            // (the passes parked the frame energies themselves: zero handling and log for all frames at once, feature.hpp:289-298)
+            if (lane_l < nfr) { const float en = elog[lane_l]; e0 = fast_log(en == 0.0f ? FLT_EPSILON : en); }
+#else
             if (lane_l < nfr) e0 = elog[lane_l];
+#endif
             v4f acc[4][2];
             // raised wave priority for the transform's 16 DG MFMAs, as for the convolution's contraction loop (fast_conv_tiles)
             __builtin_amdgcn_s_setprio(1);
