@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "kws_bank_live_create", "kws_bank_live_destroy", "kws_bank_live_reset", "kws_bank_live_window_count", "kws_bank_live_push_device",
     "kws_bank_slide_live_create", "kws_bank_slide_live_destroy", "kws_bank_slide_live_path", "kws_bank_slide_live_reset",
     "kws_bank_slide_live_window_count", "kws_bank_slide_live_push_device",
+    "kws_bank_run_classifier_routed_device", "kws_bank_run_classifier_ragged_routed_device", "kws_bank_live_route", "kws_bank_slide_live_route",
     "kws_window_frame_count", "kws_run_classifier_ragged_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_slide_live_create", "kws_slide_live_destroy", "kws_slide_live_path", "kws_slide_live_reset", "kws_slide_live_window_count",
@@ -237,6 +238,11 @@ def lib():
             L.kws_bank_slide_live_reset.argtypes = [vp, vp, sz]
             L.kws_bank_slide_live_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
             L.kws_bank_slide_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "kws_bank_live_route"):
+            L.kws_bank_run_classifier_routed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+            L.kws_bank_run_classifier_ragged_routed_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp]
+            L.kws_bank_live_route.argtypes = [vp, vp, sz, vp]
+            L.kws_bank_slide_live_route.argtypes = [vp, vp, sz, vp]
         L.kws_device_malloc.argtypes = [C.POINTER(vp), sz]
         L.kws_device_free.argtypes = [vp]
         L.kws_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -492,6 +498,15 @@ class Model:
         return SlideStreams(self, n_streams, hop_samples, flags)
 
 
+def _routes(routes, n):
+    """a host sequence of n route masks as the uint32 array the routed calls read (None: NULL, every member)"""
+    if routes is None:
+        return None
+    r = np.ascontiguousarray(routes, np.uint32)
+    assert r.shape == (n,), "one route per clip or stream"
+    return _p(r)
+
+
 class Bank:
     """K loaded models with an identical DSP block (kws_bank; the contract is in include/kws/kws.h): a call computes the front end once and
     every member's scores from it, always with the exact kernels.  scores_ptrs: one device pointer per member ([rows][that member's
@@ -521,6 +536,11 @@ class Bank:
     def run_classifier_batch_device(self, pcm_ptr, B, scores_ptrs, features_ptr=None, stream=None):
         _check(self.L.kws_bank_run_classifier_batch_device(self.b, pcm_ptr, B, self._scores(scores_ptrs), features_ptr, stream))
 
+    def run_classifier_routed_device(self, pcm_ptr, B, routes, scores_ptrs, features_ptr=None, stream=None):
+        """run_classifier_batch_device with a route per clip (host sequence of B masks: bit k set = member k scores the clip; None: every
+        member): only the rows of routed (clip, member) pairs are written, features hold every row"""
+        _check(self.L.kws_bank_run_classifier_routed_device(self.b, pcm_ptr, B, _routes(routes, B), self._scores(scores_ptrs), features_ptr, stream))
+
     def cmvn_inference_batch_device(self, mfcc_ptr, B, scores_ptrs, features_ptr=None, stream=None):
         _check(self.L.kws_bank_cmvn_inference_batch_device(self.b, mfcc_ptr, B, self._scores(scores_ptrs), features_ptr, stream))
 
@@ -542,12 +562,17 @@ class Bank:
         _check(self.L.kws_bank_scan_recordings_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, slice_samples or self._models[0].clip_samples // 4,
                                                       self._scores(scores_ptrs), raw, stream))
 
-    def run_classifier_ragged_device(self, pcm_ptr, offsets, lengths, scores_ptrs, features_ptr=None, stream=None):
-        """Model.run_classifier_ragged_device for every member: the DSP route once, features (optional) shared"""
+    def run_classifier_ragged_device(self, pcm_ptr, offsets, lengths, scores_ptrs, features_ptr=None, stream=None, routes=None):
+        """Model.run_classifier_ragged_device for every member: the DSP route once, features (optional) shared.  routes: a mask per clip as in
+        run_classifier_routed_device (None: every member scores every clip)"""
         off = np.ascontiguousarray(offsets, np.uint64)
         ln = np.ascontiguousarray(lengths, np.uint64)
         assert off.shape == ln.shape and off.ndim == 1
-        _check(self.L.kws_bank_run_classifier_ragged_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, self._scores(scores_ptrs), features_ptr, stream))
+        if routes is None:
+            _check(self.L.kws_bank_run_classifier_ragged_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, self._scores(scores_ptrs), features_ptr, stream))
+            return
+        _check(self.L.kws_bank_run_classifier_ragged_routed_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, _routes(routes, off.size),
+                                                                   self._scores(scores_ptrs), features_ptr, stream))
 
     def live_streams(self, n_streams, slice_samples=None):
         """a live session of n_streams streams in continuous mode for every member (kws_bank_live_*): see BankLiveStreams"""
@@ -709,7 +734,8 @@ class BankLiveStreams:
 
     def push_device(self, pcm_ptr, streams, offsets, lengths, scores_ptrs, raw_scores_ptrs=None, finish=None, stream=None):
         """LiveStreams.push_device for every member: scores_ptrs (and raw_scores_ptrs) hold one device pointer per member, [sum][that
-        member's n_labels]; no member can be skipped (its filter must see every window).  Returns n_windows per entry (numpy uint64)."""
+        member's n_labels]; a member can be skipped (None) only where no stream named in the push routes to it (its filter must see every
+        window of the streams it serves).  Returns n_windows per entry (numpy uint64)."""
         st = np.ascontiguousarray(streams, np.uint64)
         off = np.ascontiguousarray(offsets, np.uint64)
         ln = np.ascontiguousarray(lengths, np.uint64)
@@ -729,6 +755,12 @@ class BankLiveStreams:
             return
         st = np.ascontiguousarray(streams, np.uint64)
         _check(self.L.kws_bank_live_reset(self.lv, _p(st), st.size))
+
+    def route(self, streams, routes):
+        """routes[i] (bit k set = member k) becomes the route of stream streams[i]; only streams in their start state (created, reset or just
+        finished) may be routed.  A session that never calls this scores every stream with every member."""
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_bank_live_route(self.lv, _p(st), st.size, _routes(routes, st.size)))
 
     def close(self):
         if getattr(self, "lv", None):
@@ -779,6 +811,11 @@ class BankSlideStreams:
             return
         st = np.ascontiguousarray(streams, np.uint64)
         _check(self.L.kws_bank_slide_live_reset(self.sl, _p(st), st.size))
+
+    def route(self, streams, routes):
+        """routes[i] (bit k set = member k) becomes the route of stream streams[i], from the next push on"""
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_bank_slide_live_route(self.sl, _p(st), st.size, _routes(routes, st.size)))
 
     def close(self):
         if getattr(self, "sl", None):

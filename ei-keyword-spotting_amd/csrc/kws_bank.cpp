@@ -43,9 +43,92 @@ static EI_IMPULSE_ERROR bank_same_front_end(const kws_handle *a, const kws_handl
     return EI_IMPULSE_OK;
 }
 
-// every member's network from the feature matrix feat [B][F] (device); scores[k] + row0 * labels of member k is where its rows go
-EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, hipStream_t s)
+// Routes to lists, as host arithmetic: one counting pass over the routes sizes the K lists, a second one fills them in row order, so every
+// list is ascending.  Member k's list is out[at[k]] = its count, then its rows; at[K] = the packed size.
+void kws_bank_route_lists(const uint32_t *routes, size_t n, size_t K, std::vector<int> &out, size_t *at)
 {
+    size_t count[KWS_BANK_MAX] = { 0 };
+    for (size_t i = 0; i < n; ++i)
+        for (uint32_t r = routes[i] & ((1u << K) - 1u); r; r &= r - 1) ++count[__builtin_ctz(r)];
+    at[0] = 0;
+    for (size_t k = 0; k < K; ++k) at[k + 1] = at[k] + 1 + count[k];
+    out.resize(at[K]);
+    size_t fill[KWS_BANK_MAX];
+    for (size_t k = 0; k < K; ++k) { out[at[k]] = (int)count[k]; fill[k] = at[k] + 1; }
+    for (size_t i = 0; i < n; ++i)
+        for (uint32_t r = routes[i] & ((1u << K) - 1u); r; r &= r - 1) out[fill[__builtin_ctz(r)]++] = (int)i;
+}
+
+size_t kws_bank_route_check(const uint32_t *routes, size_t n, size_t K)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (routes[i] >> K) return i;
+    return n;
+}
+
+// The routed form of bank_networks: member k runs over the rows whose route names it.  The lists travel with the call (one upload, behind
+// the stream's earlier work: a chunk's lists replace the previous chunk's only after its launches); a member with an empty list, or without
+// a score buffer, launches nothing.
+static EI_IMPULSE_ERROR bank_networks_routed(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, const uint32_t *routes, hipStream_t s)
+{
+    const size_t K = b->m.size(), F = b->m[0]->model.nn_input_frame_size;
+    size_t at[KWS_BANK_MAX + 1];
+    // (the host copy is read by the upload of the call or chunk before: that upload has ended before it is rewritten)
+    if (b->lists_ev_used) HIP_TRY(hipEventSynchronize(b->lists_ev));
+    b->lists_ev_used = false;
+    kws_bank_route_lists(routes, B, K, b->h_lists, at);
+    EI_IMPULSE_ERROR e;
+    if ((e = grow_buffer(&b->d_lists, &b->lists_cap, at[K]))) return e;
+    KwsBankOut o16{}, o64{};
+    KwsBankLists l16{}, l64{}, lq{};
+    KwsBankQuant Q{};
+    int n16 = 0, n64 = 0, nq = 0;
+    bool any = false;
+    for (size_t k = 0; k < K; ++k) {
+        kws_handle *h = b->m[k];
+        const int n = b->h_lists[at[k]];
+        if (!scores[k] || n == 0) continue;
+        any = true;
+        if (h->is_float) continue;
+        if (kws_nn_uses_mfma(h->nn)) {
+            const bool w16 = h->nn.blk[0].in_cpad == 16;
+            KwsBankOut &o = w16 ? o16 : o64;
+            (w16 ? l16 : l64).list[o.n] = b->d_lists + at[k];
+            (w16 ? n16 : n64) = std::max(w16 ? n16 : n64, n);
+            o.rec[o.n] = (int)k; o.scores[o.n] = scores[k] + row0 * h->model.labels.size(); ++o.n;
+        } else {
+            if ((e = ensure_scratch(h, B))) return e;         // (its tensor is indexed by row: B rows, the listed ones written)
+            lq.list[Q.n] = b->d_lists + at[k];
+            nq = std::max(nq, n);
+            Q.scale[Q.n] = h->nn.in_scale; Q.zp[Q.n] = h->nn.in_zp; Q.q[Q.n] = h->s_q; ++Q.n;
+        }
+    }
+    if (!any) return EI_IMPULSE_OK;
+    HIP_TRY(hipMemcpyAsync(b->d_lists, b->h_lists.data(), at[K] * sizeof(int), hipMemcpyHostToDevice, s));
+    if (!b->lists_ev) HIP_TRY(hipEventCreateWithFlags(&b->lists_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(b->lists_ev, s));
+    b->lists_ev_used = true;
+    const int grid_cap = grid_cap_nn(b->m[0]);
+    KWS_LAUNCH_TRY_OBJ("routed bank NN kernel", kws_launch_bank_nn_mfma_routed(b->d_rec, o16, l16, 16, feat, n16, grid_cap, s));
+    KWS_LAUNCH_TRY_OBJ("routed bank NN kernel", kws_launch_bank_nn_mfma_routed(b->d_rec, o64, l64, 64, feat, n64, grid_cap, s));
+    KWS_LAUNCH_TRY("routed bank quantise kernel", kws_launch_bank_quantize_routed(feat, (int)F, Q, lq, nq, s));
+    for (size_t k = 0; k < K; ++k) {
+        kws_handle *h = b->m[k];
+        const int n = b->h_lists[at[k]];
+        if (!scores[k] || n == 0 || !(h->is_float || !kws_nn_uses_mfma(h->nn))) continue;
+        float *dst = scores[k] + row0 * h->model.labels.size();
+        if ((e = network_device(h, feat, h->s_q, (size_t)n, dst, nullptr, nullptr, nullptr, nullptr, b->d_lists + at[k], s))) return e;
+    }
+    return EI_IMPULSE_OK;
+}
+
+// every member's network from the feature matrix feat [B][F] (device); scores[k] + row0 * labels of member k is where its rows go
+EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, hipStream_t s, const uint32_t *routes)
+{
+    // (routes that all name every member: the unrouted launches, which need no list)
+    const uint32_t every = (1u << b->m.size()) - 1u;
+    for (size_t i = 0; routes && i < B; ++i)
+        if (routes[i] != every) return bank_networks_routed(b, feat, B, scores, row0, routes, s);
     const size_t K = b->m.size(), F = b->m[0]->model.nn_input_frame_size;
     KwsBankOut o16{}, o64{};
     KwsBankQuant Q{};
@@ -98,7 +181,7 @@ EI_IMPULSE_ERROR bank_window_finish(void *ctx, float *win, size_t n, size_t g0, 
         f = b->feat;
     }
     if ((e = cmvn_nn_device(h0, win, n, f, nullptr, nullptr, nullptr, nullptr, nullptr, s))) return e;
-    return bank_networks(b, f, n, c.scores, g0, s);
+    return bank_networks(b, f, n, c.scores, g0, s, c.routes ? c.routes + g0 : nullptr);
 }
 
 extern "C" {
@@ -153,6 +236,8 @@ void kws_bank_destroy(kws_bank *b)
     }
     if (b->d_rec) (void)hipFree(b->d_rec);
     if (b->feat) (void)hipFree(b->feat);
+    if (b->d_lists) (void)hipFree(b->d_lists);
+    if (b->lists_ev) (void)hipEventDestroy(b->lists_ev);
     delete b;
 }
 
@@ -177,6 +262,30 @@ EI_IMPULSE_ERROR kws_bank_run_classifier_batch_device(kws_bank *b, const int16_t
     }
     if ((e = mfcc_fused_device(h0, pcm, 0, B, f, nullptr, s))) return e;
     return bank_networks(b, f, B, scores, 0, s);
+}
+
+EI_IMPULSE_ERROR kws_bank_run_classifier_routed_device(kws_bank *b, const int16_t *pcm, size_t B, const uint32_t *routes, float *const *scores, float *features,
+                                                       void *stream)
+{
+    if (!routes) return kws_bank_run_classifier_batch_device(b, pcm, B, scores, features, stream);
+    if (!b || !pcm || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
+    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    const size_t bad = kws_bank_route_check(routes, B, b->m.size());
+    if (bad < B) return fail(KWS_ERROR_BAD_ARGUMENT, "clip %zu: route 0x%x names a member at or above the bank's %zu", bad, routes[bad], b->m.size());
+    if (B == 0) return EI_IMPULSE_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    BankUse use(b, s, false);
+    kws_handle *h0 = b->m[0];
+    EI_IMPULSE_ERROR e;
+    float *f = features;
+    if (!f) {
+        if ((e = grow_buffer(&b->feat, &b->feat_cap, B * (size_t)h0->model.nn_input_frame_size))) return e;
+        f = b->feat;
+    }
+    if ((e = mfcc_fused_device(h0, pcm, 0, B, f, nullptr, s))) return e;
+    return bank_networks(b, f, B, scores, 0, s, routes);
 }
 
 EI_IMPULSE_ERROR kws_bank_cmvn_inference_batch_device(kws_bank *b, const float *mfcc, size_t B, float *const *scores, float *features, void *stream)

@@ -33,6 +33,17 @@ struct KwsBankQuant {
 int kws_launch_bank_nn_mfma(const KwsBankRec *recs, const KwsBankOut &out, int cp, const float *features, int n_clips, int grid_cap, hipStream_t stream);
 int kws_launch_bank_quantize(const float *features, size_t n, const KwsBankQuant &Q, hipStream_t stream);
 
+// Routed calls (a route per row: bit k set = member k scores it): slot i of a launch walks its member's list of rows instead of every row.
+// A list is the `sel` list of the members' own launchers (kws_device.h): [0] = how many, [1 + j] = row, ascending; device memory, uploaded
+// with the call.  n_longest: the longest list of the launch (sizes the grid); a member with an empty list gets no slot.
+struct KwsBankLists {
+    const int *list[KWS_BANK_MAX];
+};
+int kws_launch_bank_nn_mfma_routed(const KwsBankRec *recs, const KwsBankOut &out, const KwsBankLists &lists, int cp, const float *features, int n_longest,
+                                   int grid_cap, hipStream_t stream);
+// row_len: values per feature row; member slot j's tensor is written only at its listed rows
+int kws_launch_bank_quantize_routed(const float *features, int row_len, const KwsBankQuant &Q, const KwsBankLists &lists, int n_longest, hipStream_t stream);
+
 // One moving-average launch for every member of a continuous-mode bank call (kws_bank_windows_kernels.hip): member slot i filters
 // raw[i] [windows][labels[i]] into scores[i] (may be the same buffer); a live push keeps member i's filters at maf + base[i], stream after
 // stream, [S][labels[i]][taps + 1].  By value in the launch arguments, as KwsBankOut.
@@ -45,6 +56,13 @@ struct KwsBankMaf {
 };
 int kws_launch_bank_maf_scan(const KwsBankMaf &M, const long long *wbase, int n_rec, hipStream_t stream);
 int kws_launch_bank_maf_live(const KwsBankMaf &M, const long long *meta, int n_act, int k_full, float *maf, hipStream_t stream);
+// The live form for a routed session: routes [S] (device) holds every stream's route, member[i] the bank member behind slot i; an (entry,
+// slot) pair whose stream's route leaves the member out is skipped -- its rows and its filter state are neither read nor written.
+struct KwsBankMafRoute {
+    const uint32_t *routes;
+    int member[KWS_BANK_MAX];
+};
+int kws_launch_bank_maf_live_routed(const KwsBankMaf &M, const KwsBankMafRoute &R, const long long *meta, int n_act, int k_full, float *maf, hipStream_t stream);
 
 // ---- host side (kws_bank.cpp, kws_bank_windows.cpp: the units that include kws_internal.h first) ---------------------------------------------
 #ifdef KWS_INTERNAL
@@ -59,6 +77,11 @@ struct kws_bank {
     size_t feat_cap = 0;
     hipEvent_t ev = nullptr;               // end of the last call's work
     bool ev_used = false;
+    int *d_lists = nullptr;                // a routed call's member lists, one chunk's at a time (uploaded with the call)
+    size_t lists_cap = 0;
+    std::vector<int> h_lists;              // host copy, kept for its capacity
+    hipEvent_t lists_ev = nullptr;         // end of the latest upload of h_lists: it is not rewritten before
+    bool lists_ev_used = false;
     std::mutex mu;
 };
 
@@ -71,8 +94,10 @@ struct BankUse {
     kws_bank *b;
     hipStream_t s;
     // skip_first: the pipeline runners bracket the first member themselves (kws_slide_run and the runners of kws_internal.h)
-    BankUse(kws_bank *b_, hipStream_t s_, bool skip_first) : own(b_->mu), b(b_), s(s_)
+    // held: the bank's own lock, already taken by the caller (a push that reads the session's routes under it)
+    BankUse(kws_bank *b_, hipStream_t s_, bool skip_first, std::unique_lock<std::mutex> &&held = std::unique_lock<std::mutex>()) : own(std::move(held)), b(b_), s(s_)
     {
+        if (!own.owns_lock()) own = std::unique_lock<std::mutex>(b->mu);
         for (kws_handle *h : b->by_addr) locks.emplace_back(h->mu);
         for (size_t k = skip_first ? 1 : 0; k < b->m.size(); ++k) uses.emplace_back(new ScratchUse(b->m[k], s));
     }
@@ -85,12 +110,19 @@ struct BankUse {
 // kws_bank.cpp.  bank_networks: every member's network from the feature matrix feat [B][F] (device); scores[k] + row0 * labels of member k
 // is where its rows go.  bank_window_finish: the finishing step of a chunk of gathered windows for a bank (a kws_slide_finish_fn over a
 // BankWindows): cmvnw (the MFE normalisation) once through the first member, then every member.
-KWS_INTERNAL EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, hipStream_t s);
+// routes: NULL (every member scores every row), or the routes of the B rows (host): member k then runs over the list of rows that name it.
+KWS_INTERNAL EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, hipStream_t s,
+                                            const uint32_t *routes = nullptr);
+// The K lists of n routes, packed: member k's at out[at[k]] as [count, rows ascending]; at[K] = the packed size.  One counting pass.
+KWS_INTERNAL void kws_bank_route_lists(const uint32_t *routes, size_t n, size_t K, std::vector<int> &out, size_t *at);
+// the first route of n that names a member >= K: its index, or n
+KWS_INTERNAL size_t kws_bank_route_check(const uint32_t *routes, size_t n, size_t K);
 KWS_INTERNAL bool bank_wants_nothing(const kws_bank *b, float *const *scores, const float *features);
 struct BankWindows {
     kws_bank *b;
     float *const *scores;          // [K]: where member k's rows go (NULL: skipped)
     float *features;               // the caller's [windows][F], or NULL: the bank's shared matrix, a chunk at a time
+    const uint32_t *routes = nullptr;      // [windows] (host), or NULL: every member scores every window
 };
 KWS_INTERNAL EI_IMPULSE_ERROR bank_window_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s);
 #endif

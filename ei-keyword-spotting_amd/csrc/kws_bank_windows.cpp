@@ -36,6 +36,7 @@ struct BankContinuous {
     int k_full;                            // the live form (maf != NULL): the layout's first window step
     float *maf;
     const long long *base;                 // [K] floats before member k's filters
+    const uint32_t *d_routes = nullptr;    // a routed live push: the session's routes [S] in HBM (NULL: every pair is filtered)
     BankContinuous(kws_bank *b, float *const *scores_, float *const *raw_scores, int k_full_ = 0, float *maf_ = nullptr, const long long *base_ = nullptr)
         : w{ b, raw, nullptr }, scores(scores_), k_full(k_full_), maf(maf_), base(base_)
     {
@@ -48,13 +49,20 @@ static EI_IMPULSE_ERROR bank_continuous_maf(void *ctx, const long long *meta, in
     BankContinuous &c = *(BankContinuous *)ctx;
     kws_bank *b = c.w.b;
     KwsBankMaf M{};
+    KwsBankMafRoute R{};
+    R.routes = c.d_routes;
     for (size_t k = 0; k < b->m.size(); ++k) {
         if (!c.scores[k]) continue;
+        R.member[M.n] = (int)k;
         M.labels[M.n] = (int)b->m[k]->model.labels.size();
         M.raw[M.n] = c.raw[k];
         M.scores[M.n] = c.scores[k];
         M.base[M.n] = c.base ? c.base[k] : 0;
         ++M.n;
+    }
+    if (c.maf && c.d_routes) {
+        KWS_LAUNCH_TRY("routed bank moving-average kernel", kws_launch_bank_maf_live_routed(M, R, meta, n, c.k_full, c.maf, s));
+        return EI_IMPULSE_OK;
     }
     KWS_LAUNCH_TRY("bank moving-average kernel", c.maf ? kws_launch_bank_maf_live(M, meta, n, c.k_full, c.maf, s) : kws_launch_bank_maf_scan(M, meta, n, s));
     return EI_IMPULSE_OK;
@@ -64,8 +72,72 @@ static EI_IMPULSE_ERROR bank_continuous_maf(void *ctx, const long long *meta, in
 static EI_IMPULSE_ERROR bank_ragged_finish(void *ctx, float *f, size_t B, size_t, hipStream_t s)
 {
     BankWindows &c = *(BankWindows *)ctx;
-    return bank_networks(c.b, f, B, c.scores, 0, s);
+    return bank_networks(c.b, f, B, c.scores, 0, s, c.routes);
 }
+
+// A routed push: the routes of the push's windows, in row order -- a window's route is its stream's.  The runners have every entry's
+// window count on the host before they call a hook (n_windows), so the table is built at the first chunk, before anything of the
+// networks is enqueued; bank_window_finish then hands each chunk its part.
+struct BankPushRoutes {
+    const std::vector<uint32_t> *session;  // [S]
+    const size_t *streams, *n_windows;     // the push's entries (the caller's arrays)
+    size_t n;
+    std::vector<uint32_t> windows;
+    bool built = false;
+    const uint32_t *build()
+    {
+        if (!built) {
+            for (size_t i = 0; i < n; ++i) windows.insert(windows.end(), n_windows[i], (*session)[streams[i]]);
+            built = true;
+        }
+        return windows.data();
+    }
+};
+struct BankRoutedWindows {
+    BankWindows w;                         // (first: bank_window_finish reads it)
+    BankPushRoutes r;
+};
+static EI_IMPULSE_ERROR bank_routed_window_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
+{
+    BankRoutedWindows &c = *(BankRoutedWindows *)ctx;
+    if (n) c.w.routes = c.r.build();
+    return bank_window_finish(&c.w, win, n, g0, s);
+}
+struct BankRoutedContinuous {
+    BankContinuous c;                      // (first: bank_window_finish and bank_continuous_maf read it)
+    BankPushRoutes r;
+    BankRoutedContinuous(kws_bank *b, float *const *scores, float *const *raw_scores, int k_full, float *maf, const long long *base) : c(b, scores, raw_scores, k_full, maf, base) {}
+};
+static EI_IMPULSE_ERROR bank_routed_continuous_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
+{
+    BankRoutedContinuous &c = *(BankRoutedContinuous *)ctx;
+    if (n) c.c.w.routes = c.r.build();
+    return bank_window_finish(&c.c, win, n, g0, s);
+}
+
+// the session's routes: every stream to every member until kws_bank_*_route says otherwise
+struct BankRoutes {
+    std::vector<uint32_t> route;           // [S]
+    uint32_t every = 0;
+    bool routed = false;                   // some stream's route is not `every`
+    void open(size_t S, size_t K) { every = (1u << K) - 1u; route.assign(S, every); }
+    // the checks of kws_bank_*_route; the first offending entry is named
+    EI_IMPULSE_ERROR check(const size_t *streams, size_t n, const uint32_t *routes, size_t K) const
+    {
+        if (n > 0 && (!streams || !routes)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+        for (size_t i = 0; i < n; ++i) {
+            if (streams[i] >= route.size()) return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: stream %zu of %zu", i, streams[i], route.size());
+            if (routes[i] >> K) return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: route 0x%x names a member at or above the bank's %zu", i, routes[i], K);
+        }
+        return EI_IMPULSE_OK;
+    }
+    void set(const size_t *streams, size_t n, const uint32_t *routes)
+    {
+        for (size_t i = 0; i < n; ++i) route[streams[i]] = routes[i];
+        routed = false;
+        for (uint32_t r : route) routed = routed || r != every;
+    }
+};
 
 // (the sessions: the bank, the first member's session -- carry, retained rows, mirrors, per-push scratch: ONE copy -- and what is per member)
 struct kws_bank_live {
@@ -74,10 +146,14 @@ struct kws_bank_live {
     ScanLayout L;
     float *maf = nullptr;                  // state in HBM: member k's [S][labels_k][taps + 1] at base[k]
     std::vector<long long> base;
+    BankRoutes routes;
+    uint32_t *d_routes = nullptr;          // the routes in HBM, where the routed moving average reads them (allocated by the first kws_bank_live_route)
+    std::vector<char> pushed;              // [S]: the stream has been pushed to since its start (create, reset or finish): its route is fixed
 };
 struct kws_bank_slide_live {
     kws_bank *b = nullptr;
     kws_slide_live *core = nullptr;
+    BankRoutes routes;
 };
 
 // the end of the bank's latest call, this session's last push included (BankUse records it), before a session's memory goes
@@ -111,6 +187,8 @@ EI_IMPULSE_ERROR kws_bank_live_create(kws_bank *b, size_t S, size_t slice_sample
     EI_IMPULSE_ERROR e = kws_live_open(b->m[0], S, slice_samples, 0, &lv->core);
     if (e) return e;
     (void)scan_layout(b->m[0], slice_samples, &lv->L);             // (kws_live_open has accepted the slicing)
+    lv->routes.open(S, b->m.size());
+    lv->pushed.assign(S, 0);
     long long floats = 0;
     for (const kws_handle *h : b->m) {
         lv->base.push_back(floats);
@@ -134,6 +212,7 @@ void kws_bank_live_destroy(kws_bank_live *lv)
         bank_wait(lv->b);
         kws_live_destroy(lv->core);
         if (lv->maf) (void)hipFree(lv->maf);
+        if (lv->d_routes) (void)hipFree(lv->d_routes);
     }
     delete lv;
 }
@@ -142,7 +221,36 @@ EI_IMPULSE_ERROR kws_bank_live_reset(kws_bank_live *lv, const size_t *streams, s
 {
     if (!lv) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     std::lock_guard<std::mutex> lk(lv->b->mu);
-    return kws_live_reset(lv->core, streams, n);
+    const EI_IMPULSE_ERROR e = kws_live_reset(lv->core, streams, n);
+    if (e) return e;
+    // (routes stay; the streams are in their reset state again, where a route may change)
+    if (!streams) std::fill(lv->pushed.begin(), lv->pushed.end(), 0);
+    else for (size_t i = 0; i < n; ++i) lv->pushed[streams[i]] = 0;
+    return EI_IMPULSE_OK;
+}
+
+EI_IMPULSE_ERROR kws_bank_live_route(kws_bank_live *lv, const size_t *streams, size_t n, const uint32_t *routes)
+{
+    if (!lv) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    kws_bank *b = lv->b;
+    std::lock_guard<std::mutex> lk(b->mu);
+    EI_IMPULSE_ERROR e = lv->routes.check(streams, n, routes, b->m.size());
+    if (e) return e;
+    // a member's moving-average filter must see every window of a stream it serves: no change once the stream has been pushed to
+    for (size_t i = 0; i < n; ++i)
+        if (lv->pushed[streams[i]])
+            return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: stream %zu has been pushed to; its route changes only after a reset", i, streams[i]);
+    if (n == 0) return EI_IMPULSE_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t S = lv->routes.route.size();
+    if (!lv->d_routes) HIP_TRY(hipMalloc((void **)&lv->d_routes, S * sizeof(uint32_t)));
+    // (a push enqueued earlier may still read the old table: the bank's event marks the end of its latest call)
+    bank_wait(b);
+    BankRoutes next = lv->routes;
+    next.set(streams, n, routes);
+    HIP_TRY(hipMemcpy(lv->d_routes, next.route.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice));
+    lv->routes = next;
+    return EI_IMPULSE_OK;
 }
 
 EI_IMPULSE_ERROR kws_bank_live_window_count(const kws_bank_live *lv, size_t stream, size_t n_new, int finish, size_t *n_windows)
@@ -158,16 +266,36 @@ EI_IMPULSE_ERROR kws_bank_live_push_device(kws_bank_live *lv, size_t n, const si
 {
     if (!lv) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     kws_bank *b = lv->b;
-    // every member's filter must see every window: no member is skipped in a push
+    // every member's filter must see every window of the streams it serves: a member is skipped only where no stream named in the push
+    // routes to it (a session that was never routed: no member is skipped)
+    std::unique_lock<std::mutex> own(b->mu);
+    const bool routed = lv->routes.routed;
+    uint32_t wanted = routed ? 0 : lv->routes.every;
+    for (size_t i = 0; routed && streams && i < n; ++i)
+        if (streams[i] < lv->routes.route.size()) wanted |= lv->routes.route[streams[i]];
     for (size_t k = 0; scores && k < b->m.size(); ++k)
-        if (!scores[k]) return fail(KWS_ERROR_BAD_ARGUMENT, "scores[%zu] is NULL: a live push skips no member", k);
+        if (!scores[k] && ((wanted >> k) & 1u))
+            return fail(KWS_ERROR_BAD_ARGUMENT, routed ? "scores[%zu] is NULL: a stream named in this push routes to that member" : "scores[%zu] is NULL: a live push skips no member", k);
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
-    BankUse use(b, s, true);
+    BankUse use(b, s, true, std::move(own));
     float *const none[KWS_BANK_MAX] = { nullptr };
-    BankContinuous ctx(b, scores ? scores : none, raw_scores, (int)lv->L.k_full, lv->maf, lv->base.data());
-    return kws_live_run(lv->core, n, streams, pcm, offsets, lengths, finish, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish,
-                        bank_continuous_maf, &ctx, s);
+    EI_IMPULSE_ERROR e;
+    if (!routed) {
+        BankContinuous ctx(b, scores ? scores : none, raw_scores, (int)lv->L.k_full, lv->maf, lv->base.data());
+        e = kws_live_run(lv->core, n, streams, pcm, offsets, lengths, finish, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish,
+                         bank_continuous_maf, &ctx, s);
+    } else {
+        BankRoutedContinuous ctx(b, scores ? scores : none, raw_scores, (int)lv->L.k_full, lv->maf, lv->base.data());
+        ctx.c.d_routes = lv->d_routes;
+        ctx.r = BankPushRoutes{ &lv->routes.route, streams, n_windows, n, {}, false };
+        e = kws_live_run(lv->core, n, streams, pcm, offsets, lengths, finish, scores, n_windows, bank_max_labels(b), 0, 0, bank_routed_continuous_finish,
+                         bank_continuous_maf, &ctx, s);
+    }
+    if (e) return e;
+    // (a stream the push finished starts over: its route may change again)
+    for (size_t i = 0; i < n; ++i) lv->pushed[streams[i]] = !(finish && finish[i]);
+    return EI_IMPULSE_OK;
 }
 
 EI_IMPULSE_ERROR kws_bank_slide_live_create(kws_bank *b, size_t S, size_t hop_samples, int flags, kws_bank_slide_live **out)
@@ -178,6 +306,7 @@ EI_IMPULSE_ERROR kws_bank_slide_live_create(kws_bank *b, size_t S, size_t hop_sa
     sl->b = b;
     EI_IMPULSE_ERROR e = kws_slide_live_create(b->m[0], S, hop_samples, flags, &sl->core);
     if (e) return e;
+    sl->routes.open(S, b->m.size());
     *out = sl.release();
     return EI_IMPULSE_OK;
 }
@@ -202,6 +331,16 @@ EI_IMPULSE_ERROR kws_bank_slide_live_reset(kws_bank_slide_live *sl, const size_t
     return kws_slide_live_reset(sl->core, streams, n);
 }
 
+EI_IMPULSE_ERROR kws_bank_slide_live_route(kws_bank_slide_live *sl, const size_t *streams, size_t n, const uint32_t *routes)
+{
+    if (!sl) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lk(sl->b->mu);
+    const EI_IMPULSE_ERROR e = sl->routes.check(streams, n, routes, sl->b->m.size());
+    if (e) return e;
+    sl->routes.set(streams, n, routes);          // (no per-member state: a route may change between any two pushes)
+    return EI_IMPULSE_OK;
+}
+
 EI_IMPULSE_ERROR kws_bank_slide_live_window_count(const kws_bank_slide_live *sl, size_t stream, size_t n_new, size_t *n_windows)
 {
     if (!sl) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
@@ -219,16 +358,30 @@ EI_IMPULSE_ERROR kws_bank_slide_live_push_device(kws_bank_slide_live *sl, size_t
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     BankUse use(b, s, true);
-    BankWindows ctx{ b, scores, features };
-    return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish, &ctx, s);
+    if (!sl->routes.routed) {
+        BankWindows ctx{ b, scores, features };
+        return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish, &ctx, s);
+    }
+    BankRoutedWindows ctx{ { b, scores, features }, { &sl->routes.route, streams, n_windows, n, {}, false } };
+    return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores, n_windows, bank_max_labels(b), 0, 0, bank_routed_window_finish, &ctx, s);
 }
 
 EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B,
                                                        float *const *scores, float *features, void *stream)
 {
+    return kws_bank_run_classifier_ragged_routed_device(b, pcm, offsets, lengths, B, nullptr, scores, features, stream);
+}
+
+EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B,
+                                                              const uint32_t *routes, float *const *scores, float *features, void *stream)
+{
     if (!b || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
     if (B >= ((size_t)1 << 31)) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    if (routes) {
+        const size_t bad = kws_bank_route_check(routes, B, b->m.size());
+        if (bad < B) return fail(KWS_ERROR_BAD_ARGUMENT, "clip %zu: route 0x%x names a member at or above the bank's %zu", bad, routes[bad], b->m.size());
+    }
     if (B == 0) return EI_IMPULSE_OK;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
@@ -239,7 +392,7 @@ EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_device(kws_bank *b, const int16_
         if (e) return e;
         f = b->feat;
     }
-    BankWindows ctx{ b, scores, features };
+    BankWindows ctx{ b, scores, features, routes };
     return kws_ragged_run(b->m[0], pcm, offsets, lengths, B, f, nullptr, 0, 0, bank_ragged_finish, &ctx, s);
 }
 

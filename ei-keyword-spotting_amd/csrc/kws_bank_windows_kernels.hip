@@ -4,6 +4,7 @@
 //     LIVE = false   the scan form: a fresh filter per recording over its windows in order -- kws_scan_maf_kernel for every member
 //     LIVE = true    the live form: the filter resumed from HBM and stored back, not stored for a stream the push finishes --
 //                    kws_live_maf_kernel for every member, with its w0 / k_full rule and its index as the window count mod taps
+//   kws_bank_maf_routed_kernel  the live form for a routed session: (entry, member) pairs the entry's route leaves out are skipped
 // The members' label counts differ, so a thread finds its member by walking the by-value table (at most KWS_BANK_MAX entries); member i's
 // rows are [windows][labels[i]] in its own buffers.  The arithmetic is the two existing kernels', operation for operation and in their
 // order (rs -= buf[idx]; rs += v; buf[idx] = v; out = rs / (float)taps), so a member's rows are the bits its own call writes.
@@ -59,6 +60,49 @@ __global__ __launch_bounds__(64) void kws_bank_maf_kernel(KwsBankMaf M, KwsLiveM
     st[KWS_BANK_TAPS] = rs;
 }
 
+// The live form for a routed session, a sibling: R.routes [S] holds every stream's route and R.member[i] the bank member behind slot i; a pair
+// the entry's route leaves out ends before it reads a row or its filter.  The rest is kws_bank_maf_kernel<true>, operation for operation.
+__global__ __launch_bounds__(64) void kws_bank_maf_routed_kernel(KwsBankMaf M, KwsBankMafRoute R, KwsLiveMeta m, int n, int total, int k_full, float *__restrict__ maf)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)n * total) return;
+    const int a = (int)(t / total);
+    int l = (int)(t - (long long)a * total), i = 0;
+    while (i < M.n - 1 && l >= M.labels[i]) { l -= M.labels[i]; ++i; }
+    if (!((R.routes[m.stream[a]] >> R.member[i]) & 1u)) return;
+    const int labels = M.labels[i];
+    const float *raw = M.raw[i];
+    float *scores = M.scores[i];
+    const long long g0 = m.wbase[a], g1 = m.wbase[a + 1];
+    long long w0 = 0;
+    float *st = nullptr;
+    bool store = false;
+    {
+        if (g0 == g1) return;
+        w0 = m.k0[a] > k_full ? m.k0[a] - k_full : 0;
+        st = maf + M.base[i] + ((size_t)m.stream[a] * labels + l) * (KWS_BANK_TAPS + 1);
+        store = !m.fin[a];
+    }
+    float buf[KWS_BANK_TAPS];
+    float rs = 0.0f;
+#pragma unroll
+    for (int j = 0; j < KWS_BANK_TAPS; ++j) buf[j] = w0 ? st[j] : 0.0f;
+    if (w0) rs = st[KWS_BANK_TAPS];
+    int idx = (int)(w0 % KWS_BANK_TAPS);
+    for (long long g = g0; g < g1; ++g) {
+        const float v = raw[(size_t)g * labels + l];
+        rs -= buf[idx];
+        rs += v;
+        buf[idx] = v;
+        scores[(size_t)g * labels + l] = rs / (float)KWS_BANK_TAPS;
+        if (++idx >= KWS_BANK_TAPS) idx = 0;
+    }
+    if (!store) return;
+#pragma unroll
+    for (int j = 0; j < KWS_BANK_TAPS; ++j) st[j] = buf[j];
+    st[KWS_BANK_TAPS] = rs;
+}
+
 static int bank_maf_total(const KwsBankMaf &M)
 {
     int total = 0;
@@ -85,5 +129,15 @@ int kws_launch_bank_maf_live(const KwsBankMaf &M, const long long *meta, int n_a
     const long long n = (long long)n_act * total;
     if (n <= 0) return 0;
     hipLaunchKernelGGL(kws_bank_maf_kernel<true>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, M, live_meta(meta, n_act), n_act, total, k_full, maf);
+    return (int)hipGetLastError();
+}
+
+int kws_launch_bank_maf_live_routed(const KwsBankMaf &M, const KwsBankMafRoute &R, const long long *meta, int n_act, int k_full, float *maf, hipStream_t stream)
+{
+    (void)hipGetLastError();
+    const int total = bank_maf_total(M);
+    const long long n = (long long)n_act * total;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(kws_bank_maf_routed_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, M, R, live_meta(meta, n_act), n_act, total, k_full, maf);
     return (int)hipGetLastError();
 }

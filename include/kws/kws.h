@@ -629,6 +629,48 @@ EI_IMPULSE_ERROR kws_bank_slide_live_push_device(kws_bank_slide_live *sl, size_t
 EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B,
                                                        float *const *scores, float *features, void *stream);
 
+/* ---- routed banks: each clip or stream scored only by the members it names ------------------------------------------------------------
+ * A bank call runs every member on every row.  A routed call runs the shared front end once and, for each row, only the members its
+ * route names: requests or live streams of many tenants whose models share one DSP block, each scored by its own model and by no other.
+ * Route.  A uint32_t per clip, or per stream of a live session: bit k set = member k of the bank, in bank order, scores it.  Routes are
+ * HOST data, like `offsets` / `lengths` of the ragged call.  A bit at or above kws_bank_size(b) is KWS_ERROR_BAD_ARGUMENT, kws_last_error
+ * names the first offending index and its mask, nothing is enqueued.  A zero mask is legal: the front end still runs for that clip and
+ * `features` still gets its row.  routes == NULL means every member: the call then IS the unrouted call (its launches, its bits); so is a
+ * call whose routes all name every member.
+ * Output.  The layout is the unrouted call's: member k's buffer is [clips or windows of the call][labels_k], rows in the call's order.
+ * Only the rows of routed (row, member) pairs are written; every other row of every score buffer -- raw_scores and the moving average's
+ * output included -- is left untouched, bit for bit, and the filter state of an unrouted (stream, member) pair is neither read nor
+ * written.  `features` holds every row.
+ * Parity contract.  A routed (row, member) pair's scores are the bits of the unrouted bank call's and so of that member's own entry point
+ * in KWS_MODE_EXACT (int8 bit-exact with the reference, float32 scores within 1e-6); `features` is the unrouted call's, bit for bit.
+ * Mode.  Routed calls run the exact launches only, as bank calls do: no mode, fast counter or logits tap is read or written.
+ * Launches.  The front end once.  The int8 members of the two-block matrix-core shape share one launch per activation-row width that has a
+ * member with a non-empty list (each wave walks its member's list; the grid is sized by the longest list); the other members run their own
+ * network launches over their lists; a member nobody names launches nothing.  The K lists are built on the host in one counting pass and
+ * uploaded with the call: 4 x (K + routed pairs) bytes of bank-owned device memory, grown on demand (growing synchronises the device).
+ * An int8 member outside the matrix-core shape still takes its input tensor from its own batch scratch, grown to the call's rows.
+ *   kws_bank_run_classifier_routed_device         kws_bank_run_classifier_batch_device with routes [B]
+ *   kws_bank_run_classifier_ragged_routed_device  kws_bank_run_classifier_ragged_device with routes [B]
+ *   kws_bank_live_route        sets the routes of n streams (streams, routes: HOST arrays of n entries) of a continuous-mode session.  A
+ *                     fresh session routes every stream to every member, and a session that never calls this behaves exactly as
+ *                     before.  A member's moving-average filter must see every window of a stream it serves, so a stream's route may
+ *                     be set only while the stream is in its start state: after create, kws_bank_live_reset or the push that finished
+ *                     it, before anything else was pushed to it; otherwise KWS_ERROR_BAD_ARGUMENT and nothing changes (also for a
+ *                     stream index out of range or a bad mask: the first offending entry is named).  kws_bank_live_reset keeps
+ *                     routes.  The call waits for the bank's enqueued work.  In kws_bank_live_push_device, scores[k] (and
+ *                     raw_scores[k]) may be NULL exactly when no stream named in that push routes to member k; any other NULL is
+ *                     KWS_ERROR_BAD_ARGUMENT with no state change.  The moving average stays ONE launch whatever K.
+ *   kws_bank_slide_live_route  the same for a live one-shot session; there is no per-member state, so a route may change between any two
+ *                     pushes.  kws_bank_slide_live_reset keeps routes.
+ * Not routed in this version: recording scans and slides, cepstra-in calls, the host-buffer and SDK forms. */
+EI_IMPULSE_ERROR kws_bank_run_classifier_routed_device(kws_bank *b, const int16_t *pcm, size_t B, const uint32_t *routes,
+                                                       float *const *scores, float *features, void *stream);
+EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths,
+                                                              size_t B, const uint32_t *routes, float *const *scores, float *features,
+                                                              void *stream);
+EI_IMPULSE_ERROR kws_bank_live_route(kws_bank_live *lv, const size_t *streams, size_t n, const uint32_t *routes);
+EI_IMPULSE_ERROR kws_bank_slide_live_route(kws_bank_slide_live *sl, const size_t *streams, size_t n, const uint32_t *routes);
+
 /* ---- multi-GPU: clips shard contiguously over the GPUs of one node (rank r owns clips [r*B, (r+1)*B)), tables are
  * replicated, nothing is exchanged inside the pipeline; the one collective is the all-gather of the per-clip scores over xGMI.
  * It goes through RCCL's C API (librccl is opened on first use: single-GPU applications do not need it).  One process per GPU:
