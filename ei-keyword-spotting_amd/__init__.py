@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "kws_bank_slide_live_create", "kws_bank_slide_live_destroy", "kws_bank_slide_live_path", "kws_bank_slide_live_reset",
     "kws_bank_slide_live_window_count", "kws_bank_slide_live_push_device",
     "kws_bank_run_classifier_routed_device", "kws_bank_run_classifier_ragged_routed_device", "kws_bank_live_route", "kws_bank_slide_live_route",
+    "kws_bank_scan_recordings_routed_device", "kws_bank_slide_recordings_routed_device", "kws_bank_cmvn_inference_routed_device",
     "kws_window_frame_count", "kws_run_classifier_ragged_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_slide_live_create", "kws_slide_live_destroy", "kws_slide_live_path", "kws_slide_live_reset", "kws_slide_live_window_count",
@@ -243,6 +244,10 @@ def lib():
             L.kws_bank_run_classifier_ragged_routed_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp]
             L.kws_bank_live_route.argtypes = [vp, vp, sz, vp]
             L.kws_bank_slide_live_route.argtypes = [vp, vp, sz, vp]
+        if hasattr(L, "kws_bank_scan_recordings_routed_device"):
+            L.kws_bank_scan_recordings_routed_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
+            L.kws_bank_slide_recordings_routed_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, i32, vp, vp, vp]
+            L.kws_bank_cmvn_inference_routed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
         L.kws_device_malloc.argtypes = [C.POINTER(vp), sz]
         L.kws_device_free.argtypes = [vp]
         L.kws_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -541,24 +546,39 @@ class Bank:
         member): only the rows of routed (clip, member) pairs are written, features hold every row"""
         _check(self.L.kws_bank_run_classifier_routed_device(self.b, pcm_ptr, B, _routes(routes, B), self._scores(scores_ptrs), features_ptr, stream))
 
-    def cmvn_inference_batch_device(self, mfcc_ptr, B, scores_ptrs, features_ptr=None, stream=None):
-        _check(self.L.kws_bank_cmvn_inference_batch_device(self.b, mfcc_ptr, B, self._scores(scores_ptrs), features_ptr, stream))
+    def cmvn_inference_batch_device(self, mfcc_ptr, B, scores_ptrs, features_ptr=None, stream=None, routes=None):
+        """Model.cmvn_inference_batch_device for every member.  routes: a mask per cepstral matrix as in run_classifier_routed_device (None:
+        every member scores every row)"""
+        if routes is None:
+            _check(self.L.kws_bank_cmvn_inference_batch_device(self.b, mfcc_ptr, B, self._scores(scores_ptrs), features_ptr, stream))
+            return
+        _check(self.L.kws_bank_cmvn_inference_routed_device(self.b, mfcc_ptr, B, _routes(routes, B), self._scores(scores_ptrs), features_ptr, stream))
 
-    def slide_recordings_device(self, pcm_ptr, offsets, lengths, hop_samples, scores_ptrs, features_ptr=None, flags=SLIDE_AUTO, stream=None):
-        """Model.slide_recordings_device for every member: window counts and slide_plan are any member's"""
+    def slide_recordings_device(self, pcm_ptr, offsets, lengths, hop_samples, scores_ptrs, features_ptr=None, flags=SLIDE_AUTO, stream=None, routes=None):
+        """Model.slide_recordings_device for every member: window counts and slide_plan are any member's.  routes: a mask per RECORDING (bit k
+        set = member k scores its windows; None: every member scores every window); features hold every window"""
         off = np.ascontiguousarray(offsets, np.uint64)
         ln = np.ascontiguousarray(lengths, np.uint64)
         assert off.shape == ln.shape and off.ndim == 1
+        if routes is not None:
+            _check(self.L.kws_bank_slide_recordings_routed_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, _routes(routes, off.size), hop_samples, flags,
+                                                                  self._scores(scores_ptrs), features_ptr, stream))
+            return
         _check(self.L.kws_bank_slide_recordings_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, hop_samples, flags, self._scores(scores_ptrs),
                                                        features_ptr, stream))
 
-    def scan_recordings_device(self, pcm_ptr, offsets, lengths, scores_ptrs, raw_scores_ptrs=None, slice_samples=None, stream=None):
+    def scan_recordings_device(self, pcm_ptr, offsets, lengths, scores_ptrs, raw_scores_ptrs=None, slice_samples=None, stream=None, routes=None):
         """Model.scan_recordings_device for every member: window counts are any member's.  raw_scores_ptrs: one device pointer (or None) per
-        member, or None for no raw scores at all."""
+        member, or None for no raw scores at all.  routes: a mask per RECORDING (bit k set = member k scores its windows; None: every member
+        scores every window): only the rows of routed (window, member) pairs are written."""
         off = np.ascontiguousarray(offsets, np.uint64)
         ln = np.ascontiguousarray(lengths, np.uint64)
         assert off.shape == ln.shape and off.ndim == 1
         raw = None if raw_scores_ptrs is None else self._scores(raw_scores_ptrs)
+        if routes is not None:
+            _check(self.L.kws_bank_scan_recordings_routed_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, _routes(routes, off.size),
+                                                                 slice_samples or self._models[0].clip_samples // 4, self._scores(scores_ptrs), raw, stream))
+            return
         _check(self.L.kws_bank_scan_recordings_device(self.b, pcm_ptr, _p(off), _p(ln), off.size, slice_samples or self._models[0].clip_samples // 4,
                                                       self._scores(scores_ptrs), raw, stream))
 

@@ -66,6 +66,12 @@ size_t kws_bank_route_check(const uint32_t *routes, size_t n, size_t K)
     return n;
 }
 
+void kws_bank_window_routes(const uint32_t *route, const size_t *index, const size_t *n_windows, size_t n, std::vector<uint32_t> &out)
+{
+    out.clear();
+    for (size_t i = 0; i < n; ++i) out.insert(out.end(), n_windows[i], route[index ? index[i] : i]);
+}
+
 // The routed form of bank_networks: member k runs over the rows whose route names it.  The lists travel with the call (one upload, behind
 // the stream's earlier work: a chunk's lists replace the previous chunk's only after its launches); a member with an empty list, or without
 // a score buffer, launches nothing.
@@ -238,6 +244,8 @@ void kws_bank_destroy(kws_bank *b)
     if (b->feat) (void)hipFree(b->feat);
     if (b->d_lists) (void)hipFree(b->d_lists);
     if (b->lists_ev) (void)hipEventDestroy(b->lists_ev);
+    if (b->d_routes) (void)hipFree(b->d_routes);
+    if (b->routes_ev) (void)hipEventDestroy(b->routes_ev);
     delete b;
 }
 
@@ -290,9 +298,16 @@ EI_IMPULSE_ERROR kws_bank_run_classifier_routed_device(kws_bank *b, const int16_
 
 EI_IMPULSE_ERROR kws_bank_cmvn_inference_batch_device(kws_bank *b, const float *mfcc, size_t B, float *const *scores, float *features, void *stream)
 {
+    return kws_bank_cmvn_inference_routed_device(b, mfcc, B, nullptr, scores, features, stream);
+}
+
+EI_IMPULSE_ERROR kws_bank_cmvn_inference_routed_device(kws_bank *b, const float *mfcc, size_t B, const uint32_t *routes, float *const *scores, float *features, void *stream)
+{
     if (!b || !mfcc || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
     if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    const size_t bad = routes ? kws_bank_route_check(routes, B, b->m.size()) : B;
+    if (bad < B) return fail(KWS_ERROR_BAD_ARGUMENT, "row %zu: route 0x%x names a member at or above the bank's %zu", bad, routes[bad], b->m.size());
     if (B == 0) return EI_IMPULSE_OK;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
@@ -306,7 +321,7 @@ EI_IMPULSE_ERROR kws_bank_cmvn_inference_batch_device(kws_bank *b, const float *
     }
     if ((e = ensure_scratch(h0, B))) return e;        // (a general-shape int8 first member: cmvn_nn_device writes its int8 tensor there)
     if ((e = cmvn_nn_device(h0, mfcc, B, f, nullptr, nullptr, nullptr, nullptr, nullptr, s))) return e;
-    return bank_networks(b, f, B, scores, 0, s);
+    return bank_networks(b, f, B, scores, 0, s, routes);
 }
 
 EI_IMPULSE_ERROR kws_bank_slide_recordings_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,

@@ -63,6 +63,9 @@ struct KwsBankMafRoute {
     int member[KWS_BANK_MAX];
 };
 int kws_launch_bank_maf_live_routed(const KwsBankMaf &M, const KwsBankMafRoute &R, const long long *meta, int n_act, int k_full, float *maf, hipStream_t stream);
+// The scan form for a routed call: R.routes [n_rec] (device) holds the route of every recording that has windows, in the order of wbase; a
+// (recording, slot) pair whose route leaves the member out is skipped -- its rows are neither read nor written.
+int kws_launch_bank_maf_scan_routed(const KwsBankMaf &M, const KwsBankMafRoute &R, const long long *wbase, int n_rec, hipStream_t stream);
 
 // ---- host side (kws_bank.cpp, kws_bank_windows.cpp: the units that include kws_internal.h first) ---------------------------------------------
 #ifdef KWS_INTERNAL
@@ -82,6 +85,11 @@ struct kws_bank {
     std::vector<int> h_lists;              // host copy, kept for its capacity
     hipEvent_t lists_ev = nullptr;         // end of the latest upload of h_lists: it is not rewritten before
     bool lists_ev_used = false;
+    uint32_t *d_routes = nullptr;          // a routed scan's routes, one per recording that has windows (uploaded with the call)
+    size_t routes_cap = 0;
+    std::vector<uint32_t> h_routes;        // host copy, kept until the upload has ended
+    hipEvent_t routes_ev = nullptr;        // end of the latest upload of h_routes: it is not rewritten before
+    bool routes_ev_used = false;
     std::mutex mu;
 };
 
@@ -117,6 +125,9 @@ KWS_INTERNAL EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size
 KWS_INTERNAL void kws_bank_route_lists(const uint32_t *routes, size_t n, size_t K, std::vector<int> &out, size_t *at);
 // the first route of n that names a member >= K: its index, or n
 KWS_INTERNAL size_t kws_bank_route_check(const uint32_t *routes, size_t n, size_t K);
+// The routes of a call's windows, in row order: entry i has n_windows[i] windows, each with the route of its entry -- route[index[i]] (a
+// live push: the session's routes by stream), or route[i] where index is NULL (a recording call: the call's routes by recording).
+KWS_INTERNAL void kws_bank_window_routes(const uint32_t *route, const size_t *index, const size_t *n_windows, size_t n, std::vector<uint32_t> &out);
 KWS_INTERNAL bool bank_wants_nothing(const kws_bank *b, float *const *scores, const float *features);
 struct BankWindows {
     kws_bank *b;

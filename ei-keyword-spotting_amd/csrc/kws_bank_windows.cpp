@@ -1,6 +1,7 @@
 // kws_bank_windows.cpp -- the bank forms of the window pipelines (contract in include/kws/kws.h): recording scans and live streams in
 // continuous mode, live one-shot windows and clips of their own lengths for K models that share one DSP block.
-//   kws_bank_scan_recordings_device         kws_scan_run      (kws_scan.cpp)
+//   kws_bank_scan_recordings_device         kws_scan_run      (kws_scan.cpp); _routed_: a route per recording
+//   kws_bank_slide_recordings_routed_device kws_slide_run     (kws_slide.cpp) with a route per recording (the unrouted form: kws_bank.cpp)
 //   kws_bank_live_*                         kws_live_run      (kws_live.cpp), on a session of the first member opened without filter state
 //   kws_bank_slide_live_*                   kws_slide_live_run (kws_slide_live.cpp), on a session of the first member
 //   kws_bank_run_classifier_ragged_device   kws_ragged_run    (kws_ragged.cpp) with the network skipped
@@ -37,6 +38,8 @@ struct BankContinuous {
     float *maf;
     const long long *base;                 // [K] floats before member k's filters
     const uint32_t *d_routes = nullptr;    // a routed live push: the session's routes [S] in HBM (NULL: every pair is filtered)
+    const std::vector<uint32_t> *scan_routes = nullptr;    // a routed scan: the routes of the recordings that have windows, in their order (host)
+    uint32_t wanted = ~0u;                 // a routed scan: the members some recording with windows names; the others get no filter slot
     BankContinuous(kws_bank *b, float *const *scores_, float *const *raw_scores, int k_full_ = 0, float *maf_ = nullptr, const long long *base_ = nullptr)
         : w{ b, raw, nullptr }, scores(scores_), k_full(k_full_), maf(maf_), base(base_)
     {
@@ -52,13 +55,30 @@ static EI_IMPULSE_ERROR bank_continuous_maf(void *ctx, const long long *meta, in
     KwsBankMafRoute R{};
     R.routes = c.d_routes;
     for (size_t k = 0; k < b->m.size(); ++k) {
-        if (!c.scores[k]) continue;
+        if (!c.scores[k] || !((c.wanted >> k) & 1u)) continue;
         R.member[M.n] = (int)k;
         M.labels[M.n] = (int)b->m[k]->model.labels.size();
         M.raw[M.n] = c.raw[k];
         M.scores[M.n] = c.scores[k];
         M.base[M.n] = c.base ? c.base[k] : 0;
         ++M.n;
+    }
+    if (c.scan_routes) {
+        // the routes travel with the call, behind the stream's earlier work (the host copy is the bank's: it outlives the upload)
+        if (M.n == 0) return EI_IMPULSE_OK;
+        if ((size_t)n != c.scan_routes->size()) return fail(KWS_ERROR_BAD_ARGUMENT, "routed scan: %d recordings with windows, %zu routes", n, c.scan_routes->size());
+        if (b->routes_ev_used) HIP_TRY(hipEventSynchronize(b->routes_ev));
+        b->routes_ev_used = false;
+        b->h_routes = *c.scan_routes;
+        EI_IMPULSE_ERROR e = grow_buffer(&b->d_routes, &b->routes_cap, (size_t)n);
+        if (e) return e;
+        HIP_TRY(hipMemcpyAsync(b->d_routes, b->h_routes.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (!b->routes_ev) HIP_TRY(hipEventCreateWithFlags(&b->routes_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(b->routes_ev, s));
+        b->routes_ev_used = true;
+        R.routes = b->d_routes;
+        KWS_LAUNCH_TRY("routed bank moving-average kernel", kws_launch_bank_maf_scan_routed(M, R, meta, n, s));
+        return EI_IMPULSE_OK;
     }
     if (c.maf && c.d_routes) {
         KWS_LAUNCH_TRY("routed bank moving-average kernel", kws_launch_bank_maf_live_routed(M, R, meta, n, c.k_full, c.maf, s));
@@ -75,19 +95,20 @@ static EI_IMPULSE_ERROR bank_ragged_finish(void *ctx, float *f, size_t B, size_t
     return bank_networks(c.b, f, B, c.scores, 0, s, c.routes);
 }
 
-// A routed push: the routes of the push's windows, in row order -- a window's route is its stream's.  The runners have every entry's
-// window count on the host before they call a hook (n_windows), so the table is built at the first chunk, before anything of the
-// networks is enqueued; bank_window_finish then hands each chunk its part.
-struct BankPushRoutes {
-    const std::vector<uint32_t> *session;  // [S]
-    const size_t *streams, *n_windows;     // the push's entries (the caller's arrays)
+// A routed push or recording call: the routes of its windows, in row order -- a window's route is its stream's (a push: the session's
+// routes, by streams[i]) or its recording's (a recording call: the call's routes, index == NULL).  Every entry's window count is on the host
+// before a hook is called (a push: the runner has filled the caller's n_windows; a recording call: the pipeline's count per recording), so
+// the table is built at the first chunk, before anything of the networks is enqueued; bank_window_finish then hands each chunk its part.
+struct BankWindowRoutes {
+    const uint32_t *route;                 // [S] or [R]
+    const size_t *index, *n_windows;       // the entries' streams (NULL: entry i is recording i) and window counts
     size_t n;
     std::vector<uint32_t> windows;
     bool built = false;
     const uint32_t *build()
     {
         if (!built) {
-            for (size_t i = 0; i < n; ++i) windows.insert(windows.end(), n_windows[i], (*session)[streams[i]]);
+            kws_bank_window_routes(route, index, n_windows, n, windows);
             built = true;
         }
         return windows.data();
@@ -95,7 +116,7 @@ struct BankPushRoutes {
 };
 struct BankRoutedWindows {
     BankWindows w;                         // (first: bank_window_finish reads it)
-    BankPushRoutes r;
+    BankWindowRoutes r;
 };
 static EI_IMPULSE_ERROR bank_routed_window_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
 {
@@ -105,7 +126,7 @@ static EI_IMPULSE_ERROR bank_routed_window_finish(void *ctx, float *win, size_t 
 }
 struct BankRoutedContinuous {
     BankContinuous c;                      // (first: bank_window_finish and bank_continuous_maf read it)
-    BankPushRoutes r;
+    BankWindowRoutes r;
     BankRoutedContinuous(kws_bank *b, float *const *scores, float *const *raw_scores, int k_full, float *maf, const long long *base) : c(b, scores, raw_scores, k_full, maf, base) {}
 };
 static EI_IMPULSE_ERROR bank_routed_continuous_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
@@ -176,6 +197,82 @@ EI_IMPULSE_ERROR kws_bank_scan_recordings_device(kws_bank *b, const int16_t *pcm
     BankUse use(b, s, true);
     BankContinuous ctx(b, scores, raw_scores);
     return kws_scan_run(b->m[0], pcm, offsets, lengths, R, slice_samples, bank_max_labels(b), 0, bank_window_finish, bank_continuous_maf, &ctx, s);
+}
+
+// A recording call's routes, checked; then what its hooks need: every recording's window count and, of the recordings that have windows,
+// their routes in order and the members they name.  every: the recordings that have windows all name every member (the unrouted call).
+struct BankRecordingRoutes {
+    std::vector<size_t> n_windows;         // [R]
+    std::vector<uint32_t> active;
+    uint32_t wanted = 0;
+    bool every = true;
+    void add(uint32_t route, size_t W, size_t K)
+    {
+        n_windows.push_back(W);
+        if (!W) return;
+        active.push_back(route);
+        wanted |= route;
+        every = every && route == (1u << K) - 1u;
+    }
+};
+static EI_IMPULSE_ERROR bank_recording_routes_check(const kws_bank *b, const uint32_t *routes, size_t R)
+{
+    const size_t bad = kws_bank_route_check(routes, R, b->m.size());
+    if (bad < R) return fail(KWS_ERROR_BAD_ARGUMENT, "recording %zu: route 0x%x names a member at or above the bank's %zu", bad, routes[bad], b->m.size());
+    return EI_IMPULSE_OK;
+}
+
+EI_IMPULSE_ERROR kws_bank_scan_recordings_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                        const uint32_t *routes, size_t slice_samples, float *const *scores, float *const *raw_scores,
+                                                        void *stream)
+{
+    if (!routes) return kws_bank_scan_recordings_device(b, pcm, offsets, lengths, R, slice_samples, scores, raw_scores, stream);
+    if (!b || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (bank_wants_nothing(b, scores, nullptr)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] is NULL");
+    if (R > 0 && (!pcm || !offsets || !lengths)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (R > 0x3fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "too many recordings");
+    EI_IMPULSE_ERROR e = bank_recording_routes_check(b, routes, R);
+    if (e) return e;
+    ScanLayout L;
+    if ((e = scan_layout(b->m[0], slice_samples, &L))) return e;
+    BankRecordingRoutes rr;
+    for (size_t r = 0; r < R; ++r) rr.add(routes[r], L.windows(lengths[r] / slice_samples), b->m.size());
+    if (rr.every) return kws_bank_scan_recordings_device(b, pcm, offsets, lengths, R, slice_samples, scores, raw_scores, stream);
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    BankUse use(b, s, true);
+    BankRoutedContinuous ctx(b, scores, raw_scores, 0, nullptr, nullptr);
+    ctx.r = BankWindowRoutes{ routes, nullptr, rr.n_windows.data(), R, {}, false };
+    ctx.c.scan_routes = &rr.active;
+    ctx.c.wanted = rr.wanted;
+    return kws_scan_run(b->m[0], pcm, offsets, lengths, R, slice_samples, bank_max_labels(b), 0, bank_routed_continuous_finish, bank_continuous_maf, &ctx, s);
+}
+
+EI_IMPULSE_ERROR kws_bank_slide_recordings_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                         const uint32_t *routes, size_t hop_samples, int flags, float *const *scores, float *features,
+                                                         void *stream)
+{
+    if (!routes) return kws_bank_slide_recordings_device(b, pcm, offsets, lengths, R, hop_samples, flags, scores, features, stream);
+    if (!b || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
+    // (what the unrouted call refuses: a bad hop or flags, NULL lengths, too many windows -- any member's plan)
+    kws_slide_plan_info I;
+    EI_IMPULSE_ERROR e;
+    for (kws_handle *h : b->m)
+        if ((e = kws_slide_plan(h, lengths, R, hop_samples, flags, &I))) return e;
+    if ((e = bank_recording_routes_check(b, routes, R))) return e;
+    BankRecordingRoutes rr;
+    for (size_t r = 0; r < R; ++r) {
+        size_t W = 0;
+        if ((e = kws_slide_window_count(b->m[0], lengths[r], hop_samples, &W))) return e;
+        rr.add(routes[r], W, b->m.size());
+    }
+    if (rr.every) return kws_bank_slide_recordings_device(b, pcm, offsets, lengths, R, hop_samples, flags, scores, features, stream);
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    BankUse use(b, s, true);
+    BankRoutedWindows ctx{ { b, scores, features }, { routes, nullptr, rr.n_windows.data(), R, {}, false } };
+    return kws_slide_run(b->m[0], pcm, offsets, lengths, R, hop_samples, flags, 0, bank_routed_window_finish, &ctx, s);
 }
 
 EI_IMPULSE_ERROR kws_bank_live_create(kws_bank *b, size_t S, size_t slice_samples, kws_bank_live **out)
@@ -288,7 +385,7 @@ EI_IMPULSE_ERROR kws_bank_live_push_device(kws_bank_live *lv, size_t n, const si
     } else {
         BankRoutedContinuous ctx(b, scores ? scores : none, raw_scores, (int)lv->L.k_full, lv->maf, lv->base.data());
         ctx.c.d_routes = lv->d_routes;
-        ctx.r = BankPushRoutes{ &lv->routes.route, streams, n_windows, n, {}, false };
+        ctx.r = BankWindowRoutes{ lv->routes.route.data(), streams, n_windows, n, {}, false };
         e = kws_live_run(lv->core, n, streams, pcm, offsets, lengths, finish, scores, n_windows, bank_max_labels(b), 0, 0, bank_routed_continuous_finish,
                          bank_continuous_maf, &ctx, s);
     }
@@ -362,7 +459,7 @@ EI_IMPULSE_ERROR kws_bank_slide_live_push_device(kws_bank_slide_live *sl, size_t
         BankWindows ctx{ b, scores, features };
         return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish, &ctx, s);
     }
-    BankRoutedWindows ctx{ { b, scores, features }, { &sl->routes.route, streams, n_windows, n, {}, false } };
+    BankRoutedWindows ctx{ { b, scores, features }, { sl->routes.route.data(), streams, n_windows, n, {}, false } };
     return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores, n_windows, bank_max_labels(b), 0, 0, bank_routed_window_finish, &ctx, s);
 }
 

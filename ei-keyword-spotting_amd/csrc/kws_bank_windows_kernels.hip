@@ -5,6 +5,7 @@
 //     LIVE = true    the live form: the filter resumed from HBM and stored back, not stored for a stream the push finishes --
 //                    kws_live_maf_kernel for every member, with its w0 / k_full rule and its index as the window count mod taps
 //   kws_bank_maf_routed_kernel  the live form for a routed session: (entry, member) pairs the entry's route leaves out are skipped
+//   kws_bank_maf_scan_routed_kernel  the scan form for a routed call: (recording, member) pairs the recording's route leaves out are skipped
 // The members' label counts differ, so a thread finds its member by walking the by-value table (at most KWS_BANK_MAX entries); member i's
 // rows are [windows][labels[i]] in its own buffers.  The arithmetic is the two existing kernels', operation for operation and in their
 // order (rs -= buf[idx]; rs += v; buf[idx] = v; out = rs / (float)taps), so a member's rows are the bits its own call writes.
@@ -103,6 +104,36 @@ __global__ __launch_bounds__(64) void kws_bank_maf_routed_kernel(KwsBankMaf M, K
     st[KWS_BANK_TAPS] = rs;
 }
 
+// The scan form for a routed call, a sibling: R.routes [n] holds the route of every recording that has windows, in the order of wbase, and
+// R.member[i] the bank member behind slot i; a pair the recording's route leaves out ends before it reads a row (a scan's filter is fresh per
+// recording: there is no state to skip).  The rest is kws_bank_maf_kernel<false>, operation for operation.
+__global__ __launch_bounds__(64) void kws_bank_maf_scan_routed_kernel(KwsBankMaf M, KwsBankMafRoute R, const long long *__restrict__ wbase, int n, int total)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)n * total) return;
+    const int a = (int)(t / total);
+    int l = (int)(t - (long long)a * total), i = 0;
+    while (i < M.n - 1 && l >= M.labels[i]) { l -= M.labels[i]; ++i; }
+    if (!((R.routes[a] >> R.member[i]) & 1u)) return;
+    const int labels = M.labels[i];
+    const float *raw = M.raw[i];
+    float *scores = M.scores[i];
+    const long long g0 = wbase[a], g1 = wbase[a + 1];
+    float buf[KWS_BANK_TAPS];
+    float rs = 0.0f;
+#pragma unroll
+    for (int j = 0; j < KWS_BANK_TAPS; ++j) buf[j] = 0.0f;
+    int idx = 0;
+    for (long long g = g0; g < g1; ++g) {
+        const float v = raw[(size_t)g * labels + l];
+        rs -= buf[idx];
+        rs += v;
+        buf[idx] = v;
+        scores[(size_t)g * labels + l] = rs / (float)KWS_BANK_TAPS;
+        if (++idx >= KWS_BANK_TAPS) idx = 0;
+    }
+}
+
 static int bank_maf_total(const KwsBankMaf &M)
 {
     int total = 0;
@@ -139,5 +170,15 @@ int kws_launch_bank_maf_live_routed(const KwsBankMaf &M, const KwsBankMafRoute &
     const long long n = (long long)n_act * total;
     if (n <= 0) return 0;
     hipLaunchKernelGGL(kws_bank_maf_routed_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, M, R, live_meta(meta, n_act), n_act, total, k_full, maf);
+    return (int)hipGetLastError();
+}
+
+int kws_launch_bank_maf_scan_routed(const KwsBankMaf &M, const KwsBankMafRoute &R, const long long *wbase, int n_rec, hipStream_t stream)
+{
+    (void)hipGetLastError();
+    const int total = bank_maf_total(M);
+    const long long n = (long long)n_rec * total;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(kws_bank_maf_scan_routed_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, M, R, wbase, n_rec, total);
     return (int)hipGetLastError();
 }

@@ -662,12 +662,44 @@ EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_device(kws_bank *b, const int16_
  *                     KWS_ERROR_BAD_ARGUMENT with no state change.  The moving average stays ONE launch whatever K.
  *   kws_bank_slide_live_route  the same for a live one-shot session; there is no per-member state, so a route may change between any two
  *                     pushes.  kws_bank_slide_live_reset keeps routes.
- * Not routed in this version: recording scans and slides, cepstra-in calls, the host-buffer and SDK forms. */
+ * Recording calls and cepstra-in calls.  The three forms below take the unrouted call's arguments plus `routes` (HOST) directly after the
+ * count: one route per RECORDING (a window's route is its recording's) or per cepstral matrix.  The contract is the one above:
+ *   refusals      a bit at or above kws_bank_size(b): KWS_ERROR_BAD_ARGUMENT, kws_last_error names the first offending recording (or row)
+ *                 and its mask; checked before anything is enqueued, nothing is written.  Whatever the unrouted call refuses is refused
+ *                 with its code.  R = 0, B = 0 or no window: EI_IMPULSE_OK, nothing written -- after the routes [R] / [B] were checked (a
+ *                 bad route of a recording too short for a window is still refused; with R = 0 or B = 0 no route is read).
+ *   NULL, all     routes == NULL IS the unrouted call; so is a call in which every recording that has a window (every row) names every
+ *                 member: the unrouted launches, no upload.
+ *   output        the unrouted call's layout: member k's buffer is [sum_r W_r][labels_k], recording r's windows at rows [wbase_r, wbase_r +
+ *                 W_r).  Only the rows of routed (window, member) pairs are written -- in scores, in raw_scores and by the moving average;
+ *                 every other row of every score buffer is left untouched, bit for bit.  A scan's filter is fresh per recording, so an
+ *                 unrouted (recording, member) pair has no state, and none is read.
+ *   features      (slide, cepstra-in) every row, routed or not: the unrouted call's bits.  A recording whose route is 0 still goes through
+ *                 the front end, as a zero-mask clip does in the batch call; callers that want to spare that work drop such recordings.
+ *   NULL scores   scores[k] == NULL skips member k even where it is routed (the unrouted scan's and slide's rule).  A member no recording
+ *                 with windows names, or a member without a buffer, launches nothing.
+ *   parity        a routed pair's rows are the bits of the unrouted bank call, so of that member's own kws_scan_recordings_device,
+ *                 kws_slide_recordings_device or kws_cmvn_inference_batch_device in KWS_MODE_EXACT (int8 bit-exact with the reference,
+ *                 float32 scores within 1e-6); the slide's paths (AUTO, DIRECT, SHARED) stay bit-identical to each other under any routes.
+ *   mode          exact launches only; no member's mode, fast counters or logits tap is read or written.
+ *   launches      the front end once; per chunk of windows the routed network launches above over that chunk's lists (one upload per chunk:
+ *                 4 x (K + routed pairs of the chunk) bytes); the scan's moving average is ONE launch whatever K, over the members some
+ *                 recording names, and reads the routes of the recordings that have windows from bank-owned device memory (at most R x 4
+ *                 bytes, uploaded with the call).  Ordering, locks and the rest of the device memory: the unrouted forms'.
+ * Not routed in this version: the host-buffer and SDK forms. */
 EI_IMPULSE_ERROR kws_bank_run_classifier_routed_device(kws_bank *b, const int16_t *pcm, size_t B, const uint32_t *routes,
                                                        float *const *scores, float *features, void *stream);
 EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths,
                                                               size_t B, const uint32_t *routes, float *const *scores, float *features,
                                                               void *stream);
+EI_IMPULSE_ERROR kws_bank_scan_recordings_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                        const uint32_t *routes, size_t slice_samples, float *const *scores,
+                                                        float *const *raw_scores, void *stream);
+EI_IMPULSE_ERROR kws_bank_slide_recordings_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                         const uint32_t *routes, size_t hop_samples, int flags, float *const *scores,
+                                                         float *features, void *stream);
+EI_IMPULSE_ERROR kws_bank_cmvn_inference_routed_device(kws_bank *b, const float *mfcc, size_t B, const uint32_t *routes, float *const *scores,
+                                                       float *features, void *stream);
 EI_IMPULSE_ERROR kws_bank_live_route(kws_bank_live *lv, const size_t *streams, size_t n, const uint32_t *routes);
 EI_IMPULSE_ERROR kws_bank_slide_live_route(kws_bank_slide_live *sl, const size_t *streams, size_t n, const uint32_t *routes);
 
