@@ -66,100 +66,77 @@ size_t kws_bank_route_check(const uint32_t *routes, size_t n, size_t K)
     return n;
 }
 
-void kws_bank_window_routes(const uint32_t *route, const size_t *index, const size_t *n_windows, size_t n, std::vector<uint32_t> &out)
+// the refusal of a call whose routes (NULL: none to check) name a member the bank does not have; what: the call's word for a row
+EI_IMPULSE_ERROR bank_routes_check(const kws_bank *b, const uint32_t *routes, size_t n, const char *what)
 {
-    out.clear();
-    for (size_t i = 0; i < n; ++i) out.insert(out.end(), n_windows[i], route[index ? index[i] : i]);
-}
-
-// The routed form of bank_networks: member k runs over the rows whose route names it.  The lists travel with the call (one upload, behind
-// the stream's earlier work: a chunk's lists replace the previous chunk's only after its launches); a member with an empty list, or without
-// a score buffer, launches nothing.
-static EI_IMPULSE_ERROR bank_networks_routed(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, const uint32_t *routes, hipStream_t s)
-{
-    const size_t K = b->m.size(), F = b->m[0]->model.nn_input_frame_size;
-    size_t at[KWS_BANK_MAX + 1];
-    // (the host copy is read by the upload of the call or chunk before: that upload has ended before it is rewritten)
-    if (b->lists_ev_used) HIP_TRY(hipEventSynchronize(b->lists_ev));
-    b->lists_ev_used = false;
-    kws_bank_route_lists(routes, B, K, b->h_lists, at);
-    EI_IMPULSE_ERROR e;
-    if ((e = grow_buffer(&b->d_lists, &b->lists_cap, at[K]))) return e;
-    KwsBankOut o16{}, o64{};
-    KwsBankLists l16{}, l64{}, lq{};
-    KwsBankQuant Q{};
-    int n16 = 0, n64 = 0, nq = 0;
-    bool any = false;
-    for (size_t k = 0; k < K; ++k) {
-        kws_handle *h = b->m[k];
-        const int n = b->h_lists[at[k]];
-        if (!scores[k] || n == 0) continue;
-        any = true;
-        if (h->is_float) continue;
-        if (kws_nn_uses_mfma(h->nn)) {
-            const bool w16 = h->nn.blk[0].in_cpad == 16;
-            KwsBankOut &o = w16 ? o16 : o64;
-            (w16 ? l16 : l64).list[o.n] = b->d_lists + at[k];
-            (w16 ? n16 : n64) = std::max(w16 ? n16 : n64, n);
-            o.rec[o.n] = (int)k; o.scores[o.n] = scores[k] + row0 * h->model.labels.size(); ++o.n;
-        } else {
-            if ((e = ensure_scratch(h, B))) return e;         // (its tensor is indexed by row: B rows, the listed ones written)
-            lq.list[Q.n] = b->d_lists + at[k];
-            nq = std::max(nq, n);
-            Q.scale[Q.n] = h->nn.in_scale; Q.zp[Q.n] = h->nn.in_zp; Q.q[Q.n] = h->s_q; ++Q.n;
-        }
-    }
-    if (!any) return EI_IMPULSE_OK;
-    HIP_TRY(hipMemcpyAsync(b->d_lists, b->h_lists.data(), at[K] * sizeof(int), hipMemcpyHostToDevice, s));
-    if (!b->lists_ev) HIP_TRY(hipEventCreateWithFlags(&b->lists_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->lists_ev, s));
-    b->lists_ev_used = true;
-    const int grid_cap = grid_cap_nn(b->m[0]);
-    KWS_LAUNCH_TRY_OBJ("routed bank NN kernel", kws_launch_bank_nn_mfma_routed(b->d_rec, o16, l16, 16, feat, n16, grid_cap, s));
-    KWS_LAUNCH_TRY_OBJ("routed bank NN kernel", kws_launch_bank_nn_mfma_routed(b->d_rec, o64, l64, 64, feat, n64, grid_cap, s));
-    KWS_LAUNCH_TRY("routed bank quantise kernel", kws_launch_bank_quantize_routed(feat, (int)F, Q, lq, nq, s));
-    for (size_t k = 0; k < K; ++k) {
-        kws_handle *h = b->m[k];
-        const int n = b->h_lists[at[k]];
-        if (!scores[k] || n == 0 || !(h->is_float || !kws_nn_uses_mfma(h->nn))) continue;
-        float *dst = scores[k] + row0 * h->model.labels.size();
-        if ((e = network_device(h, feat, h->s_q, (size_t)n, dst, nullptr, nullptr, nullptr, nullptr, b->d_lists + at[k], s))) return e;
-    }
+    const size_t bad = routes ? kws_bank_route_check(routes, n, b->m.size()) : n;
+    if (bad < n) return fail(KWS_ERROR_BAD_ARGUMENT, "%s %zu: route 0x%x names a member at or above the bank's %zu", what, bad, routes[bad], b->m.size());
     return EI_IMPULSE_OK;
 }
 
-// every member's network from the feature matrix feat [B][F] (device); scores[k] + row0 * labels of member k is where its rows go
+// a launch of bank_networks, with the failure text of its form (reads `routed`): "bank <what> launch failed: ..." / "routed bank <what> ..."
+#define BANK_LAUNCH_TRY(TRY, what, expr)             \
+    do {                                             \
+        const int rc = (expr);                       \
+        if (routed) TRY("routed bank " what, rc);    \
+        else TRY("bank " what, rc);                  \
+    } while (0)
+
+// Every member's network from the feature matrix feat [B][F] (device); scores[k] + row0 * labels of member k is where its rows go.  The int8
+// members fall into three classes, one launch each: matrix-core with 16-byte activation rows, matrix-core with up to 64 (kws_launch_nn's
+// rule), and the rest, whose input tensors one quantise pass writes before each runs its own network_device, as the float32 members do.
+// Routed (some route does not name every member), member k runs over the list of rows that name it: the lists travel with the call (one
+// upload, behind the stream's earlier work: a chunk's lists replace the previous chunk's only after its launches), and a member with an
+// empty list, or without a score buffer, launches nothing.
 EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, hipStream_t s, const uint32_t *routes)
 {
-    // (routes that all name every member: the unrouted launches, which need no list)
-    const uint32_t every = (1u << b->m.size()) - 1u;
-    for (size_t i = 0; routes && i < B; ++i)
-        if (routes[i] != every) return bank_networks_routed(b, feat, B, scores, row0, routes, s);
     const size_t K = b->m.size(), F = b->m[0]->model.nn_input_frame_size;
-    KwsBankOut o16{}, o64{};
-    KwsBankQuant Q{};
+    // (routes that all name every member: the unrouted launches, which need no list)
+    bool routed = false;
+    for (size_t i = 0; routes && i < B; ++i) routed = routed || routes[i] != (1u << K) - 1u;
+    size_t at[KWS_BANK_MAX + 1] = { 0 };
     EI_IMPULSE_ERROR e;
-    for (size_t k = 0; k < K; ++k) {
-        kws_handle *h = b->m[k];
-        if (!scores[k] || h->is_float) continue;
-        float *dst = scores[k] + row0 * h->model.labels.size();
-        if (kws_nn_uses_mfma(h->nn)) {
-            KwsBankOut &o = h->nn.blk[0].in_cpad == 16 ? o16 : o64;       // (kws_launch_nn's rule: 16-byte rows, or up to 64)
-            o.rec[o.n] = (int)k; o.scores[o.n] = dst; ++o.n;
-        } else {
-            if ((e = ensure_scratch(h, B))) return e;
-            Q.scale[Q.n] = h->nn.in_scale; Q.zp[Q.n] = h->nn.in_zp; Q.q[Q.n] = h->s_q; ++Q.n;
-        }
+    if (routed) {
+        if ((e = b->lists.wait())) return e;
+        kws_bank_route_lists(routes, B, K, b->lists.host, at);
+        if ((e = b->lists.grow(at[K]))) return e;
     }
-    const int grid_cap = grid_cap_nn(b->m[0]);
-    KWS_LAUNCH_TRY_OBJ("bank NN kernel", kws_launch_bank_nn_mfma(b->d_rec, o16, 16, feat, (int)B, grid_cap, s));
-    KWS_LAUNCH_TRY_OBJ("bank NN kernel", kws_launch_bank_nn_mfma(b->d_rec, o64, 64, feat, (int)B, grid_cap, s));
-    KWS_LAUNCH_TRY("bank quantise kernel", kws_launch_bank_quantize(feat, B * F, Q, s));
+    // member k's rows: how many, and which (NULL: all B)
+    auto rows = [&](size_t k) { return !scores[k] ? 0 : routed ? b->lists.host[at[k]] : (int)B; };
+    auto list = [&](size_t k) { return routed ? b->lists.dev + at[k] : (const int *)nullptr; };
+    enum { W16, W64, QUANT, CLASSES };
+    KwsBankOut o[2] = {};
+    KwsBankQuant Q{};
+    KwsBankLists l[CLASSES] = {};
+    int longest[CLASSES] = { 0 }, own[KWS_BANK_MAX], n_own = 0;
+    bool any = false;
     for (size_t k = 0; k < K; ++k) {
         kws_handle *h = b->m[k];
-        if (!scores[k]) continue;
-        float *dst = scores[k] + row0 * h->model.labels.size();
-        if ((h->is_float || !kws_nn_uses_mfma(h->nn)) && (e = network_device(h, feat, h->s_q, B, dst, nullptr, nullptr, nullptr, nullptr, nullptr, s))) return e;
+        if (rows(k) == 0) continue;
+        any = true;
+        const int c = h->is_float ? CLASSES : !kws_nn_uses_mfma(h->nn) ? QUANT : h->nn.blk[0].in_cpad == 16 ? W16 : W64;
+        if (c >= QUANT) own[n_own++] = (int)k;
+        if (c == CLASSES) continue;
+        if (c == QUANT) {
+            if ((e = ensure_scratch(h, B))) return e;         // (its tensor is indexed by row: B rows, routed the listed ones written)
+            l[c].list[Q.n] = list(k);
+            Q.scale[Q.n] = h->nn.in_scale; Q.zp[Q.n] = h->nn.in_zp; Q.q[Q.n] = h->s_q; ++Q.n;
+        } else {
+            l[c].list[o[c].n] = list(k);
+            o[c].rec[o[c].n] = (int)k; o[c].scores[o[c].n] = scores[k] + row0 * h->model.labels.size(); ++o[c].n;
+        }
+        longest[c] = std::max(longest[c], rows(k));
+    }
+    if (!any) return EI_IMPULSE_OK;
+    if (routed && (e = b->lists.send(at[K], s))) return e;
+    const int grid_cap = grid_cap_nn(b->m[0]);
+    BANK_LAUNCH_TRY(KWS_LAUNCH_TRY_OBJ, "NN kernel", kws_launch_bank_nn_mfma(b->d_rec, o[W16], routed ? &l[W16] : nullptr, 16, feat, longest[W16], grid_cap, s));
+    BANK_LAUNCH_TRY(KWS_LAUNCH_TRY_OBJ, "NN kernel", kws_launch_bank_nn_mfma(b->d_rec, o[W64], routed ? &l[W64] : nullptr, 64, feat, longest[W64], grid_cap, s));
+    BANK_LAUNCH_TRY(KWS_LAUNCH_TRY, "quantise kernel", kws_launch_bank_quantize(feat, longest[QUANT], (int)F, Q, routed ? &l[QUANT] : nullptr, s));
+    for (int j = 0; j < n_own; ++j) {
+        kws_handle *h = b->m[own[j]];
+        float *dst = scores[own[j]] + row0 * h->model.labels.size();
+        if ((e = network_device(h, feat, h->s_q, (size_t)rows(own[j]), dst, nullptr, nullptr, nullptr, nullptr, list(own[j]), s))) return e;
     }
     return EI_IMPULSE_OK;
 }
@@ -171,23 +148,34 @@ bool bank_wants_nothing(const kws_bank *b, float *const *scores, const float *fe
     return true;
 }
 
-// the finishing step of a chunk of gathered windows for a bank (the slide's, and the window pipelines' of kws_bank_windows.cpp): cmvnw (the MFE
-// normalisation) once through the first member, then every member
-EI_IMPULSE_ERROR bank_window_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
+EI_IMPULSE_ERROR bank_feature_rows(kws_bank *b, float *features, size_t n, float **f)
 {
-    if (n == 0) return EI_IMPULSE_OK;
-    BankWindows &c = *(BankWindows *)ctx;
-    kws_bank *b = c.b;
-    kws_handle *h0 = b->m[0];
-    const size_t F = h0->model.nn_input_frame_size;
-    EI_IMPULSE_ERROR e;
-    float *f = c.features ? c.features + g0 * F : nullptr;
-    if (!f) {
-        if ((e = grow_buffer(&b->feat, &b->feat_cap, n * F))) return e;
-        f = b->feat;
-    }
-    if ((e = cmvn_nn_device(h0, win, n, f, nullptr, nullptr, nullptr, nullptr, nullptr, s))) return e;
-    return bank_networks(b, f, n, c.scores, g0, s, c.routes ? c.routes + g0 : nullptr);
+    *f = features;
+    if (features) return EI_IMPULSE_OK;
+    const EI_IMPULSE_ERROR e = grow_buffer(&b->feat, &b->feat_cap, n * (size_t)b->m[0]->model.nn_input_frame_size);
+    *f = b->feat;
+    return e;
+}
+
+// The two batch calls: the checks, the front end ONCE through the first member (front: from `in` into the feature matrix), then every
+// member's network.  row: the call's word for a row in its refusals.
+template <typename Front>
+static EI_IMPULSE_ERROR bank_batch(kws_bank *b, const void *in, size_t B, const uint32_t *routes, const char *row, float *const *scores, float *features,
+                                   void *stream, Front front)
+{
+    if (!b || !in || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
+    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
+    EI_IMPULSE_ERROR e = bank_routes_check(b, routes, B, row);
+    if (e) return e;
+    if (B == 0) return EI_IMPULSE_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    BankUse use(b, s, false);
+    float *f;
+    if ((e = bank_feature_rows(b, features, B, &f))) return e;
+    if ((e = front(b->m[0], f, s))) return e;
+    return bank_networks(b, f, B, scores, 0, s, routes);
 }
 
 extern "C" {
@@ -242,10 +230,8 @@ void kws_bank_destroy(kws_bank *b)
     }
     if (b->d_rec) (void)hipFree(b->d_rec);
     if (b->feat) (void)hipFree(b->feat);
-    if (b->d_lists) (void)hipFree(b->d_lists);
-    if (b->lists_ev) (void)hipEventDestroy(b->lists_ev);
-    if (b->d_routes) (void)hipFree(b->d_routes);
-    if (b->routes_ev) (void)hipEventDestroy(b->routes_ev);
+    b->lists.release();
+    b->routes.release();
     delete b;
 }
 
@@ -254,46 +240,14 @@ kws_handle *kws_bank_member(const kws_bank *b, size_t k) { return b && k < b->m.
 
 EI_IMPULSE_ERROR kws_bank_run_classifier_batch_device(kws_bank *b, const int16_t *pcm, size_t B, float *const *scores, float *features, void *stream)
 {
-    if (!b || !pcm || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
-    if (B == 0) return EI_IMPULSE_OK;
-    HIP_TRY(hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
-    BankUse use(b, s, false);
-    kws_handle *h0 = b->m[0];
-    EI_IMPULSE_ERROR e;
-    float *f = features;
-    if (!f) {
-        if ((e = grow_buffer(&b->feat, &b->feat_cap, B * (size_t)h0->model.nn_input_frame_size))) return e;
-        f = b->feat;
-    }
-    if ((e = mfcc_fused_device(h0, pcm, 0, B, f, nullptr, s))) return e;
-    return bank_networks(b, f, B, scores, 0, s);
+    return kws_bank_run_classifier_routed_device(b, pcm, B, nullptr, scores, features, stream);
 }
 
 EI_IMPULSE_ERROR kws_bank_run_classifier_routed_device(kws_bank *b, const int16_t *pcm, size_t B, const uint32_t *routes, float *const *scores, float *features,
                                                        void *stream)
 {
-    if (!routes) return kws_bank_run_classifier_batch_device(b, pcm, B, scores, features, stream);
-    if (!b || !pcm || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
-    const size_t bad = kws_bank_route_check(routes, B, b->m.size());
-    if (bad < B) return fail(KWS_ERROR_BAD_ARGUMENT, "clip %zu: route 0x%x names a member at or above the bank's %zu", bad, routes[bad], b->m.size());
-    if (B == 0) return EI_IMPULSE_OK;
-    HIP_TRY(hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
-    BankUse use(b, s, false);
-    kws_handle *h0 = b->m[0];
-    EI_IMPULSE_ERROR e;
-    float *f = features;
-    if (!f) {
-        if ((e = grow_buffer(&b->feat, &b->feat_cap, B * (size_t)h0->model.nn_input_frame_size))) return e;
-        f = b->feat;
-    }
-    if ((e = mfcc_fused_device(h0, pcm, 0, B, f, nullptr, s))) return e;
-    return bank_networks(b, f, B, scores, 0, s, routes);
+    return bank_batch(b, pcm, B, routes, "clip", scores, features, stream,
+                      [&](kws_handle *h0, float *f, hipStream_t s) { return mfcc_fused_device(h0, pcm, 0, B, f, nullptr, s); });
 }
 
 EI_IMPULSE_ERROR kws_bank_cmvn_inference_batch_device(kws_bank *b, const float *mfcc, size_t B, float *const *scores, float *features, void *stream)
@@ -303,42 +257,10 @@ EI_IMPULSE_ERROR kws_bank_cmvn_inference_batch_device(kws_bank *b, const float *
 
 EI_IMPULSE_ERROR kws_bank_cmvn_inference_routed_device(kws_bank *b, const float *mfcc, size_t B, const uint32_t *routes, float *const *scores, float *features, void *stream)
 {
-    if (!b || !mfcc || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
-    if (B > 0x7fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
-    const size_t bad = routes ? kws_bank_route_check(routes, B, b->m.size()) : B;
-    if (bad < B) return fail(KWS_ERROR_BAD_ARGUMENT, "row %zu: route 0x%x names a member at or above the bank's %zu", bad, routes[bad], b->m.size());
-    if (B == 0) return EI_IMPULSE_OK;
-    HIP_TRY(hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
-    BankUse use(b, s, false);
-    kws_handle *h0 = b->m[0];
-    EI_IMPULSE_ERROR e;
-    float *f = features;
-    if (!f) {
-        if ((e = grow_buffer(&b->feat, &b->feat_cap, B * (size_t)h0->model.nn_input_frame_size))) return e;
-        f = b->feat;
-    }
-    if ((e = ensure_scratch(h0, B))) return e;        // (a general-shape int8 first member: cmvn_nn_device writes its int8 tensor there)
-    if ((e = cmvn_nn_device(h0, mfcc, B, f, nullptr, nullptr, nullptr, nullptr, nullptr, s))) return e;
-    return bank_networks(b, f, B, scores, 0, s, routes);
-}
-
-EI_IMPULSE_ERROR kws_bank_slide_recordings_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
-                                                  size_t hop_samples, int flags, float *const *scores, float *features, void *stream)
-{
-    if (!b || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
-    // the window count is any member's; the bound on windows x labels holds for the member with the most labels
-    kws_slide_plan_info I;
-    EI_IMPULSE_ERROR e;
-    for (kws_handle *h : b->m)
-        if ((e = kws_slide_plan(h, lengths, R, hop_samples, flags, &I))) return e;
-    HIP_TRY(hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
-    BankUse use(b, s, true);
-    BankWindows ctx{ b, scores, features };
-    return kws_slide_run(b->m[0], pcm, offsets, lengths, R, hop_samples, flags, 0, bank_window_finish, &ctx, s);
+    return bank_batch(b, mfcc, B, routes, "row", scores, features, stream, [&](kws_handle *h0, float *f, hipStream_t s) {
+        const EI_IMPULSE_ERROR e = ensure_scratch(h0, B);          // (a general-shape int8 first member: cmvn_nn_device writes its int8 tensor there)
+        return e ? e : cmvn_nn_device(h0, mfcc, B, f, nullptr, nullptr, nullptr, nullptr, nullptr, s);
+    });
 }
 
 #pragma GCC visibility pop

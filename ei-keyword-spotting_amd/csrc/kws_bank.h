@@ -30,19 +30,17 @@ struct KwsBankQuant {
     int8_t *q[KWS_BANK_MAX];       // [n] each
 };
 
-int kws_launch_bank_nn_mfma(const KwsBankRec *recs, const KwsBankOut &out, int cp, const float *features, int n_clips, int grid_cap, hipStream_t stream);
-int kws_launch_bank_quantize(const float *features, size_t n, const KwsBankQuant &Q, hipStream_t stream);
-
 // Routed calls (a route per row: bit k set = member k scores it): slot i of a launch walks its member's list of rows instead of every row.
 // A list is the `sel` list of the members' own launchers (kws_device.h): [0] = how many, [1 + j] = row, ascending; device memory, uploaded
-// with the call.  n_longest: the longest list of the launch (sizes the grid); a member with an empty list gets no slot.
+// with the call.  A member with an empty list gets no slot.
 struct KwsBankLists {
     const int *list[KWS_BANK_MAX];
 };
-int kws_launch_bank_nn_mfma_routed(const KwsBankRec *recs, const KwsBankOut &out, const KwsBankLists &lists, int cp, const float *features, int n_longest,
-                                   int grid_cap, hipStream_t stream);
-// row_len: values per feature row; member slot j's tensor is written only at its listed rows
-int kws_launch_bank_quantize_routed(const float *features, int row_len, const KwsBankQuant &Q, const KwsBankLists &lists, int n_longest, hipStream_t stream);
+// lists == NULL: the unrouted kernels over rows 0 .. n_rows - 1.  Otherwise the routed kernels, n_rows being the longest list of the launch
+// (it sizes the grid).  row_len: values per feature row; routed, member slot j's tensor is written only at its listed rows.
+int kws_launch_bank_nn_mfma(const KwsBankRec *recs, const KwsBankOut &out, const KwsBankLists *lists, int cp, const float *features, int n_rows, int grid_cap,
+                            hipStream_t stream);
+int kws_launch_bank_quantize(const float *features, int n_rows, int row_len, const KwsBankQuant &Q, const KwsBankLists *lists, hipStream_t stream);
 
 // One moving-average launch for every member of a continuous-mode bank call (kws_bank_windows_kernels.hip): member slot i filters
 // raw[i] [windows][labels[i]] into scores[i] (may be the same buffer); a live push keeps member i's filters at maf + base[i], stream after
@@ -54,22 +52,51 @@ struct KwsBankMaf {
     float *scores[KWS_BANK_MAX];
     long long base[KWS_BANK_MAX];
 };
-int kws_launch_bank_maf_scan(const KwsBankMaf &M, const long long *wbase, int n_rec, hipStream_t stream);
-int kws_launch_bank_maf_live(const KwsBankMaf &M, const long long *meta, int n_act, int k_full, float *maf, hipStream_t stream);
-// The live form for a routed session: routes [S] (device) holds every stream's route, member[i] the bank member behind slot i; an (entry,
-// slot) pair whose stream's route leaves the member out is skipped -- its rows and its filter state are neither read nor written.
+// A routed call's moving average: routes (device) holds a route per stream (live: [S], every stream of the session) or per recording that
+// has windows (scan: [n_rec], in the order of wbase), member[i] the bank member behind slot i; an (entry or recording, slot) pair whose
+// route leaves the member out is skipped -- its rows and, live, its filter state are neither read nor written.
 struct KwsBankMafRoute {
     const uint32_t *routes;
     int member[KWS_BANK_MAX];
 };
-int kws_launch_bank_maf_live_routed(const KwsBankMaf &M, const KwsBankMafRoute &R, const long long *meta, int n_act, int k_full, float *maf, hipStream_t stream);
-// The scan form for a routed call: R.routes [n_rec] (device) holds the route of every recording that has windows, in the order of wbase; a
-// (recording, slot) pair whose route leaves the member out is skipped -- its rows are neither read nor written.
-int kws_launch_bank_maf_scan_routed(const KwsBankMaf &M, const KwsBankMafRoute &R, const long long *wbase, int n_rec, hipStream_t stream);
+// R == NULL: the unrouted kernel
+int kws_launch_bank_maf_scan(const KwsBankMaf &M, const KwsBankMafRoute *R, const long long *wbase, int n_rec, hipStream_t stream);
+int kws_launch_bank_maf_live(const KwsBankMaf &M, const KwsBankMafRoute *R, const long long *meta, int n_act, int k_full, float *maf, hipStream_t stream);
 
 // ---- host side (kws_bank.cpp, kws_bank_windows.cpp: the units that include kws_internal.h first) ---------------------------------------------
 #ifdef KWS_INTERNAL
 #include <memory>
+
+// A host vector that travels to the device with a call (one upload, behind the stream's earlier work): the upload reads the host copy
+// when the stream gets there, so the copy is not rewritten before the previous upload has ended (wait), and it lives as long as the bank.
+template <typename T>
+struct BankUpload {
+    std::vector<T> host;
+    T *dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;               // end of the latest upload
+    bool ev_used = false;
+    EI_IMPULSE_ERROR wait()
+    {
+        if (ev_used) HIP_TRY(hipEventSynchronize(ev));
+        ev_used = false;
+        return EI_IMPULSE_OK;
+    }
+    EI_IMPULSE_ERROR grow(size_t n) { return grow_buffer(&dev, &cap, n); }
+    EI_IMPULSE_ERROR send(size_t n, hipStream_t s)
+    {
+        HIP_TRY(hipMemcpyAsync(dev, host.data(), n * sizeof(T), hipMemcpyHostToDevice, s));
+        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(ev, s));
+        ev_used = true;
+        return EI_IMPULSE_OK;
+    }
+    void release()
+    {
+        if (dev) (void)hipFree(dev);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
 
 struct kws_bank {
     std::vector<kws_handle *> m;           // members, in the caller's order
@@ -80,16 +107,8 @@ struct kws_bank {
     size_t feat_cap = 0;
     hipEvent_t ev = nullptr;               // end of the last call's work
     bool ev_used = false;
-    int *d_lists = nullptr;                // a routed call's member lists, one chunk's at a time (uploaded with the call)
-    size_t lists_cap = 0;
-    std::vector<int> h_lists;              // host copy, kept for its capacity
-    hipEvent_t lists_ev = nullptr;         // end of the latest upload of h_lists: it is not rewritten before
-    bool lists_ev_used = false;
-    uint32_t *d_routes = nullptr;          // a routed scan's routes, one per recording that has windows (uploaded with the call)
-    size_t routes_cap = 0;
-    std::vector<uint32_t> h_routes;        // host copy, kept until the upload has ended
-    hipEvent_t routes_ev = nullptr;        // end of the latest upload of h_routes: it is not rewritten before
-    bool routes_ev_used = false;
+    BankUpload<int> lists;                 // a routed call's member lists, one chunk's at a time
+    BankUpload<uint32_t> routes;           // a routed scan's routes, one per recording that has windows
     std::mutex mu;
 };
 
@@ -116,24 +135,21 @@ struct BankUse {
 };
 
 // kws_bank.cpp.  bank_networks: every member's network from the feature matrix feat [B][F] (device); scores[k] + row0 * labels of member k
-// is where its rows go.  bank_window_finish: the finishing step of a chunk of gathered windows for a bank (a kws_slide_finish_fn over a
-// BankWindows): cmvnw (the MFE normalisation) once through the first member, then every member.
-// routes: NULL (every member scores every row), or the routes of the B rows (host): member k then runs over the list of rows that name it.
+// is where its rows go.  routes: NULL (every member scores every row), or the routes of the B rows (host): member k then runs over the
+// list of rows that name it.
 KWS_INTERNAL EI_IMPULSE_ERROR bank_networks(kws_bank *b, const float *feat, size_t B, float *const *scores, size_t row0, hipStream_t s,
                                             const uint32_t *routes = nullptr);
 // The K lists of n routes, packed: member k's at out[at[k]] as [count, rows ascending]; at[K] = the packed size.  One counting pass.
 KWS_INTERNAL void kws_bank_route_lists(const uint32_t *routes, size_t n, size_t K, std::vector<int> &out, size_t *at);
 // the first route of n that names a member >= K: its index, or n
 KWS_INTERNAL size_t kws_bank_route_check(const uint32_t *routes, size_t n, size_t K);
-// The routes of a call's windows, in row order: entry i has n_windows[i] windows, each with the route of its entry -- route[index[i]] (a
-// live push: the session's routes by stream), or route[i] where index is NULL (a recording call: the call's routes by recording).
+// the refusal that follows from it ("<what> <index>: route ... names a member at or above the bank's ..."); routes == NULL: nothing to refuse
+KWS_INTERNAL EI_IMPULSE_ERROR bank_routes_check(const kws_bank *b, const uint32_t *routes, size_t n, const char *what);
+// The routes of a call's windows, in row order (kws_bank_windows.cpp): entry i has n_windows[i] windows, each with the route of its entry --
+// route[index[i]] (a live push: the session's routes by stream), or route[i] where index is NULL (a recording call: the call's routes by
+// recording).
 KWS_INTERNAL void kws_bank_window_routes(const uint32_t *route, const size_t *index, const size_t *n_windows, size_t n, std::vector<uint32_t> &out);
 KWS_INTERNAL bool bank_wants_nothing(const kws_bank *b, float *const *scores, const float *features);
-struct BankWindows {
-    kws_bank *b;
-    float *const *scores;          // [K]: where member k's rows go (NULL: skipped)
-    float *features;               // the caller's [windows][F], or NULL: the bank's shared matrix, a chunk at a time
-    const uint32_t *routes = nullptr;      // [windows] (host), or NULL: every member scores every window
-};
-KWS_INTERNAL EI_IMPULSE_ERROR bank_window_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s);
+// where n feature rows of a call go: the caller's buffer, or (features == NULL) the bank's shared matrix, grown to hold them
+KWS_INTERNAL EI_IMPULSE_ERROR bank_feature_rows(kws_bank *b, float *features, size_t n, float **f);
 #endif

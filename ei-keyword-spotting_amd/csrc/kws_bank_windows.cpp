@@ -1,17 +1,18 @@
 // kws_bank_windows.cpp -- the bank forms of the window pipelines (contract in include/kws/kws.h): recording scans and live streams in
 // continuous mode, live one-shot windows and clips of their own lengths for K models that share one DSP block.
 //   kws_bank_scan_recordings_device         kws_scan_run      (kws_scan.cpp); _routed_: a route per recording
-//   kws_bank_slide_recordings_routed_device kws_slide_run     (kws_slide.cpp) with a route per recording (the unrouted form: kws_bank.cpp)
+//   kws_bank_slide_recordings_device        kws_slide_run     (kws_slide.cpp); _routed_: a route per recording
 //   kws_bank_live_*                         kws_live_run      (kws_live.cpp), on a session of the first member opened without filter state
 //   kws_bank_slide_live_*                   kws_slide_live_run (kws_slide_live.cpp), on a session of the first member
 //   kws_bank_run_classifier_ragged_device   kws_ragged_run    (kws_ragged.cpp) with the network skipped
-// Each is the first member's pipeline runner (kws_internal.h) with the bank's hooks, as kws_bank_slide_recordings_device is kws_slide_run with
-// bank_window_finish: staging, the spectral kernels, gathering, carry and retained rows are the first member's and run ONCE; every chunk of
-// gathered windows ends in bank_window_finish (cmvnw once, then every member's network: kws_bank.cpp), and continuous mode's moving average
-// is ONE launch of kws_bank_maf_kernel for all members (kws_bank_windows_kernels.hip).  What is per member: its scores, its raw scores and,
+// Each is the first member's pipeline runner (kws_internal.h) with the bank's hooks: staging, the spectral kernels, gathering, carry and retained rows are the first member's and run ONCE; every chunk of
+// gathered windows ends in bank_window_finish (cmvnw once, then every member's network: bank_networks of kws_bank.cpp), and continuous mode's
+// moving average is ONE launch of kws_bank_maf_kernel for all members (kws_bank_windows_kernels.hip).  What is per member: its scores, its raw scores and,
 // in a live session, its filters -- sum_k labels_k x (taps + 1) floats per stream, in one allocation of the session.
 // These are the launches of KWS_MODE_EXACT: nothing here reads or writes a member's mode, fast counters or logits tap, and no hook of the
 // bank's asks for the idle finishing call (finish_idle) that the single-model pushes use to reset their counters.
+// A call that takes routes is the entry point; the call without is that call with routes = NULL, and a routed call's hooks are the unrouted
+// call's over a context that also holds the routes.
 #include "kws_internal.h"
 #include "kws_bank.h"
 
@@ -26,6 +27,52 @@ static size_t bank_max_labels(const kws_bank *b)
     size_t c = 0;
     for (const kws_handle *h : b->m) c = std::max(c, h->model.labels.size());
     return c;
+}
+
+void kws_bank_window_routes(const uint32_t *route, const size_t *index, const size_t *n_windows, size_t n, std::vector<uint32_t> &out)
+{
+    out.clear();
+    for (size_t i = 0; i < n; ++i) out.insert(out.end(), n_windows[i], route[index ? index[i] : i]);
+}
+
+// What the finishing step of a chunk of gathered windows needs.  A routed push or recording call adds the routes of its entries (route_by):
+// a window's route is its stream's (a push: the session's routes, by streams[i]) or its recording's (a recording call: the call's routes,
+// index == NULL).  Every entry's window count is on the host before a hook is called (a push: the runner has filled the caller's
+// n_windows; a recording call: the pipeline's count per recording), so the per-window table is built at the first non-empty chunk, before
+// anything of the networks is enqueued, and each chunk is handed its part.
+struct BankWindows {
+    kws_bank *b;
+    float *const *scores;          // [K]: where member k's rows go (NULL: skipped)
+    float *features;               // the caller's [windows][F], or NULL: the bank's shared matrix, a chunk at a time
+    const uint32_t *routes = nullptr;      // [windows] (host), or NULL: every member scores every window
+    const uint32_t *route = nullptr;       // the entries' routes [S] or [R], from which `routes` is built (NULL: `routes` is as given)
+    const size_t *index = nullptr, *n_windows = nullptr;       // the entries' streams (NULL: entry i is recording i) and window counts
+    size_t n = 0;
+    std::vector<uint32_t> table;
+    void route_by(const uint32_t *route_, const size_t *index_, const size_t *n_windows_, size_t n_) { route = route_; index = index_; n_windows = n_windows_; n = n_; }
+};
+
+// the finishing step of a chunk of gathered windows for a bank: cmvnw (the MFE normalisation) once through the first member, then every member
+static EI_IMPULSE_ERROR bank_window_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
+{
+    if (n == 0) return EI_IMPULSE_OK;
+    BankWindows &c = *(BankWindows *)ctx;
+    if (c.route && !c.routes) {
+        kws_bank_window_routes(c.route, c.index, c.n_windows, c.n, c.table);
+        c.routes = c.table.data();
+    }
+    float *f;
+    EI_IMPULSE_ERROR e = bank_feature_rows(c.b, c.features ? c.features + g0 * c.b->m[0]->model.nn_input_frame_size : nullptr, n, &f);
+    if (e) return e;
+    if ((e = cmvn_nn_device(c.b->m[0], win, n, f, nullptr, nullptr, nullptr, nullptr, nullptr, s))) return e;
+    return bank_networks(c.b, f, n, c.scores, g0, s, c.routes ? c.routes + g0 : nullptr);
+}
+
+// the ragged call's finishing step: the DSP route has written the full-stride feature rows; every member's network reads them
+static EI_IMPULSE_ERROR bank_ragged_finish(void *ctx, float *f, size_t B, size_t, hipStream_t s)
+{
+    BankWindows &c = *(BankWindows *)ctx;
+    return bank_networks(c.b, f, B, c.scores, 0, s, c.routes);
 }
 
 // Continuous mode for a bank: the chunks' raw scores go where each member's moving average reads them -- its raw_scores, or its scores
@@ -64,76 +111,20 @@ static EI_IMPULSE_ERROR bank_continuous_maf(void *ctx, const long long *meta, in
         ++M.n;
     }
     if (c.scan_routes) {
-        // the routes travel with the call, behind the stream's earlier work (the host copy is the bank's: it outlives the upload)
+        // the routes travel with the call, behind the stream's earlier work
         if (M.n == 0) return EI_IMPULSE_OK;
         if ((size_t)n != c.scan_routes->size()) return fail(KWS_ERROR_BAD_ARGUMENT, "routed scan: %d recordings with windows, %zu routes", n, c.scan_routes->size());
-        if (b->routes_ev_used) HIP_TRY(hipEventSynchronize(b->routes_ev));
-        b->routes_ev_used = false;
-        b->h_routes = *c.scan_routes;
-        EI_IMPULSE_ERROR e = grow_buffer(&b->d_routes, &b->routes_cap, (size_t)n);
+        EI_IMPULSE_ERROR e = b->routes.wait();
         if (e) return e;
-        HIP_TRY(hipMemcpyAsync(b->d_routes, b->h_routes.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (!b->routes_ev) HIP_TRY(hipEventCreateWithFlags(&b->routes_ev, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(b->routes_ev, s));
-        b->routes_ev_used = true;
-        R.routes = b->d_routes;
-        KWS_LAUNCH_TRY("routed bank moving-average kernel", kws_launch_bank_maf_scan_routed(M, R, meta, n, s));
-        return EI_IMPULSE_OK;
+        b->routes.host = *c.scan_routes;
+        if ((e = b->routes.grow((size_t)n)) || (e = b->routes.send((size_t)n, s))) return e;
+        R.routes = b->routes.dev;
     }
-    if (c.maf && c.d_routes) {
-        KWS_LAUNCH_TRY("routed bank moving-average kernel", kws_launch_bank_maf_live_routed(M, R, meta, n, c.k_full, c.maf, s));
-        return EI_IMPULSE_OK;
-    }
-    KWS_LAUNCH_TRY("bank moving-average kernel", c.maf ? kws_launch_bank_maf_live(M, meta, n, c.k_full, c.maf, s) : kws_launch_bank_maf_scan(M, meta, n, s));
+    const KwsBankMafRoute *routed = R.routes ? &R : nullptr;
+    const int rc = c.maf ? kws_launch_bank_maf_live(M, routed, meta, n, c.k_full, c.maf, s) : kws_launch_bank_maf_scan(M, routed, meta, n, s);
+    if (routed) KWS_LAUNCH_TRY("routed bank moving-average kernel", rc);
+    else KWS_LAUNCH_TRY("bank moving-average kernel", rc);
     return EI_IMPULSE_OK;
-}
-
-// the ragged call's finishing step: the DSP route has written the full-stride feature rows; every member's network reads them
-static EI_IMPULSE_ERROR bank_ragged_finish(void *ctx, float *f, size_t B, size_t, hipStream_t s)
-{
-    BankWindows &c = *(BankWindows *)ctx;
-    return bank_networks(c.b, f, B, c.scores, 0, s, c.routes);
-}
-
-// A routed push or recording call: the routes of its windows, in row order -- a window's route is its stream's (a push: the session's
-// routes, by streams[i]) or its recording's (a recording call: the call's routes, index == NULL).  Every entry's window count is on the host
-// before a hook is called (a push: the runner has filled the caller's n_windows; a recording call: the pipeline's count per recording), so
-// the table is built at the first chunk, before anything of the networks is enqueued; bank_window_finish then hands each chunk its part.
-struct BankWindowRoutes {
-    const uint32_t *route;                 // [S] or [R]
-    const size_t *index, *n_windows;       // the entries' streams (NULL: entry i is recording i) and window counts
-    size_t n;
-    std::vector<uint32_t> windows;
-    bool built = false;
-    const uint32_t *build()
-    {
-        if (!built) {
-            kws_bank_window_routes(route, index, n_windows, n, windows);
-            built = true;
-        }
-        return windows.data();
-    }
-};
-struct BankRoutedWindows {
-    BankWindows w;                         // (first: bank_window_finish reads it)
-    BankWindowRoutes r;
-};
-static EI_IMPULSE_ERROR bank_routed_window_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
-{
-    BankRoutedWindows &c = *(BankRoutedWindows *)ctx;
-    if (n) c.w.routes = c.r.build();
-    return bank_window_finish(&c.w, win, n, g0, s);
-}
-struct BankRoutedContinuous {
-    BankContinuous c;                      // (first: bank_window_finish and bank_continuous_maf read it)
-    BankWindowRoutes r;
-    BankRoutedContinuous(kws_bank *b, float *const *scores, float *const *raw_scores, int k_full, float *maf, const long long *base) : c(b, scores, raw_scores, k_full, maf, base) {}
-};
-static EI_IMPULSE_ERROR bank_routed_continuous_finish(void *ctx, float *win, size_t n, size_t g0, hipStream_t s)
-{
-    BankRoutedContinuous &c = *(BankRoutedContinuous *)ctx;
-    if (n) c.c.w.routes = c.r.build();
-    return bank_window_finish(&c.c, win, n, g0, s);
 }
 
 // the session's routes: every stream to every member until kws_bank_*_route says otherwise
@@ -187,20 +178,8 @@ static void bank_wait(kws_bank *b)
 extern "C" {
 #pragma GCC visibility push(default)
 
-EI_IMPULSE_ERROR kws_bank_scan_recordings_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
-                                                 size_t slice_samples, float *const *scores, float *const *raw_scores, void *stream)
-{
-    if (!b || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (bank_wants_nothing(b, scores, nullptr)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] is NULL");
-    HIP_TRY(hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
-    BankUse use(b, s, true);
-    BankContinuous ctx(b, scores, raw_scores);
-    return kws_scan_run(b->m[0], pcm, offsets, lengths, R, slice_samples, bank_max_labels(b), 0, bank_window_finish, bank_continuous_maf, &ctx, s);
-}
-
-// A recording call's routes, checked; then what its hooks need: every recording's window count and, of the recordings that have windows,
-// their routes in order and the members they name.  every: the recordings that have windows all name every member (the unrouted call).
+// A recording call's routes: every recording's window count and, of the recordings that have windows, their routes in order and the members
+// they name.  every: the recordings that have windows all name every member (the unrouted call).
 struct BankRecordingRoutes {
     std::vector<size_t> n_windows;         // [R]
     std::vector<uint32_t> active;
@@ -215,64 +194,73 @@ struct BankRecordingRoutes {
         every = every && route == (1u << K) - 1u;
     }
 };
-static EI_IMPULSE_ERROR bank_recording_routes_check(const kws_bank *b, const uint32_t *routes, size_t R)
+
+EI_IMPULSE_ERROR kws_bank_scan_recordings_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                 size_t slice_samples, float *const *scores, float *const *raw_scores, void *stream)
 {
-    const size_t bad = kws_bank_route_check(routes, R, b->m.size());
-    if (bad < R) return fail(KWS_ERROR_BAD_ARGUMENT, "recording %zu: route 0x%x names a member at or above the bank's %zu", bad, routes[bad], b->m.size());
-    return EI_IMPULSE_OK;
+    return kws_bank_scan_recordings_routed_device(b, pcm, offsets, lengths, R, nullptr, slice_samples, scores, raw_scores, stream);
 }
 
 EI_IMPULSE_ERROR kws_bank_scan_recordings_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
                                                         const uint32_t *routes, size_t slice_samples, float *const *scores, float *const *raw_scores,
                                                         void *stream)
 {
-    if (!routes) return kws_bank_scan_recordings_device(b, pcm, offsets, lengths, R, slice_samples, scores, raw_scores, stream);
     if (!b || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (bank_wants_nothing(b, scores, nullptr)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] is NULL");
-    if (R > 0 && (!pcm || !offsets || !lengths)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    if (R > 0x3fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "too many recordings");
-    EI_IMPULSE_ERROR e = bank_recording_routes_check(b, routes, R);
-    if (e) return e;
-    ScanLayout L;
-    if ((e = scan_layout(b->m[0], slice_samples, &L))) return e;
     BankRecordingRoutes rr;
-    for (size_t r = 0; r < R; ++r) rr.add(routes[r], L.windows(lengths[r] / slice_samples), b->m.size());
-    if (rr.every) return kws_bank_scan_recordings_device(b, pcm, offsets, lengths, R, slice_samples, scores, raw_scores, stream);
+    if (routes) {
+        // (the routes are sorted out before the pipeline runs, so what it would refuse of the arguments read here is refused here)
+        if (R > 0 && (!pcm || !offsets || !lengths)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+        if (R > 0x3fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "too many recordings");
+        EI_IMPULSE_ERROR e = bank_routes_check(b, routes, R, "recording");
+        if (e) return e;
+        ScanLayout L;
+        if ((e = scan_layout(b->m[0], slice_samples, &L))) return e;
+        for (size_t r = 0; r < R; ++r) rr.add(routes[r], L.windows(lengths[r] / slice_samples), b->m.size());
+    }
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     BankUse use(b, s, true);
-    BankRoutedContinuous ctx(b, scores, raw_scores, 0, nullptr, nullptr);
-    ctx.r = BankWindowRoutes{ routes, nullptr, rr.n_windows.data(), R, {}, false };
-    ctx.c.scan_routes = &rr.active;
-    ctx.c.wanted = rr.wanted;
-    return kws_scan_run(b->m[0], pcm, offsets, lengths, R, slice_samples, bank_max_labels(b), 0, bank_routed_continuous_finish, bank_continuous_maf, &ctx, s);
+    BankContinuous ctx(b, scores, raw_scores);
+    if (!rr.every) {
+        ctx.w.route_by(routes, nullptr, rr.n_windows.data(), R);
+        ctx.scan_routes = &rr.active;
+        ctx.wanted = rr.wanted;
+    }
+    return kws_scan_run(b->m[0], pcm, offsets, lengths, R, slice_samples, bank_max_labels(b), 0, bank_window_finish, bank_continuous_maf, &ctx, s);
+}
+
+EI_IMPULSE_ERROR kws_bank_slide_recordings_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                  size_t hop_samples, int flags, float *const *scores, float *features, void *stream)
+{
+    return kws_bank_slide_recordings_routed_device(b, pcm, offsets, lengths, R, nullptr, hop_samples, flags, scores, features, stream);
 }
 
 EI_IMPULSE_ERROR kws_bank_slide_recordings_routed_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
                                                          const uint32_t *routes, size_t hop_samples, int flags, float *const *scores, float *features,
                                                          void *stream)
 {
-    if (!routes) return kws_bank_slide_recordings_device(b, pcm, offsets, lengths, R, hop_samples, flags, scores, features, stream);
     if (!b || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
-    // (what the unrouted call refuses: a bad hop or flags, NULL lengths, too many windows -- any member's plan)
+    // the window count is any member's; the bound on windows x labels holds for the member with the most labels (a bad hop or flags, NULL
+    // lengths, too many windows: any member's plan refuses them)
     kws_slide_plan_info I;
     EI_IMPULSE_ERROR e;
     for (kws_handle *h : b->m)
         if ((e = kws_slide_plan(h, lengths, R, hop_samples, flags, &I))) return e;
-    if ((e = bank_recording_routes_check(b, routes, R))) return e;
+    if ((e = bank_routes_check(b, routes, R, "recording"))) return e;
     BankRecordingRoutes rr;
-    for (size_t r = 0; r < R; ++r) {
+    for (size_t r = 0; routes && r < R; ++r) {
         size_t W = 0;
         if ((e = kws_slide_window_count(b->m[0], lengths[r], hop_samples, &W))) return e;
         rr.add(routes[r], W, b->m.size());
     }
-    if (rr.every) return kws_bank_slide_recordings_device(b, pcm, offsets, lengths, R, hop_samples, flags, scores, features, stream);
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     BankUse use(b, s, true);
-    BankRoutedWindows ctx{ { b, scores, features }, { routes, nullptr, rr.n_windows.data(), R, {}, false } };
-    return kws_slide_run(b->m[0], pcm, offsets, lengths, R, hop_samples, flags, 0, bank_routed_window_finish, &ctx, s);
+    BankWindows ctx{ b, scores, features };
+    if (!rr.every) ctx.route_by(routes, nullptr, rr.n_windows.data(), R);
+    return kws_slide_run(b->m[0], pcm, offsets, lengths, R, hop_samples, flags, 0, bank_window_finish, &ctx, s);
 }
 
 EI_IMPULSE_ERROR kws_bank_live_create(kws_bank *b, size_t S, size_t slice_samples, kws_bank_live **out)
@@ -377,18 +365,13 @@ EI_IMPULSE_ERROR kws_bank_live_push_device(kws_bank_live *lv, size_t n, const si
     hipStream_t s = (hipStream_t)stream;
     BankUse use(b, s, true, std::move(own));
     float *const none[KWS_BANK_MAX] = { nullptr };
-    EI_IMPULSE_ERROR e;
-    if (!routed) {
-        BankContinuous ctx(b, scores ? scores : none, raw_scores, (int)lv->L.k_full, lv->maf, lv->base.data());
-        e = kws_live_run(lv->core, n, streams, pcm, offsets, lengths, finish, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish,
-                         bank_continuous_maf, &ctx, s);
-    } else {
-        BankRoutedContinuous ctx(b, scores ? scores : none, raw_scores, (int)lv->L.k_full, lv->maf, lv->base.data());
-        ctx.c.d_routes = lv->d_routes;
-        ctx.r = BankWindowRoutes{ lv->routes.route.data(), streams, n_windows, n, {}, false };
-        e = kws_live_run(lv->core, n, streams, pcm, offsets, lengths, finish, scores, n_windows, bank_max_labels(b), 0, 0, bank_routed_continuous_finish,
-                         bank_continuous_maf, &ctx, s);
+    BankContinuous ctx(b, scores ? scores : none, raw_scores, (int)lv->L.k_full, lv->maf, lv->base.data());
+    if (routed) {
+        ctx.d_routes = lv->d_routes;
+        ctx.w.route_by(lv->routes.route.data(), streams, n_windows, n);
     }
+    const EI_IMPULSE_ERROR e = kws_live_run(lv->core, n, streams, pcm, offsets, lengths, finish, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish,
+                                            bank_continuous_maf, &ctx, s);
     if (e) return e;
     // (a stream the push finished starts over: its route may change again)
     for (size_t i = 0; i < n; ++i) lv->pushed[streams[i]] = !(finish && finish[i]);
@@ -455,12 +438,9 @@ EI_IMPULSE_ERROR kws_bank_slide_live_push_device(kws_bank_slide_live *sl, size_t
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     BankUse use(b, s, true);
-    if (!sl->routes.routed) {
-        BankWindows ctx{ b, scores, features };
-        return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish, &ctx, s);
-    }
-    BankRoutedWindows ctx{ { b, scores, features }, { sl->routes.route.data(), streams, n_windows, n, {}, false } };
-    return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores, n_windows, bank_max_labels(b), 0, 0, bank_routed_window_finish, &ctx, s);
+    BankWindows ctx{ b, scores, features };
+    if (sl->routes.routed) ctx.route_by(sl->routes.route.data(), streams, n_windows, n);
+    return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores, n_windows, bank_max_labels(b), 0, 0, bank_window_finish, &ctx, s);
 }
 
 EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_device(kws_bank *b, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B,
@@ -475,20 +455,14 @@ EI_IMPULSE_ERROR kws_bank_run_classifier_ragged_routed_device(kws_bank *b, const
     if (!b || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (bank_wants_nothing(b, scores, features)) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: every scores[k] and features are NULL");
     if (B >= ((size_t)1 << 31)) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
-    if (routes) {
-        const size_t bad = kws_bank_route_check(routes, B, b->m.size());
-        if (bad < B) return fail(KWS_ERROR_BAD_ARGUMENT, "clip %zu: route 0x%x names a member at or above the bank's %zu", bad, routes[bad], b->m.size());
-    }
+    EI_IMPULSE_ERROR e = bank_routes_check(b, routes, B, "clip");
+    if (e) return e;
     if (B == 0) return EI_IMPULSE_OK;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     BankUse use(b, s, true);
-    float *f = features;
-    if (!f) {
-        EI_IMPULSE_ERROR e = grow_buffer(&b->feat, &b->feat_cap, B * (size_t)b->m[0]->model.nn_input_frame_size);
-        if (e) return e;
-        f = b->feat;
-    }
+    float *f;
+    if ((e = bank_feature_rows(b, features, B, &f))) return e;
     BankWindows ctx{ b, scores, features, routes };
     return kws_ragged_run(b->m[0], pcm, offsets, lengths, B, f, nullptr, 0, 0, bank_ragged_finish, &ctx, s);
 }

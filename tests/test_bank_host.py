@@ -47,13 +47,17 @@ def test_bank_symbols_are_exported_and_bound():
 
 @pytest.fixture(scope="module")
 def bank_exe(host_exe, tmp_path_factory):
-    """tests/bank/bank_host_driver.cpp linked with the host objects host_exe built, plus the bank's units and the slide's (whose runner the
-    bank's slide goes through; and the scan's kernel unit, whose count launch the slide shares) compiled the same way.  What this adds goes
-    to a directory of its own: the other host tests link every object they find next to host_exe."""
+    """tests/bank/bank_host_driver.cpp linked with the host objects host_exe built, plus the bank's units and the pipelines' (the bank's slide
+    lives in kws_bank_windows.cpp beside its routed form, and that unit names every pipeline's runner) compiled the same way: the unit list
+    of tests/test_bank_windows_host.py.  What this adds goes to a directory of its own: the other host tests link every object they find
+    next to host_exe."""
     lib_dir = os.path.dirname(host_exe)
     out = str(tmp_path_factory.mktemp("kws_bank_stub"))
     objs = []
-    for unit, ext in (("kws_bank", "cpp"), ("kws_bank_kernels", "hip"), ("kws_slide", "cpp"), ("kws_slide_kernels", "hip"), ("kws_scan_kernels", "hip")):
+    for unit, ext in (("kws_bank", "cpp"), ("kws_bank_kernels", "hip"), ("kws_bank_windows", "cpp"), ("kws_bank_windows_kernels", "hip"),
+                      ("kws_scan", "cpp"), ("kws_scan_kernels", "hip"), ("kws_live", "cpp"), ("kws_live_kernels", "hip"),
+                      ("kws_slide", "cpp"), ("kws_slide_kernels", "hip"), ("kws_slide_live", "cpp"), ("kws_slide_live_kernels", "hip"),
+                      ("kws_ragged", "cpp"), ("kws_ragged_kernels", "hip")):
         o = os.path.join(out, "bank_" + unit + ".o")
         subprocess.check_call([CLANG] + FLAGS + ["-c", "-o", o, os.path.join(CSRC, unit + "." + ext)])
         objs.append(o)
