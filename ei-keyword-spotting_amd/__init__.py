@@ -52,6 +52,9 @@ EXPORTED_SYMBOLS = [
     "kws_bank_slide_live_window_count", "kws_bank_slide_live_push_device",
     "kws_bank_run_classifier_routed_device", "kws_bank_run_classifier_ragged_routed_device", "kws_bank_live_route", "kws_bank_slide_live_route",
     "kws_bank_scan_recordings_routed_device", "kws_bank_slide_recordings_routed_device", "kws_bank_cmvn_inference_routed_device",
+    "kws_pool_create", "kws_pool_destroy", "kws_pool_size", "kws_pool_member", "kws_pool_score_stride", "kws_pool_item_rows",
+    "kws_pool_run_classifier_device", "kws_pool_run_classifier_ragged_device",
+    "kws_pool_live_create", "kws_pool_live_destroy", "kws_pool_live_reset", "kws_pool_live_assign", "kws_pool_live_window_count", "kws_pool_live_push_device",
     "kws_window_frame_count", "kws_run_classifier_ragged_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_slide_live_create", "kws_slide_live_destroy", "kws_slide_live_path", "kws_slide_live_reset", "kws_slide_live_window_count",
@@ -248,6 +251,26 @@ def lib():
             L.kws_bank_scan_recordings_routed_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
             L.kws_bank_slide_recordings_routed_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, i32, vp, vp, vp]
             L.kws_bank_cmvn_inference_routed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        if hasattr(L, "kws_pool_create"):
+            L.kws_pool_create.argtypes = [vp, sz, C.POINTER(vp)]
+            L.kws_pool_destroy.argtypes = [vp]
+            L.kws_pool_destroy.restype = None
+            L.kws_pool_size.argtypes = [vp]
+            L.kws_pool_size.restype = sz
+            L.kws_pool_member.argtypes = [vp, sz]
+            L.kws_pool_member.restype = vp
+            L.kws_pool_score_stride.argtypes = [vp]
+            L.kws_pool_score_stride.restype = sz
+            L.kws_pool_item_rows.argtypes = []
+            L.kws_pool_run_classifier_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+            L.kws_pool_run_classifier_ragged_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp]
+            L.kws_pool_live_create.argtypes = [vp, sz, sz, C.POINTER(vp)]
+            L.kws_pool_live_destroy.argtypes = [vp]
+            L.kws_pool_live_destroy.restype = None
+            L.kws_pool_live_reset.argtypes = [vp, vp, sz]
+            L.kws_pool_live_assign.argtypes = [vp, vp, sz, vp]
+            L.kws_pool_live_window_count.argtypes = [vp, sz, sz, C.c_int, C.POINTER(sz)]
+            L.kws_pool_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.kws_device_malloc.argtypes = [C.POINTER(vp), sz]
         L.kws_device_free.argtypes = [vp]
         L.kws_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -841,6 +864,119 @@ class BankSlideStreams:
         if getattr(self, "sl", None):
             self.L.kws_bank_slide_live_destroy(self.sl)
             self.sl = None
+
+
+POOL_MAX = 4096
+POOL_NONE = 0xffffffff
+
+
+def _members(member, n):
+    """a host sequence of n member indices (POOL_NONE: nobody) as the uint32 array the pool calls read"""
+    r = np.ascontiguousarray(member, np.uint32)
+    assert r.shape == (n,), "one member index per clip or stream"
+    return r
+
+
+class Pool:
+    """Up to POOL_MAX loaded int8 models of the two-block matrix-core shape with an identical DSP block (kws_pool; the contract is in
+    include/kws/kws.h): a call computes the front end once and scores every row with the ONE member it names (member: a host sequence of
+    indices in pool order, POOL_NONE for nobody), always with the exact kernels.  scores_ptr: device, [rows][score_stride] float; row i gets
+    its member's n_labels columns and nothing else is written.  Close the pool before its models."""
+
+    def __init__(self, models):
+        self._models = list(models)
+        self.L = lib()
+        hs = (C.c_void_p * max(len(self._models), 1))(*[m.h for m in self._models])
+        p = C.c_void_p()
+        _check(self.L.kws_pool_create(hs, len(self._models), C.byref(p)))
+        self.p = p
+
+    @property
+    def members(self):
+        """the member models, in the order given"""
+        return list(self._models)
+
+    @property
+    def score_stride(self):
+        """columns of a score row: the most labels any member has"""
+        return int(self.L.kws_pool_score_stride(self.p))
+
+    def __len__(self):
+        return int(self.L.kws_pool_size(self.p))
+
+    def run_classifier_device(self, pcm_ptr, B, member, scores_ptr, features_ptr=None, stream=None):
+        _check(self.L.kws_pool_run_classifier_device(self.p, pcm_ptr, B, _p(_members(member, B)), scores_ptr, features_ptr, stream))
+
+    def run_classifier_ragged_device(self, pcm_ptr, offsets, lengths, member, scores_ptr, features_ptr=None, stream=None):
+        """Model.run_classifier_ragged_device with a member per clip: the DSP route once, features (optional) for every clip"""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        _check(self.L.kws_pool_run_classifier_ragged_device(self.p, pcm_ptr, _p(off), _p(ln), off.size, _p(_members(member, off.size)), scores_ptr, features_ptr,
+                                                            stream))
+
+    def live_streams(self, n_streams, slice_samples=None):
+        """a live session of n_streams streams in continuous mode, each assigned to one member (kws_pool_live_*): see PoolLiveStreams"""
+        return PoolLiveStreams(self, n_streams, slice_samples)
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.kws_pool_destroy(self.p)
+            self.p = None
+
+
+class PoolLiveStreams:
+    """LiveStreams for a pool (kws_pool_live; the contract is in include/kws/kws.h): one session, one copy of every stream's carried samples
+    and retained rows, one moving-average state [S][score_stride][taps + 1].  Every stream starts assigned to nobody (POOL_NONE).  Close the
+    session before its pool."""
+
+    def __init__(self, pool, n_streams, slice_samples=None):
+        self.pool = pool
+        self.L = pool.L
+        self.slice_samples = slice_samples or pool.members[0].clip_samples // 4
+        lv = C.c_void_p()
+        _check(self.L.kws_pool_live_create(pool.p, n_streams, self.slice_samples, C.byref(lv)))
+        self.lv = lv
+        self.n_streams = n_streams
+
+    def assign(self, streams, member):
+        """member[i] (an index in pool order, or POOL_NONE) becomes the member of stream streams[i]; only streams in their start state
+        (created, reset or just finished) may be assigned"""
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_pool_live_assign(self.lv, _p(st), st.size, _p(_members(member, st.size))))
+
+    def window_count(self, stream, n_new, finish=False):
+        """windows a push of n_new samples to `stream` (finishing it if finish) would return now"""
+        n = C.c_size_t()
+        _check(self.L.kws_pool_live_window_count(self.lv, stream, n_new, 1 if finish else 0, C.byref(n)))
+        return n.value
+
+    def push_device(self, pcm_ptr, streams, offsets, lengths, scores_ptr, raw_scores_ptr=None, finish=None, stream=None):
+        """LiveStreams.push_device on rows of score_stride floats: scores (and raw_scores) are [sum][score_stride], device; the rows of an
+        unassigned stream are counted but not written.  Returns n_windows per entry (numpy uint64)."""
+        st = np.ascontiguousarray(streams, np.uint64)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert st.shape == off.shape == ln.shape and st.ndim == 1
+        fin = None if finish is None else np.ascontiguousarray(finish, np.int32)
+        assert fin is None or fin.shape == st.shape
+        nw = np.zeros(st.size, np.uint64)
+        _check(self.L.kws_pool_live_push_device(self.lv, st.size, _p(st), pcm_ptr, _p(off), _p(ln), None if fin is None else _p(fin), scores_ptr,
+                                                raw_scores_ptr, _p(nw), stream))
+        return nw
+
+    def reset(self, streams=None):
+        """streams (host sequence; None: all) back to fresh state; assignments stay"""
+        if streams is None:
+            _check(self.L.kws_pool_live_reset(self.lv, None, 0))
+            return
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_pool_live_reset(self.lv, _p(st), st.size))
+
+    def close(self):
+        if getattr(self, "lv", None):
+            self.L.kws_pool_live_destroy(self.lv)
+            self.lv = None
 
 
 class Comm:

@@ -17,7 +17,8 @@
 #define DIFFER(field, fmt, a, b_)                                                                                                      \
     return fail(KWS_ERROR_BAD_ARGUMENT, "bank member %zu differs from member 0 in " field ": " fmt " against " fmt, k, a, b_)
 
-static EI_IMPULSE_ERROR bank_same_front_end(const kws_handle *a, const kws_handle *h, size_t k)
+// (also the membership rule of a pool: kws_pool.cpp)
+EI_IMPULSE_ERROR bank_same_front_end(const kws_handle *a, const kws_handle *h, size_t k)
 {
     const Model &x = a->model, &y = h->model;
     const DspCfg &p = x.dsp, &q = y.dsp;

@@ -149,6 +149,8 @@ KWS_INTERNAL EI_IMPULSE_ERROR bank_routes_check(const kws_bank *b, const uint32_
 // route[index[i]] (a live push: the session's routes by stream), or route[i] where index is NULL (a recording call: the call's routes by
 // recording).
 KWS_INTERNAL void kws_bank_window_routes(const uint32_t *route, const size_t *index, const size_t *n_windows, size_t n, std::vector<uint32_t> &out);
+// the membership rule: member k (handle h) has member 0's (a) device and front end, field by field; the refusal names the first that differs
+KWS_INTERNAL EI_IMPULSE_ERROR bank_same_front_end(const kws_handle *a, const kws_handle *h, size_t k);
 KWS_INTERNAL bool bank_wants_nothing(const kws_bank *b, float *const *scores, const float *features);
 // where n feature rows of a call go: the caller's buffer, or (features == NULL) the bank's shared matrix, grown to hold them
 KWS_INTERNAL EI_IMPULSE_ERROR bank_feature_rows(kws_bank *b, float *features, size_t n, float **f);

@@ -3,52 +3,14 @@
 // features on load) and kws_bank_quantize_kernel (the int8 input tensors of the other int8 members in one pass over the matrix).  Each has
 // two forms: the unrouted one, where every member takes every row, and the routed one (_routed_kernel), where each member takes its own
 // list of rows.  The two forms of the matrix-core kernel share their set-up (bank_nn_stage) and the quantise-on-load of a feature row
-// (bank_quantize_row); each keeps its own loop over clips and its own LDS declarations, because one body behind both costs
-// kws_bank_nn_mfma_kernel<64> four registers (profiles/bank_route_codeobj.md).
+// (bank_quantize_row), both in kws_bank_nn_dev.h, where the pool's kernel finds them too; each keeps its own loop over clips and its own
+// LDS declarations, because one body behind both costs kws_bank_nn_mfma_kernel<64> four registers (profiles/bank_route_codeobj.md).
 // The network itself is kws_nn_int8_dev.h's, unchanged: a member's scores are those of its own kws_nn_mfma_kernel launch bit for bit.
 #include "kws_device.h"
 
 #include "kws_nn_int8_dev.h"
 #include "kws_bank.h"
-
-// One clip's float feature row src [time][in_c] (F values) -> int8 LDS rows of CP bytes at row (time + pad_left) of act1, quantised with
-// quantize_feature (the expression of every other path) -- no int8 tensor goes through HBM.  inv_c: i / in_c == (i * inv_c) >> 20 for
-// i < n_features <= 4096.  quads: four channels per load and store where the rows allow it (feature rows and activation rows 16- / 4-byte
-// aligned).
-template <int CP>
-__device__ __forceinline__ void bank_quantize_row(const float *__restrict__ src, int8_t *act1, int F, int in_c, int pad_left, unsigned inv_c, bool quads,
-                                                  float in_scale, int in_zp, int lane)
-{
-    if (quads) {
-        for (int i = lane * 4; i < F; i += 64 * 4) {
-            const float4 v = *(const float4 *)(src + i);
-            const int tt = (int)(((unsigned)i * inv_c) >> 20), c = i - tt * in_c;
-            const int w = (quantize_feature(v.x, in_scale, in_zp) & 0xff) | ((quantize_feature(v.y, in_scale, in_zp) & 0xff) << 8) |
-                          ((quantize_feature(v.z, in_scale, in_zp) & 0xff) << 16) | (int)((unsigned)(quantize_feature(v.w, in_scale, in_zp) & 0xff) << 24);
-            *(int *)(act1 + (tt + pad_left) * CP + c) = w;
-        }
-    } else {
-        for (int i = lane; i < F; i += 64) {
-            const int tt = (int)(((unsigned)i * inv_c) >> 20), c = i - tt * in_c;       // i / in_c
-            act1[(tt + pad_left) * CP + c] = quantize_feature(src[i], in_scale, in_zp);
-        }
-    }
-}
-
-// What a workgroup does once before its waves take clips: the member's head and ADD tables into LDS, the wave's padding rows, its context.
-template <int CP>
-__device__ __forceinline__ NnHeadTab bank_nn_stage(const KwsNnPlan &N, unsigned char *s_head, int8_t *s_lut1, int8_t *s_lut2, int8_t *act1, int8_t *act2,
-                                                   NnMfmaCtx<CP> &ctx, int lane)
-{
-    const KwsConvBlock &k1 = N.blk[0], &k2 = N.blk[1];
-    const NnHeadTab head = nn_head_stage(N, s_head);
-    for (int i = threadIdx.x * 4; i < k1.out_c * 256; i += blockDim.x * 4) *(int *)(s_lut1 + i) = *(const int *)(k1.add_lut + i);
-    for (int i = threadIdx.x * 4; i < k2.out_c * 256; i += blockDim.x * 4) *(int *)(s_lut2 + i) = *(const int *)(k2.add_lut + i);
-    nn_mfma_fill_padding<CP>(N, act1, act2, lane);
-    nn_mfma_init<CP>(ctx, N, lane);
-    __syncthreads();
-    return head;
-}
+#include "kws_bank_nn_dev.h"
 
 // ---------------------------------------------------------------------------------------------------------
 //  Grid (clip tiles, member): blockIdx.y picks the member's record in HBM (its plan and input quantisation; uniform over the
@@ -60,14 +22,6 @@ __device__ __forceinline__ NnHeadTab bank_nn_stage(const KwsNnPlan &N, unsigned 
 //    routed     the same grid, sized by the longest list of the launch; slot blockIdx.y walks lists.list[blockIdx.y] -- [0] = how many,
 //               then the clips, ascending -- instead: a wave's position in the list is uniform, so the clip index is one scalar load
 // ---------------------------------------------------------------------------------------------------------
-#define KWS_BANK_NN_LDS(CP)                                                                  \
-    __shared__ __attribute__((aligned(16))) int8_t s_lut1[32 * 256];                         \
-    __shared__ __attribute__((aligned(16))) int8_t s_lut2[16 * 256];                         \
-    __shared__ __attribute__((aligned(16))) int8_t s_act1[KWS_NN_WAVES][KWS_A1_ROWS * CP];   \
-    __shared__ __attribute__((aligned(16))) int8_t s_act2[KWS_NN_WAVES][KWS_A2_ROWS * 32];   \
-    __shared__ int s_vec[KWS_NN_WAVES][64];                                                  \
-    __shared__ __attribute__((aligned(16))) unsigned char s_head[KWS_HEAD_BYTES]
-
 template <int CP>
 __global__ __launch_bounds__(KWS_WAVE * KWS_NN_WAVES) void kws_bank_nn_mfma_kernel(const KwsBankRec *__restrict__ recs, KwsBankOut out,
                                                                                    const float *__restrict__ features, int n_clips)

@@ -703,6 +703,77 @@ EI_IMPULSE_ERROR kws_bank_cmvn_inference_routed_device(kws_bank *b, const float 
 EI_IMPULSE_ERROR kws_bank_live_route(kws_bank_live *lv, const size_t *streams, size_t n, const uint32_t *routes);
 EI_IMPULSE_ERROR kws_bank_slide_live_route(kws_bank_slide_live *sl, const size_t *streams, size_t n, const uint32_t *routes);
 
+/* ---- pools: hundreds of int8 models behind one DSP block, ONE member per row ----------------------------------------------------------
+ * A bank serves any subset of at most 16 members of any graph family per row, with one score buffer and one filter state per member.  A
+ * pool is its narrow sibling for a service with hundreds of tenants, each with its own keywords trained on the same architecture: up to
+ * KWS_POOL_MAX members that share one DSP block, every row (clip or live stream) scored by the ONE member it names, all scores in ONE
+ * matrix.  The front end runs once per call, every member's network runs in ONE launch whatever K, and a live session keeps one filter
+ * state for all members.
+ * Membership.  1 <= K <= KWS_POOL_MAX handles (the range is checked before a member is read), none NULL, none twice, member k equal to
+ * member 0 in everything a bank requires (device, DSP block kind and configuration, sampling frequency, raw_sample_count; the bank's rule
+ * with the bank's messages): KWS_ERROR_BAD_ARGUMENT otherwise.  Every member must be an int8 graph of the two-block matrix-core shape --
+ * two CONV_2D(1-D) + MAX_POOL blocks, FULLY_CONNECTED, SOFTMAX: the stock graph, the shape of both shipped models, the graphs for which
+ * kws_nn_kernel_name says "kws_nn_mfma_kernel".  A float32 member, or an int8 member of another family (depthwise, dense stack, strided,
+ * 2-D, residual): KWS_ERROR_UNSUPPORTED_MODEL, kws_last_error names the member and the reason.  Label counts may differ:
+ * kws_pool_score_stride is the largest.  kws_pool_create changes no member; a member stays usable on its own.
+ * Member index.  A uint32_t per clip, or per stream of a live session: the member's index in pool order, or KWS_POOL_NONE.  `member`
+ * arrays are HOST data.  An index at or above kws_pool_size(p) that is not KWS_POOL_NONE: KWS_ERROR_BAD_ARGUMENT before anything is
+ * enqueued; kws_last_error names the first such row and its value.
+ * Output.  scores is [rows][stride] float, device, stride = kws_pool_score_stride(p).  Row i gets, in columns 0 .. labels - 1 of its member,
+ * the bits of that member's own KWS_MODE_EXACT call on row i (int8: bit-exact with the reference).  Nothing else of `scores` is written:
+ * not the columns at or above the member's label count, not a row that names KWS_POOL_NONE.  `features` ([rows][feature_count], optional)
+ * is written for every row, KWS_POOL_NONE rows included, with the bits of the single-model call.
+ * Locks and lifetimes.  The pool copies each member's plan record to device memory at creation (1 072 bytes per member, and 4 for its label
+ * count); after that it reads only the members' immutable device weights.  A pool call is a call on the pool and on the FIRST member only,
+ * whose front end and scratch it uses, for the rules at the top of this file: it holds those two locks and takes no other member's lock or
+ * scratch bracket, so calls on the other members run beside it.  Calls on one pool are serialised.  Members outlive the pool; sessions are
+ * destroyed before their pool (kws_pool_destroy waits for the pool's enqueued work).
+ * Mode.  A pool call always runs the exact kernels, as bank and ragged calls do: no member's mode, fast counter or logits tap is read or
+ * written.
+ * Launches and memory.  The rows' members become one ascending row list per named member (one counting and one filling pass on the host);
+ * the lists are cut into work items of at most kws_pool_item_rows() rows, one workgroup each; items and lists go up in one upload with the
+ * call: 16 bytes per item + 4 per named row of pool-owned device memory, grown on demand (growing synchronises the device), like the shared
+ * feature matrix of calls without `features`.  A member nobody names costs nothing; rows that all name KWS_POOL_NONE launch no network.
+ *   kws_pool_run_classifier_device         run_classifier() for B clips, clip i by member[i].  scores and features both NULL, NULL pool, NULL
+ *                     pcm or member with B > 0, B >= 2^31: KWS_ERROR_BAD_ARGUMENT.  B = 0: EI_IMPULSE_OK, nothing written.
+ *   kws_pool_run_classifier_ragged_device  the same for clips of their own lengths (kws_run_classifier_ragged_device's contract: the rows
+ *                     are the bits of the member's own ragged call); whatever that call refuses is refused with its code.
+ *   kws_pool_live_*   kws_live_* for a pool: one session of S streams, one copy of every stream's carried samples and retained rows, filter
+ *                     state [S][stride][taps + 1] floats in total.  Each stream is assigned to one member or to none; a fresh session assigns
+ *                     every stream to KWS_POOL_NONE.  kws_pool_live_assign(lv, streams, n, member) sets the members of n streams (HOST
+ *                     arrays).  A stream's moving-average filter must see every window through one member, so a stream may be assigned only
+ *                     in its start state: after create, kws_pool_live_reset or the push that finished it, before anything else was pushed
+ *                     to it; otherwise -- or for a stream out of range or named twice, or a bad index -- KWS_ERROR_BAD_ARGUMENT, the first
+ *                     offending entry is named, nothing changes.  Reset keeps assignments.  The call waits for the pool's enqueued work.
+ *                     kws_pool_live_push_device has kws_live_push_device's arguments; scores and raw_scores (optional) are
+ *                     [windows of the push][stride], entry after entry.  An assigned stream's rows, filtered and raw, are the bits of its
+ *                     member's own kws_live_* session fed the same pushes.  A push to an unassigned stream advances its carry and counts
+ *                     its windows in n_windows, but writes no row and touches no filter state.  The moving average is ONE launch per push.
+ * Not built: float32 and other-family members, recording scans and slides, live one-shot windows, the cepstra-in call, device-resident
+ * member arrays, KWS_MODE_FAST. */
+#define KWS_POOL_MAX 4096
+#define KWS_POOL_NONE 0xffffffffu
+typedef struct kws_pool kws_pool;
+typedef struct kws_pool_live kws_pool_live;
+EI_IMPULSE_ERROR kws_pool_create(kws_handle *const *members, size_t K, kws_pool **out);
+void kws_pool_destroy(kws_pool *p);
+size_t kws_pool_size(const kws_pool *p);
+kws_handle *kws_pool_member(const kws_pool *p, size_t k);                  /* NULL for k >= K */
+size_t kws_pool_score_stride(const kws_pool *p);                           /* the most labels any member has */
+int kws_pool_item_rows(void);                                              /* rows of one work item at most (diagnostics; tests place lists at its edges) */
+EI_IMPULSE_ERROR kws_pool_run_classifier_device(kws_pool *p, const int16_t *pcm, size_t B, const uint32_t *member, float *scores,
+                                                float *features, void *stream);
+EI_IMPULSE_ERROR kws_pool_run_classifier_ragged_device(kws_pool *p, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t B,
+                                                       const uint32_t *member, float *scores, float *features, void *stream);
+EI_IMPULSE_ERROR kws_pool_live_create(kws_pool *p, size_t S, size_t slice_samples, kws_pool_live **out);
+void kws_pool_live_destroy(kws_pool_live *lv);
+EI_IMPULSE_ERROR kws_pool_live_reset(kws_pool_live *lv, const size_t *streams, size_t n);
+EI_IMPULSE_ERROR kws_pool_live_assign(kws_pool_live *lv, const size_t *streams, size_t n, const uint32_t *member);
+EI_IMPULSE_ERROR kws_pool_live_window_count(const kws_pool_live *lv, size_t stream, size_t n_new, int finish, size_t *n_windows);
+EI_IMPULSE_ERROR kws_pool_live_push_device(kws_pool_live *lv, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets,
+                                           const size_t *lengths, const int *finish, float *scores, float *raw_scores, size_t *n_windows,
+                                           void *stream);
+
 /* ---- multi-GPU: clips shard contiguously over the GPUs of one node (rank r owns clips [r*B, (r+1)*B)), tables are
  * replicated, nothing is exchanged inside the pipeline; the one collective is the all-gather of the per-clip scores over xGMI.
  * It goes through RCCL's C API (librccl is opened on first use: single-GPU applications do not need it).  One process per GPU:
