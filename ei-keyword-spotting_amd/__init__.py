@@ -55,6 +55,9 @@ EXPORTED_SYMBOLS = [
     "kws_pool_create", "kws_pool_destroy", "kws_pool_size", "kws_pool_member", "kws_pool_score_stride", "kws_pool_item_rows",
     "kws_pool_run_classifier_device", "kws_pool_run_classifier_ragged_device",
     "kws_pool_live_create", "kws_pool_live_destroy", "kws_pool_live_reset", "kws_pool_live_assign", "kws_pool_live_window_count", "kws_pool_live_push_device",
+    "kws_pool_scan_recordings_device", "kws_pool_slide_recordings_device", "kws_pool_cmvn_inference_device",
+    "kws_pool_slide_live_create", "kws_pool_slide_live_destroy", "kws_pool_slide_live_path", "kws_pool_slide_live_reset", "kws_pool_slide_live_assign",
+    "kws_pool_slide_live_window_count", "kws_pool_slide_live_push_device",
     "kws_window_frame_count", "kws_run_classifier_ragged_device",
     "kws_live_create", "kws_live_destroy", "kws_live_reset", "kws_live_window_count", "kws_live_push_device",
     "kws_slide_live_create", "kws_slide_live_destroy", "kws_slide_live_path", "kws_slide_live_reset", "kws_slide_live_window_count",
@@ -271,6 +274,18 @@ def lib():
             L.kws_pool_live_assign.argtypes = [vp, vp, sz, vp]
             L.kws_pool_live_window_count.argtypes = [vp, sz, sz, C.c_int, C.POINTER(sz)]
             L.kws_pool_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "kws_pool_scan_recordings_device"):
+            L.kws_pool_scan_recordings_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
+            L.kws_pool_slide_recordings_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, C.c_int, vp, vp, vp]
+            L.kws_pool_cmvn_inference_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+            L.kws_pool_slide_live_create.argtypes = [vp, sz, sz, C.c_int, C.POINTER(vp)]
+            L.kws_pool_slide_live_destroy.argtypes = [vp]
+            L.kws_pool_slide_live_destroy.restype = None
+            L.kws_pool_slide_live_path.argtypes = [vp]
+            L.kws_pool_slide_live_reset.argtypes = [vp, vp, sz]
+            L.kws_pool_slide_live_assign.argtypes = [vp, vp, sz, vp]
+            L.kws_pool_slide_live_window_count.argtypes = [vp, sz, sz, C.POINTER(sz)]
+            L.kws_pool_slide_live_push_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         L.kws_device_malloc.argtypes = [C.POINTER(vp), sz]
         L.kws_device_free.argtypes = [vp]
         L.kws_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -919,6 +934,33 @@ class Pool:
         """a live session of n_streams streams in continuous mode, each assigned to one member (kws_pool_live_*): see PoolLiveStreams"""
         return PoolLiveStreams(self, n_streams, slice_samples)
 
+    def scan_recordings_device(self, pcm_ptr, offsets, lengths, member, scores_ptr, raw_scores_ptr=None, slice_samples=None, stream=None):
+        """Model.scan_recordings_device with a member per recording (POOL_NONE: its windows keep their rows, unwritten): scores (and
+        raw_scores) are [windows of the call][score_stride], device; without raw_scores the moving average filters in place.  The front end
+        runs for every recording, the ones that name nobody included."""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        _check(self.L.kws_pool_scan_recordings_device(self.p, pcm_ptr, _p(off), _p(ln), off.size, _p(_members(member, off.size)),
+                                                      slice_samples or self._models[0].clip_samples // 4, scores_ptr, raw_scores_ptr, stream))
+
+    def slide_recordings_device(self, pcm_ptr, offsets, lengths, member, hop_samples, scores_ptr, features_ptr=None, flags=SLIDE_AUTO, stream=None):
+        """Model.slide_recordings_device with a member per recording: scores are [windows of the call][score_stride], features (optional)
+        [windows][n_features] for every window"""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert off.shape == ln.shape and off.ndim == 1
+        _check(self.L.kws_pool_slide_recordings_device(self.p, pcm_ptr, _p(off), _p(ln), off.size, _p(_members(member, off.size)), hop_samples, flags,
+                                                       scores_ptr, features_ptr, stream))
+
+    def cmvn_inference_device(self, mfcc_ptr, B, member, scores_ptr, features_ptr=None, stream=None):
+        """Model.cmvn_inference_batch_device with a member per row of cepstra"""
+        _check(self.L.kws_pool_cmvn_inference_device(self.p, mfcc_ptr, B, _p(_members(member, B)), scores_ptr, features_ptr, stream))
+
+    def slide_streams(self, n_streams, hop_samples, flags=SLIDE_AUTO):
+        """a live session of n_streams streams of one-shot windows, each assigned to one member (kws_pool_slide_live_*): see PoolSlideStreams"""
+        return PoolSlideStreams(self, n_streams, hop_samples, flags)
+
     def close(self):
         if getattr(self, "p", None):
             self.L.kws_pool_destroy(self.p)
@@ -977,6 +1019,60 @@ class PoolLiveStreams:
         if getattr(self, "lv", None):
             self.L.kws_pool_live_destroy(self.lv)
             self.lv = None
+
+
+class PoolSlideStreams:
+    """SlideStreams for a pool (kws_pool_slide_live; the contract is in include/kws/kws.h): one session, one copy of every stream's carried
+    samples and retained rows, nothing per member.  Every stream starts assigned to nobody (POOL_NONE).  Close the session before its pool."""
+
+    def __init__(self, pool, n_streams, hop_samples, flags=SLIDE_AUTO):
+        self.pool = pool
+        self.L = pool.L
+        self.hop_samples = hop_samples
+        sl = C.c_void_p()
+        _check(self.L.kws_pool_slide_live_create(pool.p, n_streams, hop_samples, flags, C.byref(sl)))
+        self.sl = sl
+        self.n_streams = n_streams
+
+    @property
+    def path(self):
+        """SLIDE_DIRECT or SLIDE_SHARED: what the session's pushes run"""
+        return int(self.L.kws_pool_slide_live_path(self.sl))
+
+    def assign(self, streams, member):
+        """member[i] (an index in pool order, or POOL_NONE) becomes the member of stream streams[i], from the next push on"""
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_pool_slide_live_assign(self.sl, _p(st), st.size, _p(_members(member, st.size))))
+
+    def window_count(self, stream, n_new):
+        """windows a push of n_new samples to `stream` would return now"""
+        n = C.c_size_t()
+        _check(self.L.kws_pool_slide_live_window_count(self.sl, stream, n_new, C.byref(n)))
+        return n.value
+
+    def push_device(self, pcm_ptr, streams, offsets, lengths, scores_ptr, features_ptr=None, stream=None):
+        """SlideStreams.push_device on rows of score_stride floats: scores are [sum][score_stride], device; the rows of an unassigned stream
+        are counted but not written; features (optional) are written for every window.  Returns n_windows per entry (numpy uint64)."""
+        st = np.ascontiguousarray(streams, np.uint64)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint64)
+        assert st.shape == off.shape == ln.shape and st.ndim == 1
+        nw = np.zeros(st.size, np.uint64)
+        _check(self.L.kws_pool_slide_live_push_device(self.sl, st.size, _p(st), pcm_ptr, _p(off), _p(ln), scores_ptr, features_ptr, _p(nw), stream))
+        return nw
+
+    def reset(self, streams=None):
+        """streams (host sequence; None: all) back to fresh state; assignments stay"""
+        if streams is None:
+            _check(self.L.kws_pool_slide_live_reset(self.sl, None, 0))
+            return
+        st = np.ascontiguousarray(streams, np.uint64)
+        _check(self.L.kws_pool_slide_live_reset(self.sl, _p(st), st.size))
+
+    def close(self):
+        if getattr(self, "sl", None):
+            self.L.kws_pool_slide_live_destroy(self.sl)
+            self.sl = None
 
 
 class Comm:

@@ -8,6 +8,10 @@
 //   scores         ONE matrix [rows][stride], stride = the most labels any member has; row i gets its member's labels, nothing else is written
 //   live sessions  one filter state [S][stride][taps + 1] and one moving-average launch per push (kws_pool_maf_live_kernel); the streams'
 //                  members are the session's, on the host and in HBM
+//   recordings     kws_scan_run and kws_slide_run with the same finishing hook: a window's member is its recording's; the scan's moving
+//                  average is one launch of kws_pool_maf_scan_kernel, the members of the recordings that have windows going up with the call
+//   one-shot live  kws_slide_live_run on a session of the first member; no state per member, so a stream's member is host data only
+//   cepstra in     cmvn_nn_device once, then pool_networks
 // A pool call is a call on the pool and on the FIRST member only: it takes that member's lock and scratch bracket and nobody else's -- of
 // the other members it reads only the immutable device weights their records point to.  These are the launches of KWS_MODE_EXACT: nothing
 // here reads or writes a member's mode, fast counters or logits tap.
@@ -59,10 +63,10 @@ size_t kws_pool_member_check(const uint32_t *member, size_t n, size_t K)
     return n;
 }
 
-void kws_pool_window_members(const uint32_t *assign, const size_t *streams, const size_t *n_windows, size_t n, std::vector<uint32_t> &out)
+void kws_pool_window_members(const uint32_t *assign, const size_t *index, const size_t *n_windows, size_t n, std::vector<uint32_t> &out)
 {
     out.clear();
-    for (size_t i = 0; i < n; ++i) out.insert(out.end(), n_windows[i], assign[streams[i]]);
+    for (size_t i = 0; i < n; ++i) out.insert(out.end(), n_windows[i], assign[index ? index[i] : i]);
 }
 
 // the refusal of a call whose rows name a member the pool does not have; what: the call's word for a row
@@ -126,18 +130,21 @@ static void pool_wait(kws_pool *p)
     if (p->ev && p->ev_used) (void)hipEventSynchronize(p->ev);
 }
 
-// What the finishing step of a call's rows needs: the rows' members (host), or -- a live push -- the session's members by stream, from
-// which the per-window table is built at the first non-empty chunk: every entry's window count is on the host before a hook is called (the
-// runner has filled the caller's n_windows), so nothing of the networks is enqueued before it, and each chunk is handed its part.
+// What the finishing step of a call's rows needs: the rows' members (host), or the members of the call's entries -- a live push: the
+// session's members by stream; a recording call: the call's members by recording (streams == NULL) -- from which the per-window table is
+// built at the first non-empty chunk: every entry's window count is on the host before a hook is called (a push: the runner has filled
+// the caller's n_windows; a recording call: counted before the runner starts), so nothing of the networks is enqueued before it, and each
+// chunk is handed its part.
 struct PoolWindows {
     kws_pool *p;
     float *scores;                         // [rows][stride] (NULL: no network)
     float *features;                       // the caller's [rows][F], or NULL: the pool's shared matrix, a chunk at a time
     const uint32_t *member = nullptr;      // [rows] (host)
-    const uint32_t *assign = nullptr;      // a live push: the session's members [S] ...
-    const size_t *streams = nullptr, *n_windows = nullptr;     // ... and the entries' streams and window counts
+    const uint32_t *assign = nullptr;      // the entries' members: a live push's session [S], a recording call's [R] ...
+    const size_t *streams = nullptr, *n_windows = nullptr;     // ... and the entries' streams (NULL: entry i is recording i) and window counts
     size_t n = 0;
     std::vector<uint32_t> table;
+    void by_entry(const uint32_t *assign_, const size_t *streams_, const size_t *n_windows_, size_t n_) { assign = assign_; streams = streams_; n_windows = n_windows_; n = n_; }
 };
 
 // the finishing step of a chunk of gathered windows: cmvnw (the MFE normalisation) once through the first member, then the windows' members
@@ -180,7 +187,48 @@ static EI_IMPULSE_ERROR pool_continuous_maf(void *ctx, const long long *meta, in
     return EI_IMPULSE_OK;
 }
 
-// (the session: the pool, the first member's session -- carry, retained rows, mirrors, per-push scratch: ONE copy -- and the streams' members)
+// A recording call's members: every recording's window count and, of the recordings that have windows, their members in order (what
+// the scan's moving average reads, in the order of the runner's wbase); named: one of those is not KWS_POOL_NONE.
+struct PoolRecordings {
+    std::vector<size_t> n_windows;         // [R]
+    std::vector<uint32_t> active;
+    bool named = false;
+    void add(uint32_t member, size_t W)
+    {
+        n_windows.push_back(W);
+        if (!W) return;
+        active.push_back(member);
+        named = named || member != KWS_POOL_NONE;
+    }
+};
+
+// The scan: raw scores as in a live push; the filter step is one launch over (recording with windows, column) pairs, a fresh filter each.
+// The members travel with the call, behind the stream's earlier work, in an upload of their own (the table's host copy is the last chunk's).
+struct PoolScan {
+    PoolWindows w;                         // (first: pool_window_finish reads it)
+    float *scores;
+    const PoolRecordings *rec;
+};
+static EI_IMPULSE_ERROR pool_scan_maf(void *ctx, const long long *wbase, int n, hipStream_t s)
+{
+    PoolScan &c = *(PoolScan *)ctx;
+    kws_pool *p = c.w.p;
+    if (!c.rec->named) return EI_IMPULSE_OK;
+    if ((size_t)n != c.rec->active.size()) return fail(KWS_ERROR_BAD_ARGUMENT, "pool scan: %d recordings with windows, %zu members", n, c.rec->active.size());
+    EI_IMPULSE_ERROR e = p->scan_members.wait();
+    if (e) return e;
+    p->scan_members.host = c.rec->active;
+    if ((e = p->scan_members.grow((size_t)n)) || (e = p->scan_members.send((size_t)n, s))) return e;
+    KWS_LAUNCH_TRY("pool scan moving-average kernel", kws_launch_pool_maf_scan(c.w.scores, c.scores, wbase, n, (int)p->stride, p->scan_members.dev, p->d_labels, s));
+    return EI_IMPULSE_OK;
+}
+
+// (the sessions: the pool, the first member's session -- carry, retained rows, mirrors, per-push scratch: ONE copy -- and the streams' members)
+struct kws_pool_slide_live {
+    kws_pool *p = nullptr;
+    kws_slide_live *core = nullptr;
+    std::vector<uint32_t> assign;          // [S]: the stream's member, or KWS_POOL_NONE (host only: nothing per member is kept)
+};
 struct kws_pool_live {
     kws_pool *p = nullptr;
     kws_live *core = nullptr;
@@ -191,13 +239,14 @@ struct kws_pool_live {
     std::vector<char> pushed;              // [S]: the stream has been pushed to since its start (create, reset or finish): its member is fixed
 };
 
-static EI_IMPULSE_ERROR pool_call_checks(const kws_pool *p, const void *pcm, size_t B, const uint32_t *member, const float *scores, const float *features, bool need_pcm)
+static EI_IMPULSE_ERROR pool_call_checks(const kws_pool *p, const void *pcm, size_t B, const uint32_t *member, const float *scores, const float *features, bool need_pcm,
+                                         const char *what = "clip")
 {
     if (!p) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
     if (!scores && !features) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: scores and features are NULL");
     if (B >= ((size_t)1 << 31)) return fail(KWS_ERROR_BAD_ARGUMENT, "batch too large");
     if (B > 0 && (!member || (need_pcm && !pcm))) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
-    return pool_members_check(p, member, B, "clip");
+    return pool_members_check(p, member, B, what);
 }
 
 extern "C" {
@@ -245,7 +294,10 @@ EI_IMPULSE_ERROR kws_pool_create(kws_handle *const *members, size_t K, kws_pool 
         rec[k].in_scale = members[k]->nn.in_scale;
         rec[k].in_zp = members[k]->nn.in_zp;
         labels[k] = (int)members[k]->model.labels.size();
-        p->stride = std::max(p->stride, members[k]->model.labels.size());
+        if (members[k]->model.labels.size() > p->stride) {
+            p->stride = members[k]->model.labels.size();
+            p->most = k;
+        }
     }
     hipError_t he = hipMalloc((void **)&p->d_rec, K * sizeof(KwsBankRec));
     if (he == hipSuccess) he = hipMalloc((void **)&p->d_labels, K * sizeof(int));
@@ -273,6 +325,7 @@ void kws_pool_destroy(kws_pool *p)
     if (p->d_labels) (void)hipFree(p->d_labels);
     if (p->feat) (void)hipFree(p->feat);
     p->table.release();
+    p->scan_members.release();
     delete p;
 }
 
@@ -407,16 +460,149 @@ EI_IMPULSE_ERROR kws_pool_live_push_device(kws_pool_live *lv, size_t n, const si
     hipStream_t s = (hipStream_t)stream;
     PoolUse use(p, s, false, std::move(own));
     PoolContinuous ctx{ { p, raw_scores ? raw_scores : scores, nullptr }, scores, (int)lv->L.k_full, lv->maf, lv->d_assign };
-    ctx.w.assign = lv->assign.data();
-    ctx.w.streams = streams;
-    ctx.w.n_windows = n_windows;
-    ctx.w.n = n;
+    ctx.w.by_entry(lv->assign.data(), streams, n_windows, n);
     const EI_IMPULSE_ERROR e = kws_live_run(lv->core, n, streams, pcm, offsets, lengths, finish, scores, n_windows, p->stride, 0, 0, pool_window_finish,
                                             pool_continuous_maf, &ctx, s);
     if (e) return e;
     // (a stream the push finished starts over: its member may change again)
     for (size_t i = 0; i < n; ++i) lv->pushed[streams[i]] = !(finish && finish[i]);
     return EI_IMPULSE_OK;
+}
+
+EI_IMPULSE_ERROR kws_pool_cmvn_inference_device(kws_pool *p, const float *mfcc, size_t B, const uint32_t *member, float *scores, float *features, void *stream)
+{
+    EI_IMPULSE_ERROR e = pool_call_checks(p, mfcc, B, member, scores, features, true, "row");
+    if (e) return e;
+    if (B == 0) return EI_IMPULSE_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t s = (hipStream_t)stream;
+    PoolUse use(p, s, true);
+    float *f;
+    if ((e = pool_feature_rows(p, features, B, &f))) return e;
+    if ((e = ensure_scratch(p->m[0], B))) return e;
+    if ((e = cmvn_nn_device(p->m[0], mfcc, B, f, nullptr, nullptr, nullptr, nullptr, nullptr, s))) return e;
+    return pool_networks(p, f, B, member, scores, 0, s);
+}
+
+EI_IMPULSE_ERROR kws_pool_scan_recordings_device(kws_pool *p, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R, const uint32_t *member,
+                                                 size_t slice_samples, float *scores, float *raw_scores, void *stream)
+{
+    if (!p || !scores) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    // (the members are sorted out before the pipeline runs, so what it would refuse of the arguments read here is refused here)
+    if (R > 0 && (!pcm || !offsets || !lengths || !member)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (R > 0x3fffffff) return fail(KWS_ERROR_BAD_ARGUMENT, "too many recordings");
+    EI_IMPULSE_ERROR e = pool_members_check(p, member, R, "recording");
+    if (e) return e;
+    ScanLayout L;
+    if ((e = scan_layout(p->m[0], slice_samples, &L))) return e;
+    PoolRecordings rec;
+    for (size_t r = 0; r < R; ++r) rec.add(member[r], L.windows(lengths[r] / slice_samples));
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t s = (hipStream_t)stream;
+    PoolUse use(p, s, false);
+    PoolScan ctx{ { p, raw_scores ? raw_scores : scores, nullptr }, scores, &rec };
+    ctx.w.by_entry(member, nullptr, rec.n_windows.data(), R);
+    return kws_scan_run(p->m[0], pcm, offsets, lengths, R, slice_samples, p->stride, 0, pool_window_finish, pool_scan_maf, &ctx, s);
+}
+
+EI_IMPULSE_ERROR kws_pool_slide_recordings_device(kws_pool *p, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R, const uint32_t *member,
+                                                  size_t hop_samples, int flags, float *scores, float *features, void *stream)
+{
+    if (!p) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (!scores && !features) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: scores and features are NULL");
+    // the window count is any member's; the bound on windows x labels holds at the stride, the label count of member `most` (a bad hop or
+    // flags, NULL lengths, too many windows: its plan refuses them)
+    kws_slide_plan_info I;
+    EI_IMPULSE_ERROR e = kws_slide_plan(p->m[p->most], lengths, R, hop_samples, flags, &I);
+    if (e) return e;
+    if (R > 0 && (!pcm || !offsets || !member)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if ((e = pool_members_check(p, member, R, "recording"))) return e;
+    PoolRecordings rec;
+    for (size_t r = 0; r < R; ++r) {
+        size_t W = 0;
+        if ((e = kws_slide_window_count(p->m[0], lengths[r], hop_samples, &W))) return e;
+        rec.add(member[r], W);
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t s = (hipStream_t)stream;
+    PoolUse use(p, s, false);
+    PoolWindows ctx{ p, scores, features };
+    ctx.by_entry(member, nullptr, rec.n_windows.data(), R);
+    return kws_slide_run(p->m[0], pcm, offsets, lengths, R, hop_samples, flags, 0, pool_window_finish, &ctx, s);
+}
+
+EI_IMPULSE_ERROR kws_pool_slide_live_create(kws_pool *p, size_t S, size_t hop_samples, int flags, kws_pool_slide_live **out)
+{
+    if (out) *out = nullptr;
+    if (!p || !out) return fail(KWS_ERROR_BAD_ARGUMENT, "bad argument");
+    std::unique_ptr<kws_pool_slide_live> sl(new kws_pool_slide_live());
+    sl->p = p;
+    EI_IMPULSE_ERROR e = kws_slide_live_create(p->m[0], S, hop_samples, flags, &sl->core);
+    if (e) return e;
+    sl->assign.assign(S, KWS_POOL_NONE);
+    *out = sl.release();
+    return EI_IMPULSE_OK;
+}
+
+void kws_pool_slide_live_destroy(kws_pool_slide_live *sl)
+{
+    if (!sl) return;
+    {
+        std::lock_guard<std::mutex> lk(sl->p->mu);
+        pool_wait(sl->p);
+        kws_slide_live_destroy(sl->core);
+    }
+    delete sl;
+}
+
+int kws_pool_slide_live_path(const kws_pool_slide_live *sl) { return sl ? kws_slide_live_path(sl->core) : 0; }
+
+EI_IMPULSE_ERROR kws_pool_slide_live_reset(kws_pool_slide_live *sl, const size_t *streams, size_t n)
+{
+    if (!sl) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lk(sl->p->mu);
+    return kws_slide_live_reset(sl->core, streams, n);          // (members stay)
+}
+
+EI_IMPULSE_ERROR kws_pool_slide_live_assign(kws_pool_slide_live *sl, const size_t *streams, size_t n, const uint32_t *member)
+{
+    if (!sl) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lk(sl->p->mu);
+    if (n > 0 && (!streams || !member)) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    const size_t S = sl->assign.size(), K = sl->p->m.size();
+    std::vector<char> named(S, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (streams[i] >= S) return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: stream %zu of %zu", i, streams[i], S);
+        if (named[streams[i]]) return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: stream %zu named twice", i, streams[i]);
+        named[streams[i]] = 1;
+        if (member[i] >= K && member[i] != KWS_POOL_NONE) return fail(KWS_ERROR_BAD_ARGUMENT, "entry %zu: member %u is at or above the pool's %zu", i, member[i], K);
+    }
+    // (no per-member state and no device table: a push reads the members on the host, under the pool's lock, so a member may change
+    // between any two pushes)
+    for (size_t i = 0; i < n; ++i) sl->assign[streams[i]] = member[i];
+    return EI_IMPULSE_OK;
+}
+
+EI_IMPULSE_ERROR kws_pool_slide_live_window_count(const kws_pool_slide_live *sl, size_t stream, size_t n_new, size_t *n_windows)
+{
+    if (!sl) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lk(sl->p->mu);
+    return kws_slide_live_window_count(sl->core, stream, n_new, n_windows);
+}
+
+EI_IMPULSE_ERROR kws_pool_slide_live_push_device(kws_pool_slide_live *sl, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets,
+                                                 const size_t *lengths, float *scores, float *features, size_t *n_windows, void *stream)
+{
+    if (!sl) return fail(KWS_ERROR_BAD_ARGUMENT, "null argument");
+    if (!scores && !features) return fail(KWS_ERROR_BAD_ARGUMENT, "no output requested: scores and features are NULL");
+    kws_pool *p = sl->p;
+    std::unique_lock<std::mutex> own(p->mu);
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t s = (hipStream_t)stream;
+    PoolUse use(p, s, false, std::move(own));
+    PoolWindows ctx{ p, scores, features };
+    ctx.by_entry(sl->assign.data(), streams, n_windows, n);
+    return kws_slide_live_run(sl->core, n, streams, pcm, offsets, lengths, scores ? scores : features, n_windows, p->stride, 0, 0, pool_window_finish, &ctx, s);
 }
 
 #pragma GCC visibility pop

@@ -34,6 +34,11 @@ int kws_launch_pool_nn_mfma(const KwsBankRec *recs, const KwsPoolItem *items, in
 // in HBM; raw and scores [windows][stride]; maf [S][stride][taps + 1].
 int kws_launch_pool_maf_live(const float *raw, float *scores, const long long *meta, int n_act, int stride, const uint32_t *assign, const int *labels, int k_full,
                              float *maf, hipStream_t stream);
+// The moving average of a pool scan: one thread per (recording with windows, column < stride), a fresh filter each; member [n_rec] (a
+// member, or KWS_POOL_NONE: the recordings that have windows, in the order of wbase [n_rec + 1]) and labels [K] in HBM; raw and scores
+// [windows][stride], which may be the same buffer.
+int kws_launch_pool_maf_scan(const float *raw, float *scores, const long long *wbase, int n_rec, int stride, const uint32_t *member, const int *labels,
+                             hipStream_t stream);
 
 // ---- host side (kws_pool.cpp: includes kws_internal.h first) ----------------------------------------------------------------------------------
 #ifdef KWS_INTERNAL
@@ -44,6 +49,7 @@ struct kws_pool {
     int device = 0;
     int cp = 0;                            // bytes of an activation row of block 0: every member's (they share the feature matrix's columns)
     size_t stride = 0;                     // columns of a score row: the most labels any member has
+    size_t most = 0;                       // the first member that has them (the slide's bound on windows x labels is its plan's)
     KwsBankRec *d_rec = nullptr;           // [K]
     int *d_labels = nullptr;               // [K]
     float *feat = nullptr;                 // the shared feature matrix of calls without `features`
@@ -51,6 +57,7 @@ struct kws_pool {
     hipEvent_t ev = nullptr;               // end of the last call's work
     bool ev_used = false;
     BankUpload<int> table;                 // a call's items, then its row list: one chunk's at a time
+    BankUpload<uint32_t> scan_members;     // a scan's members, one per recording that has windows (the table's host copy is the last chunk's items)
     std::vector<int> fill;                 // [K] scratch of the list builder
     std::mutex mu;
 };
@@ -61,9 +68,10 @@ struct kws_pool {
 KWS_INTERNAL size_t kws_pool_items(const uint32_t *member, size_t n, size_t K, int item_rows, std::vector<int> &out, std::vector<int> &fill);
 // the first of n entries that is neither a member < K nor KWS_POOL_NONE: its index, or n
 KWS_INTERNAL size_t kws_pool_member_check(const uint32_t *member, size_t n, size_t K);
-// The per-window member table of a live push, as kws_bank_window_routes builds the routes: entry i has n_windows[i] windows of member
-// assign[streams[i]].
-KWS_INTERNAL void kws_pool_window_members(const uint32_t *assign, const size_t *streams, const size_t *n_windows, size_t n, std::vector<uint32_t> &out);
+// The per-window member table of a call, as kws_bank_window_routes builds the routes: entry i has n_windows[i] windows of member
+// assign[index[i]] (a live push: the session's members by stream), or assign[i] where index is NULL (a recording call: the call's members
+// by recording).
+KWS_INTERNAL void kws_pool_window_members(const uint32_t *assign, const size_t *index, const size_t *n_windows, size_t n, std::vector<uint32_t> &out);
 // Every named member's network from the feature matrix feat [n][F] (device): row i's scores go to scores + (row0 + i) * stride.
 KWS_INTERNAL EI_IMPULSE_ERROR pool_networks(kws_pool *p, const float *feat, size_t n, const uint32_t *member, float *scores, size_t row0, hipStream_t s);
 #endif

@@ -2,6 +2,7 @@
 // matrix-core shape behind ONE float feature matrix, each row scored by the one member it names.
 //   kws_pool_nn_mfma_kernel<CP>   every member's network in one launch over a flat table of work items in HBM: one workgroup per item
 //   kws_pool_maf_live_kernel      continuous mode's filter of a live push on rows of `stride` floats, the member being the stream's assignment
+//   kws_pool_maf_scan_kernel      the same for a recording scan: a fresh filter per recording, the member being the recording's
 // The network kernel is built from the bank kernel's pieces, unchanged (kws_bank_nn_dev.h: bank_nn_stage, bank_quantize_row; kws_nn_int8_dev.h:
 // nn_mfma_clip), so a row's scores are those of its member's own kws_nn_mfma_kernel launch bit for bit.  nn_mfma_clip stores a clip's scores
 // at scores[clip * fc_out + lane] and reads `clip` otherwise only for the parity taps, which a pool call does not request: with clip = 0 and
@@ -101,6 +102,38 @@ __global__ __launch_bounds__(64) void kws_pool_maf_live_kernel(const float *__re
 }
 
 // ---------------------------------------------------------------------------------------------------------
+//  The scan's moving average: thread t = a * stride + l is recording a (of the n that have windows), column l.  The member is the
+//  recording's, from the table uploaded with the call; the thread ends before any read of a row if the recording names nobody or the column
+//  is at or above the member's label count.  Otherwise it is kws_scan_maf_kernel's arithmetic (kws_scan_kernels.hip), operation for
+//  operation: fresh taps and a running sum of zero, the index from 0, subtract the oldest tap, add the new value, store it as the tap,
+//  out = sum / (float)taps -- on rows of `stride` floats from wbase[a] to wbase[a + 1].  raw and scores may be the same buffer (a scan
+//  without raw_scores filters in place), so neither is __restrict__.  A body of its own: kws_pool_maf_live_kernel stays what it is.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void kws_pool_maf_scan_kernel(const float *raw, float *scores, const long long *__restrict__ wbase, int n, int stride,
+                                                               const uint32_t *__restrict__ members, const int *__restrict__ labels)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)n * stride) return;
+    const int a = (int)(t / stride);
+    const int l = (int)(t - (long long)a * stride);
+    const uint32_t member = members[a];
+    if (member == KWS_POOL_NONE || l >= labels[member]) return;
+    float buf[KWS_POOL_TAPS];
+#pragma unroll
+    for (int j = 0; j < KWS_POOL_TAPS; ++j) buf[j] = 0.0f;
+    float rs = 0.0f;
+    int idx = 0;
+    for (long long g = wbase[a]; g < wbase[a + 1]; ++g) {
+        const float v = raw[(size_t)g * stride + l];
+        rs -= buf[idx];
+        rs += v;
+        buf[idx] = v;
+        scores[(size_t)g * stride + l] = rs / (float)KWS_POOL_TAPS;
+        if (++idx >= KWS_POOL_TAPS) idx = 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 //  launchers (called from kws_pool.cpp)
 // ---------------------------------------------------------------------------------------------------------
 int kws_launch_pool_nn_mfma(const KwsBankRec *recs, const KwsPoolItem *items, int n_items, const int *rows, int cp, const float *features, float *scores, int stride,
@@ -123,5 +156,15 @@ int kws_launch_pool_maf_live(const float *raw, float *scores, const long long *m
     if (n <= 0) return 0;
     hipLaunchKernelGGL(kws_pool_maf_live_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, raw, scores, live_meta(meta, n_act), n_act, stride, assign, labels,
                        k_full, maf);
+    return (int)hipGetLastError();
+}
+
+int kws_launch_pool_maf_scan(const float *raw, float *scores, const long long *wbase, int n_rec, int stride, const uint32_t *member, const int *labels,
+                             hipStream_t stream)
+{
+    (void)hipGetLastError();
+    const long long n = (long long)n_rec * stride;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(kws_pool_maf_scan_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, raw, scores, wbase, n_rec, stride, member, labels);
     return (int)hipGetLastError();
 }

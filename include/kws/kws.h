@@ -749,12 +749,39 @@ EI_IMPULSE_ERROR kws_bank_slide_live_route(kws_bank_slide_live *sl, const size_t
  *                     [windows of the push][stride], entry after entry.  An assigned stream's rows, filtered and raw, are the bits of its
  *                     member's own kws_live_* session fed the same pushes.  A push to an unassigned stream advances its carry and counts
  *                     its windows in n_windows, but writes no row and touches no filter state.  The moving average is ONE launch per push.
- * Not built: float32 and other-family members, recording scans and slides, live one-shot windows, the cepstra-in call, device-resident
- * member arrays, KWS_MODE_FAST. */
+ * Recordings, live one-shot windows, cepstra in.  What a bank serves of these a pool serves too, each being the first member's pipeline
+ * with the pool's finishing step.  scores (and raw_scores) are [windows of the call][stride] in the order of the single-model call; a
+ * window's member is its recording's (scan, slide) or its stream's (live).  A window of a recording or stream that names KWS_POOL_NONE
+ * keeps its place in the matrix.  A named window's row holds, in columns 0 .. labels - 1 of its member, the bits of that member's own
+ * KWS_MODE_EXACT call on that recording alone (live: of the member's own session fed the same pushes), raw and filtered alike.  Nothing
+ * else of scores / raw_scores is written: not the columns at or above the member's label count, not a KWS_POOL_NONE window's row, not a row
+ * past the call.  `features`, where a call has it, is written for every window or row, KWS_POOL_NONE ones included, with the single-model
+ * call's bits.  The front end runs ONCE through the first member for ALL recordings or streams of the call, the ones that name nobody
+ * included -- its launches are exactly those of the first member's own call -- so a caller who wants no work done for a recording drops it
+ * from the call.  The networks are one launch per gathered chunk of windows (64 MiB of cepstra) whatever K.  Every refusal comes before
+ * anything is enqueued and names the first offending entry: an index at or above K that is not KWS_POOL_NONE (named as "recording", "row"
+ * or "entry"), no output requested, a NULL pool or session, NULL member with a non-empty call, a stream out of range or named twice
+ * (KWS_ERROR_BAD_ARGUMENT), and whatever the single-model call refuses, with its code (a bad slicing, hop or flags, too many windows, NULL
+ * lengths).  Locks: the pool's and the first member's, as above.
+ *   kws_pool_scan_recordings_device   kws_scan_recordings_device for a pool, recording r by member[r].  scores is required; with raw_scores
+ *                     == NULL the moving average filters in place.  A fresh filter per recording; the moving average is ONE launch per call,
+ *                     and none when no recording with windows names a member.  The members of the recordings that have windows go up with
+ *                     the call (4 bytes each).
+ *   kws_pool_slide_recordings_device  kws_slide_recordings_device for a pool, recording r by member[r].  scores and features both NULL:
+ *                     refused.  The bound on windows x labels holds at the stride (kws_slide_plan of the member with the most labels).
+ *   kws_pool_cmvn_inference_device    kws_cmvn_inference_batch_device for a pool: B rows of cepstra, row i by member[i].
+ *   kws_pool_slide_live_*   kws_slide_live_* for a pool: one session of S streams on the first member; no state per member.  A fresh
+ *                     session assigns every stream to KWS_POOL_NONE; kws_pool_slide_live_assign sets the members of n streams (HOST arrays;
+ *                     host-only: no device table and no wait) and may change a stream's member between any two pushes, as
+ *                     kws_bank_slide_live_route may.  Reset keeps assignments.  kws_pool_slide_live_push_device has
+ *                     kws_slide_live_push_device's arguments; scores is [windows of the push][stride], entry after entry.  A push to an
+ *                     unassigned stream advances its carry and counts its windows in n_windows, but writes no score row.
+ * Not built: float32 and other-family members, device-resident member arrays, KWS_MODE_FAST, a tenant object lighter than a kws_handle. */
 #define KWS_POOL_MAX 4096
 #define KWS_POOL_NONE 0xffffffffu
 typedef struct kws_pool kws_pool;
 typedef struct kws_pool_live kws_pool_live;
+typedef struct kws_pool_slide_live kws_pool_slide_live;
 EI_IMPULSE_ERROR kws_pool_create(kws_handle *const *members, size_t K, kws_pool **out);
 void kws_pool_destroy(kws_pool *p);
 size_t kws_pool_size(const kws_pool *p);
@@ -773,6 +800,22 @@ EI_IMPULSE_ERROR kws_pool_live_window_count(const kws_pool_live *lv, size_t stre
 EI_IMPULSE_ERROR kws_pool_live_push_device(kws_pool_live *lv, size_t n, const size_t *streams, const int16_t *pcm, const size_t *offsets,
                                            const size_t *lengths, const int *finish, float *scores, float *raw_scores, size_t *n_windows,
                                            void *stream);
+EI_IMPULSE_ERROR kws_pool_scan_recordings_device(kws_pool *p, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                 const uint32_t *member /* [R] */, size_t slice_samples, float *scores, float *raw_scores, void *stream);
+EI_IMPULSE_ERROR kws_pool_slide_recordings_device(kws_pool *p, const int16_t *pcm, const size_t *offsets, const size_t *lengths, size_t R,
+                                                  const uint32_t *member /* [R] */, size_t hop_samples, int flags, float *scores, float *features,
+                                                  void *stream);
+EI_IMPULSE_ERROR kws_pool_cmvn_inference_device(kws_pool *p, const float *mfcc, size_t B, const uint32_t *member /* [B] */, float *scores,
+                                                float *features, void *stream);
+EI_IMPULSE_ERROR kws_pool_slide_live_create(kws_pool *p, size_t S, size_t hop_samples, int flags, kws_pool_slide_live **out);
+void kws_pool_slide_live_destroy(kws_pool_slide_live *sl);
+int kws_pool_slide_live_path(const kws_pool_slide_live *sl);
+EI_IMPULSE_ERROR kws_pool_slide_live_reset(kws_pool_slide_live *sl, const size_t *streams, size_t n);
+EI_IMPULSE_ERROR kws_pool_slide_live_assign(kws_pool_slide_live *sl, const size_t *streams, size_t n, const uint32_t *member);
+EI_IMPULSE_ERROR kws_pool_slide_live_window_count(const kws_pool_slide_live *sl, size_t stream, size_t n_new, size_t *n_windows);
+EI_IMPULSE_ERROR kws_pool_slide_live_push_device(kws_pool_slide_live *sl, size_t n, const size_t *streams, const int16_t *pcm,
+                                                 const size_t *offsets, const size_t *lengths, float *scores, float *features, size_t *n_windows,
+                                                 void *stream);
 
 /* ---- multi-GPU: clips shard contiguously over the GPUs of one node (rank r owns clips [r*B, (r+1)*B)), tables are
  * replicated, nothing is exchanged inside the pipeline; the one collective is the all-gather of the per-clip scores over xGMI.
