@@ -350,6 +350,28 @@ def test_quant_edge_models_against_recorded_reference(group, oracle, tmp_path):
         assert quant_edge_not_vacuous(key, r["edited"], r["fc"]) is None, (key, quant_edge_not_vacuous(key, r["edited"], r["fc"]))
 
 
+@pytest.mark.parametrize("name", __import__("pool_envelope_testlib").PINNED)
+def test_pool_envelope_corners_against_recorded_reference(name, oracle, tmp_path):
+    """tests/golden/pool_envelope_l476.npz: what the reference's op registrations gave for every corner graph of the pool envelope at 49x13
+    (tests/pool_envelope_testlib.py; the two graphs outside the matrix-core shape included) on the 24 rows of quant_edge_inputs -- the int8
+    output, the FULLY_CONNECTED output and a digest of the pooled tensors.  tests/test_gpu_pool_envelope.py compares pools and banks with the
+    restatement alone; this holds the restatement to the reference at those graphs where the reference is not built."""
+    from kws_testlib import OracleModel, quant_edge_digest, quant_edge_golden_rows, quant_edge_inputs, quant_edge_run
+    from pool_envelope_testlib import PINNED, PINNED_WIDTH, envelope_golden, member_blob
+    g = envelope_golden()
+    assert sorted(g) == sorted(PINNED)
+    blob = member_blob(PINNED_WIDTH, name)
+    p = tmp_path / "m.kwsm"
+    p.write_bytes(blob)
+    om = OracleModel(oracle, str(p))
+    r = quant_edge_run(lambda q: om.nn_invoke(q, taps=True), blob, ("fc",), quant_edge_inputs(om.n_features, golden_rows=True))
+    assert len(r["out"]) == len(quant_edge_golden_rows()) and r["out"].shape[1] == om.n_labels
+    assert (r["out"] == g[name]["out"]).all() and (r["fc"] == g[name]["fc"]).all(), name
+    assert (quant_edge_digest(r["pooled"]) == g[name]["pooled_sha"]).all(), name
+    # against a vacuous pin: the FULLY_CONNECTED outputs are not one value (the one-filter graphs leave few)
+    assert len(np.unique(r["fc"])) >= (2 if "min" in name else 5), name
+
+
 @pytest.mark.parametrize("group", sorted({k.split("/")[0] + "/" + k.split("/")[1] for k in __import__("kws_testlib").f32_all_cases()}))
 def test_f32_edge_graphs_against_recorded_reference(group, oracle, tmp_path):
     """tests/golden/f32_edges_l476.npz: what the reference's float op registrations gave for every graph of kws_testlib.F32_BLOCKINGS and

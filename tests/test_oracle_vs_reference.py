@@ -391,6 +391,28 @@ def test_quant_edge_models_through_reference_op_registrations(group, oracle, ref
         assert quant_edge_not_vacuous(key, r["edited"], r["fc"]) is None, (key, quant_edge_not_vacuous(key, r["edited"], r["fc"]))
 
 
+@pytest.mark.parametrize("name", __import__("pool_envelope_testlib").PINNED)
+def test_pool_envelope_corners_through_reference_op_registrations(name, oracle, reference, tmp_path):
+    """The corner graphs of the pool envelope at 49x13 (tests/pool_envelope_testlib.py: 32 x 8 taps / 16 x 8 taps with 48 labels, one tap and
+    one filter, convolution biases without ADD, 33 labels behind one filter, one label, the stock graph, and the two graphs outside the
+    matrix-core shape), each through the reference's own op registrations on the 384 input rows of the quantisation-edge pins: the
+    restatement equals it on every int8 tensor and on the output."""
+    from kws_testlib import OracleModel, quant_edge_inputs
+    from pool_envelope_testlib import PINNED_WIDTH, member_blob
+    blob = member_blob(PINNED_WIDTH, name)
+    p = tmp_path / "m.kwsm"
+    p.write_bytes(blob)
+    om = OracleModel(oracle, str(p))
+    fcs = []
+    for q in quant_edge_inputs(om.n_features):
+        out, taps = reference.graph_run(blob, q)
+        oo, ot = om.nn_invoke(q, taps=True)
+        assert (out == oo).all(), name
+        assert all((a == t).all() for a, t in zip(taps, ot) if a.dtype == np.int8), name
+        fcs.append(np.array(ot[len(ot) - 2]))
+    assert len(np.unique(np.stack(fcs))) >= (2 if "min" in name else 5), name
+
+
 @pytest.mark.parametrize("name", __import__("general_dsp_shapes").NAMES)
 def test_general_envelope_shapes_pinned(name, oracle, reference, tmp_path):
     """Every served shape of tests/general_dsp_shapes.py -- the ends of what build_dsp_plan hands the general kernels: mixed-radix and degenerate

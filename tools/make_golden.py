@@ -20,6 +20,7 @@ Without arguments: leaves_l476, e2e_l476, deep_l476, continuous_l476, f32_twin_l
   --only-mfe-other-length  mfe_other_length_l432.npz  the same for the MFE-block model, composed from the L432 copy's leaves
   --only-quant-edges       quant_edges_l476.npz     the int8 graphs at the edges of their quantisation (kws_testlib.QUANT_EDGES)
   --only-f32-edges         f32_edges_l476.npz       the float32 graphs over every blocking and at float edges (kws_testlib.F32_BLOCKINGS / F32_EDGES)
+  --only-pool-envelope     pool_envelope_l476.npz   the corner graphs of the pool envelope at 49x13 (pool_envelope_testlib.PINNED)
 """
 import os
 import sys
@@ -191,6 +192,26 @@ def quant_edges(ref):
     out["out"], out["fc"], out["pooled_sha"] = np.concatenate(out["out"]), np.concatenate(out["fc"]), np.stack(out["pooled_sha"])
     np.savez_compressed(os.path.join(GOLDEN, "quant_edges_l476.npz"), **out)
     print("quant_edges_l476.npz", os.path.getsize(os.path.join(GOLDEN, "quant_edges_l476.npz")), "bytes;", len(keys), "models")
+
+
+def pool_envelope(ref):
+    """Every corner graph of tests/pool_envelope_testlib.py at 49x13 through the reference's own op registrations on the 24 input rows of
+    quant_edge_inputs(golden_rows=True): the int8 output and the FULLY_CONNECTED output in full, the pooled tensors as per-row digests.
+    Recorded results only: models and inputs are regenerated in the tests."""
+    import eon_import
+    from kws_testlib import quant_edge_digest, quant_edge_inputs, quant_edge_run
+    from pool_envelope_testlib import PINNED, PINNED_WIDTH, member_blob
+    out = {"keys": np.array(PINNED), "n_labels": [], "out": [], "fc": [], "pooled_sha": []}
+    for name in PINNED:
+        blob = member_blob(PINNED_WIDTH, name)
+        tens, _, t_in, _, _ = eon_import.parse_blob(blob)
+        r = quant_edge_run(lambda q: ref.graph_run(blob, q), blob, ("fc",), quant_edge_inputs(tens[t_in]["nbytes"], golden_rows=True))
+        out["n_labels"].append(r["out"].shape[1])
+        out["out"].append(r["out"].reshape(-1)); out["fc"].append(r["fc"].reshape(-1)); out["pooled_sha"].append(quant_edge_digest(r["pooled"]))
+    out["n_labels"] = np.int32(out["n_labels"])
+    out["out"], out["fc"], out["pooled_sha"] = np.concatenate(out["out"]), np.concatenate(out["fc"]), np.stack(out["pooled_sha"])
+    np.savez_compressed(os.path.join(GOLDEN, "pool_envelope_l476.npz"), **out)
+    print("pool_envelope_l476.npz", os.path.getsize(os.path.join(GOLDEN, "pool_envelope_l476.npz")), "bytes;", len(PINNED), "models")
 
 
 def f32_edges(ref):
@@ -403,6 +424,8 @@ def main():
         return quant_edges(ref)
     if "--only-f32-edges" in sys.argv:
         return f32_edges(ref)
+    if "--only-pool-envelope" in sys.argv:
+        return pool_envelope(ref)
     synth = Oracle()          # only used for kwso_synth_fill (shared integer generator)
     cfg = L476_CONFIG()
     os.makedirs(GOLDEN, exist_ok=True)
