@@ -144,8 +144,8 @@ struct KwsFastPlan {
     // [8][12] x float2 { tw[k], tw[2 k], tw[3 k] } for k = fl + 8 a, then [8][8] x float2 super twiddles of the lane's eight bin pairs -- read per
     // pass instead of living in 40 registers (a register reloaded from scratch inside the pass loop waits for the pass's sample prefetch: one counter)
     int twl_off;
-    // (wps = 3 only) two words in device memory, zero between launches: the ticket counter the kernel deals its clips out by, and the count of waves that
-    // have left (kws_fast.hip: the clip loop and the kernel's end).  (A launch that does not run to its end -- a device fault -- leaves them dirty: like the rest of
+    // (wps = 3 only) KWS_FAST_TICKET_WORDS ints in device memory, zero between launches: the ticket heads the kernel deals its clips out by, one per 128-byte
+    // line, and behind them, on a line of its own, the count of waves that have left (kws_fast_ticket.h; kws_fast.hip: the clip loop and the kernel's end).  (A launch that does not run to its end -- a device fault -- leaves them dirty: like the rest of
     // the handle's device state, they are only good for launches that complete.)
     int *tickets;
     // (wps = 3 only, and always 1 there: build_fast_fused gives a graph that cannot take it the two-wave layout) block 0's image ARRIVES SPLIT: cmvnw stores

@@ -21,6 +21,7 @@
 
 #include "kws_device.h"
 #include "kws_fast.h"
+#include "kws_fast_ticket.h"
 #include "kws_bfly_m2k1.h"
 #include "kws_fast_maxmin.h"
 // The second compilation of this file (kws_fast_w3.o, -DKWS_FAST_WPS=3: three waves per SIMD, <= 168 registers, the float32-network forms only) goes into the
@@ -1052,7 +1053,7 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
 }
 
 // PROF: development aid -- shader-clock totals per phase of wave 0 of workgroup 0 (tools/gpu_fast_phase_profile.py)
-#define KWS_FAST_NPHASE 20       // 0..8 phases, 9..11 detail of block 0, 12 + b: block b >= 1 on its own
+#define KWS_FAST_NPHASE 20       // 0..8 phases, 9..11 detail of block 0, 12 + b: block b >= 1 on its own (three waves per SIMD b <= 3: 16..18 are the clip's edge; 19: column 0's means)
 // the three-wave build's pass loop (each can be switched off on the compiler's command line, to be measured apart): a second copy of the mel phase for passes
 // of eight live frames, sample requests as scalar base + 32-bit lane offset, the frame energies' log once per clip
 #ifndef KWS_FAST_FULL_PASS
@@ -1071,6 +1072,8 @@ __device__ __forceinline__ float fast_cmvn(float *__restrict__ img, const float 
 #else
 #define KWS_FAST_ELOG(e) fast_log((e) == 0.0f ? FLT_EPSILON : (e))
 #endif
+// (PROF) the blocks behind the first that have a slot of their own: three waves per SIMD slots 16 .. 18 are the clip's edge (the pass loop)
+#define KWS_FAST_PROF_BLOCK(b) (KWS_FAST_WPS >= 3 ? (b) > 0 && (b) < 4 : (b) > 0)
 #define FPH(i) do { if (PROF) { const long long now_ = clock64(); ph[i] += now_ - tlast; tlast = now_; } } while (0)
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1181,14 +1184,15 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
     // (Until this round it was drawn when a clip ended and looked at when the next one ended.  Its round trip was over no sooner for that -- the next clip's
     // first wait for a load waited for it --, and carried through a whole clip it is the register the allocator gives up first wherever a phase grows by one: a
     // ticket that lives in scratch is waited for where it is drawn, a device-memory round trip per clip.)  The counter cleans up after
-    // itself -- a wave that leaves counts itself out, and the last one to do so zeroes both words (below the loop) --, so a launch needs nothing from the
+    // itself -- a wave that leaves counts itself out, and the last one to do so zeroes every head and the count (below the loop) --, so a launch needs nothing from the
     // host: no argument that changes from launch to launch, no memset.  Launches of a handle are serial (its flag
     // lists are too).
     // (a flat pointer on purpose: said to be device memory, the draw is rewritten as one add for the whole wave whose result is handed out lane by lane --
     // and waited for on the spot)
     // (ni is assigned where the ticket is looked at, in the PCM forms' spectral phase: a form that starts from cepstra would never leave this loop)
     static_assert(!FROM_CEP, "the forms that start from cepstra are not built for three waves per SIMD");
-    int *const tk = FP.tickets;
+    // (one head word served the whole grid until the heads were sharded: kws_fast_ticket.h says which ticket of which head is which clip)
+    int *const tk = FP.tickets + kws_fast_ticket_head(kws_fast_ticket_home((int)blockIdx.x));
     int ni = 0;
     for (int ci = blockIdx.x * n_waves + wave; ci < n_sel; ci = ni) {
         // (every draw is looked at in the clip that makes it: when the wave leaves the loop, every draw it made has been waited for)
@@ -1425,7 +1429,10 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         int touched = touch(1);
 #if KWS_FAST_WPS >= 3
         // the ticket: this clip's successor
-        ni = clip_stride + __builtin_amdgcn_readfirstlane(tv);
+        const int tk_home = kws_fast_ticket_home((int)blockIdx.x);
+        ni = kws_fast_ticket_clip(clip_stride, tk_home, __builtin_amdgcn_readfirstlane(tv));
+        // (a home shard that is past the last clip: the clip has no successor as far as its tail pass is concerned; the other shards are
+        // asked at the clip's end, below)
         const int next_clip = ni < n_sel ? ni : -1;                                    // the wave's next clip (paired tail pass)
 #endif
         const bool pair_tail = n_tail == 1 && !have_stash && next_clip >= 0;
@@ -1444,6 +1451,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
             const int fbase = KWS_FAST_MEL_CHUNK * q;
             const int f = fbase + fg;
             const bool live = f < nfr;
+            const long long ptop = PROF && KWS_FAST_WPS >= 3 ? clock64() : 0;                  // (PROF) the clip's edge: phase 0 of pass 0 on its own, see below
             cf u[4][4];                                                  // after the exchange: u[a][b] = position fl + 8 a + 32 b
             {
                 cf z[2][8];
@@ -1462,6 +1470,9 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                 fetch(q + 1, nxt);
                 asm volatile("" : : "v"(touched));
                 touched = touch(q + 2);
+                // (PROF; tools/gpu_fast_clip_edges.py) slot 18: phase 0 of every pass 0, from the pass's top -- the wait for the clip's first samples and its wrap
+                // sample is in it --, slot 16: phase 0 of the other passes, slot 17: the clips this wave took
+                if (PROF && KWS_FAST_WPS >= 3) { ph[q == 0 ? 18 : 16] += clock64() - ptop; ph[17] += q == 0; }
                 FPH(0);
                 // kf_bfly2 (m = 1, twiddle 1) on the (i4 = 0, 1) pairs, then kf_bfly4 (m = 2) on the sums (k = 0) and the
                 // differences (k = 1): outputs 8 j + k + 2 i
@@ -1908,7 +1919,15 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                 if (rem > 1) sum += v.y;
                 if (rem > 2) sum += v.z;
             }
+#if KWS_FAST_WPS >= 3
+            // (the divisor is converted here, from a copy the compiler cannot see through: converted once in front of the clip loop it holds a vector register
+            // through every phase of every clip -- the one the allocator then sends to scratch, reloaded per clip, as soon as the pass loop grows by one)
+            int win_here = win_size;
+            asm volatile("" : "+s"(win_here));
+            if (lane_m < nfr) elog[lane_m] = __fdiv_rn(sum, (float)win_here);
+#else
             if (lane_m < nfr) elog[lane_m] = __fdiv_rn(sum, (float)win_size);
+#endif
             WAVE_SYNC();
         }
         if (PROF) { const long long now_ = clock64(); ph[19] += now_ - tlast; }
@@ -2023,7 +2042,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
                 fast_dwconv(k, cur, oth, shared, lane_b, o_stride, o_cp);
                 WAVE_SYNC();
                 float *tmp = cur; cur = oth; oth = tmp;
-                if (PROF && b > 0) { const long long now_ = clock64(); ph[12 + b] += now_ - tlast; }
+                if (PROF && KWS_FAST_PROF_BLOCK(b)) { const long long now_ = clock64(); ph[12 + b] += now_ - tlast; }
                 FPH(6 + (b > 0));
                 continue;
             }
@@ -2063,7 +2082,7 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
             else fast_pool(k, stage, oth, lane_b, o_stride, o_cp, pooled);
             WAVE_SYNC();
             float *tmp = cur; cur = oth; oth = tmp;
-            if (PROF && b > 0) { const long long now_ = clock64(); ph[12 + b] += now_ - tlast; }
+            if (PROF && KWS_FAST_PROF_BLOCK(b)) { const long long now_ = clock64(); ph[12 + b] += now_ - tlast; }
             FPH(6 + (b > 0));
         }
         {
@@ -2097,17 +2116,28 @@ __global__ __launch_bounds__(256 * KWS_FAST_WPS, KWS_FAST_WPS) void kws_fast_ker
         WAVE_SYNC();
         FPH(8);
         }   // NET
+#if KWS_FAST_WPS >= 3
+        // the home shard is past the last clip (a wave's last round only): one draw per other shard, each waited for on the spot -- here, where next to nothing
+        // is live, rather than where the ticket is looked at: there the walk costs the headline form a register it does not have
+        if (ni >= n_sel) {
+            ni = kws_fast_ticket_walk(clip_stride, n_sel, kws_fast_ticket_home((int)blockIdx.x), [&](int s) {
+                int v = 0;
+                if (lane == 0) v = __hip_atomic_fetch_add(FP.tickets + kws_fast_ticket_head(s), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return __builtin_amdgcn_readfirstlane(v);
+            });
+        }
+#endif
     }
 #if KWS_FAST_WPS >= 3
     // the ticket counter's clean-up: every draw of this wave has landed (its value was waited for: the clip loop), so the wave counts itself out; the last
-    // wave of the launch finds every other wave's count -- hence every draw -- behind it and zeroes both words for the next launch
+    // wave of the launch finds every other wave's count -- hence every draw -- behind it and zeroes every head and the count for the next launch
     if (lane == 0) {
         // (relaxed: the counters are only ever touched by atomics, which meet in one place, and each wave has waited for its own; an acquire / release
         // pair at agent scope writes back and invalidates the caches under the waves that are still running: +5 % on the whole launch)
-        const int gone = __hip_atomic_fetch_add(FP.tickets + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int gone = __hip_atomic_fetch_add(FP.tickets + kws_fast_ticket_gone(), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (gone == (int)(gridDim.x * (blockDim.x >> 6)) - 1) {
-            __hip_atomic_store(FP.tickets, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(FP.tickets + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int s = 0; s < KWS_FAST_TICKET_SHARDS; ++s) __hip_atomic_store(FP.tickets + kws_fast_ticket_head(s), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(FP.tickets + kws_fast_ticket_gone(), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 #endif

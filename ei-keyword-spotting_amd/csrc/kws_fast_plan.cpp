@@ -2,6 +2,7 @@
 // the audio is computed once per model on the host and uploaded.
 #include "kws_internal.h"
 #include "kws_bfly_m2k1.h"
+#include "kws_fast_ticket.h"
 #include <atomic>
 #include <cstdlib>
 
@@ -493,7 +494,7 @@ static EI_IMPULSE_ERROR finish_fast_plan(kws_handle *h, KwsFastPlan &F, std::vec
     F.tickets = nullptr;
     if (F.wps >= 3) {
         const int *dev = nullptr;
-        if ((e = h->upload(std::vector<int>(4, 0), &dev))) return e;
+        if ((e = h->upload(std::vector<int>(KWS_FAST_TICKET_WORDS, 0), &dev))) return e;       // (hipMalloc: aligned to more than a 128-byte line)
         F.tickets = const_cast<int *>(dev);
     }
     std::vector<KwsFastPlan> one(1, F);
